@@ -9,11 +9,10 @@ candidates.  Workload (per GPU): Franka Panda, 256 seeds x 4 line-search candida
 rollouts of 32 steps (padded 33) per step, 4-cuboid world.  Rollouts/s counts cost+gradient
 trajectory evaluations.
 
-Timing protocol (state-stable): a *block* = re-initialise the optimiser from the seeds, run
-``--warmup`` untimed iterations, then time EXACTLY ``--steps`` iterations + the arg-min exchange
-between barrier + synchronize pairs (MAX over ranks).  Blocks repeat until >= 0.25 s of timed work
-has been collected (every block starts from the same state, so the data-dependent culling of the
-collision passes cannot drift the figure); ``ms_per_step`` is the MEDIAN block time / steps.
+Timing protocol (state-stable): re-initialise the optimiser from the seeds, run ``--warmup`` untimed iterations, then
+time EXACTLY ``--steps`` iterations + the arg-min exchange between barrier + synchronize pairs (MAX over ranks);
+``ms_per_step`` is that time / steps.  Before it, every hipGraph the timed steps replay is captured and replayed once
+(each distinct chunk of iterations, not all ``--steps`` of them), so neither capture nor first launch is timed.
 
 ``--gpus N`` without a torchrun environment re-executes itself under ``torch.distributed.run``
 with N ranks (one per GPU, RCCL); ``n_gpus`` is only ever printed after an RCCL all-reduce over
@@ -21,11 +20,12 @@ exactly N ranks succeeded.  Weak scaling by default (256 seeds per rank); ``--sc
 splits 256 seeds over the ranks.  The only exchange of the path is the all-gather arg-min over
 seeds at the end of the timed steps.
 
-Prints ONE compact JSON line (< 4 KB, the last thing on stdout) on rank 0 with `roofline` (dominant
-kernel), `cpu_baseline` (the C oracle on the host cores, bounded sample) and the IK half of the
-metric; the full record -- fixed-state figures, the single-GPU shares of BASELINE configs C3 / C4 /
-C5 with their own rooflines, mesh world, solvers -- is written to bench_full.json (and
-gpurun_out/bench_full.json).
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, ``--dump-outputs DIR`` (what the
+last timed step computed, as .npy files) and ONE compact JSON line (< 4 KB, the last thing on stdout) on rank 0.
+``--full`` adds everything else, measured after the headline: a repeated-block reading of the same steps (median over
+blocks), `roofline` (dominant kernel), `cpu_baseline` (the C oracle on the host cores, bounded sample), the IK half of
+the metric, the single-GPU shares of BASELINE configs C3 / C4 / C5 with their own rooflines, mesh world, solvers, and
+for N > 1 the strong-scaling reading and the sharded C4 / C5 legs; the full record is written to bench_full.json.
 """
 
 from __future__ import annotations
@@ -64,7 +64,7 @@ def parse_args():
     ap.add_argument("--seeds", type=int, default=256, help="seeds per GPU (weak) / in total (strong)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline time budget per leg")
     ap.add_argument("--graph-iters", type=int, default=25,
                     help="L-BFGS iterations per captured graph (the reference's inner_iters, lbfgs_bspline_trajopt.yml)")
@@ -74,16 +74,22 @@ def parse_args():
                     help="drop-in kernel sequence (7 launches per rollout) instead of the fused rollout kernel")
     ap.add_argument("--shards", type=int, default=4,
                     help="seed shards of the optimiser on separate HIP streams of the GPU (1 = one batch, one stream)")
-    ap.add_argument("--no-ik", action="store_true", help="skip the secondary solver measurements (IK, trajopt solve)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C3 / C4 / C5 single-GPU shares")
-    ap.add_argument("--only", default="", help="comma list of secondary objects to run (c3,c4,c5,mesh,ik,fixed); default all")
+    ap.add_argument("--no-ik", action="store_true", help="with --full: skip the secondary solver measurements (IK, trajopt solve)")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the C3 / C4 / C5 single-GPU shares")
+    ap.add_argument("--only", default="", help="with --full: comma list of secondary objects to run (c3,c4,c5,mesh,ik,fixed); default all")
     ap.add_argument("--ik-problems", type=int, default=100)
     ap.add_argument("--ik-seeds", type=int, default=64)
-    ap.add_argument("--min-timed-s", type=float, default=MIN_TIMED_S)
-    ap.add_argument("--legs", action="store_true", help="also run the sharded C4 / C5 legs with one rank (they always run with --gpus > 1)")
+    ap.add_argument("--min-timed-s", type=float, default=MIN_TIMED_S,
+                    help="with --full: seconds of timed work the repeated-block reading collects (at least 5 blocks)")
+    ap.add_argument("--legs", action="store_true", help="with --full: also run the sharded C4 / C5 legs with one rank (they always run with --full --gpus > 1)")
     ap.add_argument("--selftest", action="store_true",
                     help="multi-rank plumbing only: init -> all-reduce -> one global arg-min -> destroy; prints the rank count the "
                          "collective saw, so that an RCCL / xGMI problem is told apart from a kernel problem")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else (repeated-block reading, roofline, CPU baselines, "
+                         "C3 / C4 / C5, mesh, IK and solvers, multi-GPU legs) and write bench_full.json; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed (per-seed best cost / knots, the arg-min exchange) as DIR/<name>.npy")
     ap.add_argument("--dist-timeout", type=float, default=float(os.environ.get("CUROBO_BENCH_DIST_TIMEOUT_S", "180")),
                     help="seconds a rank waits in a collective before it gives up (a rank that died must not hang the job)")
     return ap.parse_args()
@@ -137,6 +143,21 @@ def graphed(fn, reps, torch):
         for _ in range(reps):
             fn()
     return g
+
+
+def dump_outputs(path, opt, best_c, best_i, best_x, seeds, n_knots, dof):
+    """What a caller of the timed path receives after its last step, as float32 / float64 .npy files under `path`: the
+    optimiser's per-seed best cost and knots (this rank's seeds) and the winner of the arg-min exchange over all ranks."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {
+        "best_cost": opt.best_cost.detach().float().cpu().numpy().reshape(seeds),
+        "best_knots": opt.best_action.detach().float().cpu().numpy().reshape(seeds, n_knots, dof),
+        "argmin_cost": best_c.detach().float().cpu().numpy(),
+        "argmin_seed": best_i.detach().cpu().numpy().astype(np.float64),
+        "argmin_knots": best_x.detach().float().cpu().numpy().reshape(-1, n_knots, dof),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def usable_cores():
@@ -365,25 +386,37 @@ def main():
         linalg_hip.argmin_rows(row_buf, opt.best_cost.view(1, -1).contiguous(), opt.best_action.view(1, seeds, -1).contiguous(),
                                rank * seeds)
 
-    def run_steps(k, with_exchange=False):
-        """exactly k optimiser iterations (with_exchange: + the local stage of the arg-min exchange behind the last one)"""
-        one = opt.step if shards > 1 else opt._opt_step
+    def run_chunk(n, last):
+        """n optimiser iterations as one chunk (last: + the local stage of the arg-min exchange behind them)"""
         if args.no_graph:
-            for _ in range(k):
+            one = opt.step if shards > 1 else opt._opt_step
+            for _ in range(n):
                 one()
-            if with_exchange:
+            if last:
                 local_exchange_stage()
             return
-        chunks = step_chunks(k)
-        for ci, n in enumerate(chunks):
-            last = with_exchange and ci == len(chunks) - 1
-            if n == G and not last:
-                opt.run_inner()
-                continue
-            key = (n, last)
-            if key not in rem_graphs:  # its own (cached) graph, so any step count runs at replay speed
-                rem_graphs[key] = opt.make_graph(n, after=local_exchange_stage if last else None)
-            rem_graphs[key].replay()
+        if n == G and not last:
+            opt.run_inner()
+            return
+        key = (n, last)
+        if key not in rem_graphs:  # its own (cached) graph, so any step count runs at replay speed
+            rem_graphs[key] = opt.make_graph(n, after=local_exchange_stage if last else None)
+        rem_graphs[key].replay()
+
+    def chunks_of(k, with_exchange=False):
+        parts = [k] if args.no_graph else step_chunks(k)
+        return [(n, with_exchange and i == len(parts) - 1) for i, n in enumerate(parts)]
+
+    def run_steps(k, with_exchange=False):
+        """exactly k optimiser iterations (with_exchange: + the local stage of the arg-min exchange behind the last one)"""
+        for n, last in chunks_of(k, with_exchange):
+            run_chunk(n, last)
+
+    def warm_steps(k, with_exchange=False):
+        """every DISTINCT chunk of run_steps(k) once: its graph is captured (state restored) and replayed, so the timed
+        steps neither capture nor launch a graph for the first time -- without running all k iterations first"""
+        for n, last in dict.fromkeys(chunks_of(k, with_exchange)):
+            run_chunk(1 if args.no_graph else n, last)
 
     def sync_all():
         torch.cuda.synchronize()
@@ -402,9 +435,10 @@ def main():
         # the one real exchange of the path: arg-min over the seeds of all ranks (1 problem)
         return global_argmin_of_rows(row_buf)
 
-    # every graph the timed region replays is captured before it; the exchange is warmed too
-    run_steps(max(args.warmup, 1))
-    run_block()
+    # every graph the timed region replays is captured and launched once before it; the exchange is warmed too
+    warm_steps(max(args.warmup, 1))
+    warm_steps(args.steps, with_exchange=True)
+    global_argmin_of_rows(row_buf)
     sync_all()
 
     def timed_block():
@@ -422,21 +456,26 @@ def main():
             el = float(tt.item())
         return el, res
 
-    blocks, total, t_wall = [], 0.0, time.perf_counter()
-    while True:
-        el, (best_c, best_i, best_x) = timed_block()
-        blocks.append(el)
-        total += el
-        go_on = (total < args.min_timed_s or len(blocks) < 5) and len(blocks) < 2000 and time.perf_counter() - t_wall < 60.0
-        if world > 1:  # every rank must take the same decision
-            flag = torch.tensor([1.0 if go_on else 0.0], device=device if backend == "nccl" else "cpu")
-            dist.broadcast(flag, 0)
-            go_on = bool(flag.item() > 0.5)
-        if not go_on:
-            break
-    elapsed = float(np.median(blocks))
+    elapsed, res = timed_block()
+    best_c, best_i, best_x = (t.clone() for t in res)  # (views of the exchange buffer, which a later block rewrites)
     rollouts_per_step = seeds * nls * world
     value = rollouts_per_step * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, opt, best_c, best_i, best_x, seeds, cfg.n_knots, kin.num_dof)
+
+    blocks = []
+    if args.full:  # the same block repeated from the seeds until >= --min-timed-s of timed work (and >= 5 blocks): its spread
+        total, t_wall = 0.0, time.perf_counter()
+        while True:
+            blocks.append(timed_block()[0])
+            total += blocks[-1]
+            go_on = (total < args.min_timed_s or len(blocks) < 5) and len(blocks) < 2000 and time.perf_counter() - t_wall < 60.0
+            if world > 1:  # every rank must take the same decision
+                flag = torch.tensor([1.0 if go_on else 0.0], device=device if backend == "nccl" else "cpu")
+                dist.broadcast(flag, 0)
+                go_on = bool(flag.item() > 0.5)
+            if not go_on:
+                break
 
     out = None
     if rank == 0:
@@ -462,9 +501,8 @@ def main():
             },
             "timing": {
                 "protocol": "block = reinitialise from the seeds, `warmup` untimed iterations, then `steps` timed iterations + "
-                            "arg-min exchange between barrier+synchronize pairs (max over ranks); ms_per_step = median block / steps",
-                "blocks": len(blocks), "timed_total_s": round(total, 4), "block_ms_median": round(elapsed * 1e3, 4),
-                "block_ms_min": round(min(blocks) * 1e3, 4), "block_ms_max": round(max(blocks) * 1e3, 4),
+                            "arg-min exchange between barrier+synchronize pairs (max over ranks); ms_per_step = one block / steps",
+                "block_ms": round(elapsed * 1e3, 4),
             },
             "best_cost": float(best_c[0].item()), "best_seed": int(best_i[0].item()),
         }
@@ -475,10 +513,17 @@ def main():
             except Exception as e:  # noqa: BLE001
                 out[key] = {"error": f"{type(e).__name__}: {e}"}
 
+        if blocks:
+            out["timing"]["repeated_blocks"] = {
+                "blocks": len(blocks), "timed_total_s": round(sum(blocks), 4), "block_ms_median": round(float(np.median(blocks)) * 1e3, 4),
+                "block_ms_min": round(min(blocks) * 1e3, 4), "block_ms_max": round(max(blocks) * 1e3, 4),
+                "ms_per_step_median": round(float(np.median(blocks)) / args.steps * 1e3, 5)}
+
         def roofline():
             return c2_roofline(args, opt, rollout, cfg, kin, seed_t, seeds, shards, nls, elapsed / args.steps, torch)
-        guarded("roofline", roofline)
-        if world == 1:
+        if args.full:
+            guarded("roofline", roofline)
+        if world == 1 and args.full:
             if want("c3") and not args.no_configs:
                 guarded("c3_ur10e_voxel", lambda: c3_benchmark(device, torch))
             if want("c4") and not args.no_configs:
@@ -502,7 +547,7 @@ def main():
                     except Exception as e:  # noqa: BLE001
                         out["cpu_baseline"]["optimizer_stage"] = {"error": f"{type(e).__name__}: {e}"}
     world_alive = True
-    if world > 1 and args.scaling == "weak":
+    if args.full and world > 1 and args.scaling == "weak":
         # the strong-scaling reading of the same job (north_star: 256 seeds in total), measured in the same launch
         strong = run_leg_on_all_ranks(
             "strong_scaling", lambda a, w, r, d, b, t, di: strong_scaling_leg(a, w, r, kin, scene, cfg, ocfg, model, start_t, bounds, d, b, t, di),
@@ -510,7 +555,7 @@ def main():
         world_alive = not strong.get("fatal", False)
         if rank == 0:
             out["strong_scaling"] = strong
-    if (world > 1 or args.legs) and not args.no_configs and world_alive:
+    if args.full and (world > 1 or args.legs) and not args.no_configs and world_alive:
         # BASELINE configs 4 and 5 are multi-GPU jobs: their sharded legs (every rank runs them; rank 0 reports)
         legs = {}
         for key, fn in (("c4_humanoid_seed_shard", c4_sharded_leg), ("c5_batch_planner_problem_shard", c5_sharded_leg)):
@@ -521,7 +566,12 @@ def main():
         if rank == 0:
             out["multi_gpu_legs"] = legs
     if rank == 0:  # the line goes out BEFORE the last barrier: a peer that died must not take the measured headline with it
-        emit(out)
+        if args.full:
+            emit(out)
+        else:  # a plain run writes no full record: the line alone
+            line = compact_line(out)
+            line.pop("full_record", None)
+            print(json.dumps(line), flush=True)
     if world > 1 and world_alive:
         try:
             dist.barrier()

@@ -1,10 +1,12 @@
 """The C-ABI library loads on a CPU-only machine and exports every symbol the header declares;
 the Python backend modules expose the reference's function names with the reference's
-positional argument order (checked against the reference sources when they are present)."""
+positional argument order (a table recorded from the reference sources, tests/golden/reference_backend_signatures.json;
+checked against the sources themselves when they are present)."""
 
 import ast
 import ctypes
 import inspect
+import json
 import os
 
 import pytest
@@ -82,15 +84,23 @@ def test_extension_backend_modules(module):
         assert callable(getattr(mod, fn)), f"{module}.{fn}"
 
 
+# the reference backend's positional arguments per function, recorded from its sources (cuda_core_backend/<module>.py)
+REF_SIGNATURES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_backend_signatures.json")
+
+
 def _ref_signature(module, fn):
-    tree = ast.parse(open(os.path.join(REF_BACKEND, f"{module}.py")).read())
-    for node in tree.body:
-        if isinstance(node, ast.FunctionDef) and node.name == fn:
-            return [a.arg for a in node.args.args]
-    raise KeyError(fn)
+    if os.path.isdir(REF_BACKEND):  # the sources themselves where they are present: the recorded table must still match them
+        tree = ast.parse(open(os.path.join(REF_BACKEND, f"{module}.py")).read())
+        live = next(([a.arg for a in node.args.args] for node in tree.body
+                     if isinstance(node, ast.FunctionDef) and node.name == fn), None)
+        assert live is not None, f"{module}.{fn} not in the reference backend"
+        with open(REF_SIGNATURES) as fh:
+            assert json.load(fh)[module][fn] == live, f"{REF_SIGNATURES} is stale for {module}.{fn}"
+        return live
+    with open(REF_SIGNATURES) as fh:
+        return json.load(fh)[module][fn]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_BACKEND), reason="reference checkout not present")
 @pytest.mark.parametrize("module,fn", [(m, f) for m in sorted(EXPECTED) for f in EXPECTED[m]])
 def test_positional_arguments_match_reference(module, fn):
     import importlib

@@ -32,7 +32,7 @@ def test_selftest_counts_the_ranks_and_checks_the_exchange(device):
 
 def test_a_rank_that_fails_its_leg_does_not_hang_the_job(device):
     # rank 1 raises at the start of the C4 leg; rank 0 is then alone in the leg's collectives until the 20 s timeout
-    p, out = _run(["--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-ik", "--min-timed-s", "0.02", "--dist-timeout", "20"],
+    p, out = _run(["--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-ik", "--min-timed-s", "0.02", "--dist-timeout", "20"],
                   {"CUROBO_BENCH_FAIL_LEG": "c4_humanoid_seed_shard:1"}, 600)
     assert out is not None, (p.returncode, p.stderr[-3000:])
     assert out["n_gpus"] == 2 and out["value"] > 0, "the headline is reported"

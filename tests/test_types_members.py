@@ -1,6 +1,8 @@
 """Host types without the reference checkout: the members of ``JointState`` / ``ToolPose`` / ``GoalToolPose`` that the CPU harness holds to
 the reference's classes (tests/golden/compare_joint_state.py, compare_goal_tool_pose.py) checked here against their definitions, so that
 the suite covers them on a machine that has only this repository."""
+import os
+
 import pytest
 import torch
 
@@ -216,6 +218,35 @@ def test_ik_result_clone_and_merges():
     assert torch.equal(w.js_solution.position[1], b.solution[1])
 
 
+REF_CUROBO = "/root/reference/curobo"
+REF_TASKS = os.path.join(REF_CUROBO, "content", "configs", "task")
+# the values these tests read from the reference's task files (and its MPCSolverCfg iteration counts), recorded from them
+REF_TASK_VALUES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_task_configs.json")
+
+
+def _reference_task_file(name):
+    """the recorded blocks of a reference task file (``name`` relative to content/configs/task) or ``solver_mpc_cfg``; where
+    the reference checkout is present, the record must still match the files themselves"""
+    import json
+    import re
+
+    import yaml
+
+    with open(REF_TASK_VALUES) as fh:
+        rec = json.load(fh)[name]
+    if os.path.isdir(REF_TASKS):
+        if name == "solver_mpc_cfg":
+            src = open(os.path.join(REF_CUROBO, "_src", "solver", "solver_mpc_cfg.py")).read()
+            live = {k: int(re.search(rf"{k}: int = (\d+)", src).group(1)) for k in rec}
+        else:
+            with open(os.path.join(REF_TASKS, name)) as fh:
+                y = yaml.safe_load(fh)
+            live = {k: ({kk: y[k][kk] for kk in rec[k]} if k == "rollout" else y[k]) for k in rec}
+            live = {k: ({kk: {n: v[kk][n] for n in rec[k][kk]} for kk in v} if k == "rollout" else v) for k, v in live.items()}
+        assert json.loads(json.dumps(live)) == rec, f"{REF_TASK_VALUES} is stale for {name}"
+    return rec
+
+
 def test_mpc_reference_task_is_the_reference_file():
     """``MPCSolverCfg.reference_task()`` against content/configs/task/mpc/lbfgs_mpc.yml, value by value (this package's own MPC defaults differ
     from that file on purpose; the option carries the file's)"""
@@ -227,11 +258,7 @@ def test_mpc_reference_task_is_the_reference_file():
 
     c = MPCSolverCfg.reference_task(goal_ik_seeds=8)
     assert c.goal_ik_seeds == 8 and c.rollout.non_terminal_pose_factor == 1.0
-    path = "/root/reference/curobo/content/configs/task/mpc/lbfgs_mpc.yml"
-    if not os.path.exists(path):
-        pytest.skip("needs the reference checkout")
-    with open(path) as fh:
-        y = yaml.safe_load(fh)
+    y = _reference_task_file("mpc/lbfgs_mpc.yml")
     cost, con, opt = y["rollout"]["cost_cfg"], y["rollout"]["constraint_cfg"], y["optimizer"]
     r, o = c.rollout, c.optimizer
     cs = cost["cspace_cfg"]
@@ -259,10 +286,8 @@ def test_mpc_reference_task_is_the_reference_file():
         dataclasses.replace(o, fixed_iters=False).improvement_thresholds()
     assert dataclasses.replace(o, fixed_iters=False, cost_relative_threshold=0.01).improvement_thresholds() == (0.0, 0.01)
     # the iteration counts are those of the reference's MPCSolverCfg (solver_mpc_cfg.py:75-78)
-    import re
-    src = open("/root/reference/curobo/_src/solver/solver_mpc_cfg.py").read()
-    warm = int(re.search(r"warm_start_optimization_num_iters: int = (\d+)", src).group(1))
-    cold = int(re.search(r"cold_start_optimization_num_iters: int = (\d+)", src).group(1))
+    it = _reference_task_file("solver_mpc_cfg")
+    warm, cold = it["warm_start_optimization_num_iters"], it["cold_start_optimization_num_iters"]
     assert (c.cold_start_optimization_num_iters, c.warm_start_optimization_num_iters) == (cold, warm) == (300, 200)
 
 
@@ -279,11 +304,7 @@ def test_mppi_reference_tasks_are_the_reference_files(task, path):
     assert c.num_problems == 3
     with pytest.raises(ValueError):
         MPPICfg.reference_task("mpc")
-    full = os.path.join("/root/reference/curobo/content/configs/task", path)
-    if not os.path.exists(full):
-        pytest.skip("needs the reference checkout")
-    with open(full) as fh:
-        o = yaml.safe_load(fh)["optimizer"]
+    o = _reference_task_file(path)["optimizer"]
     for k in ("gamma", "init_cov", "kappa", "beta", "step_size_cov", "step_size_mean", "null_act_frac"):
         assert float(o[k]) == getattr(c, k), k
     for k in ("num_iters", "inner_iters", "num_particles", "sample_per_problem", "seed", "update_cov"):

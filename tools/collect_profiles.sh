@@ -12,7 +12,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT/summary"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --no-cpu-baseline --no-ik --steps 100 --warmup 20"
+BENCH="python $ROOT/bench.py --full --no-cpu-baseline --no-ik --steps 100 --warmup 20"
 if [ -z "${PMC_ONLY:-}" ]; then
 echo "== kernel trace + stats (default command)"
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- $BENCH > "$OUT/bench_under_trace.json" 2> "$OUT/trace.log"
@@ -25,13 +25,13 @@ for shape in 1024 256; do
     name=$(echo $grp | cut -d' ' -f1)
     echo "== pmc $grp, $shape trajectories per launch"
     timeout 70 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d "$OUT/pmc_${shape}_$name" -- \
-      python $ROOT/bench.py --no-cpu-baseline --no-ik --steps 20 --warmup 10 --shards 1 --seeds $seeds > /dev/null 2> "$OUT/pmc_${shape}_$name.log" \
+      python $ROOT/bench.py --full --no-cpu-baseline --no-ik --steps 20 --warmup 10 --shards 1 --seeds $seeds > /dev/null 2> "$OUT/pmc_${shape}_$name.log" \
       || echo "   (failed or timed out)"
   done
 done
 if [ -z "${PMC_ONLY:-}" ]; then
 echo "== plain bench (no profiler)"
-timeout 300 python "$ROOT/bench.py" > "$OUT/summary/${TAG}_bench_c2.json" 2> "$OUT/bench.log"
+timeout 300 python "$ROOT/bench.py" --full > "$OUT/summary/${TAG}_bench_c2.json" 2> "$OUT/bench.log"
 fi
 python "$ROOT/tools/summarize_profiles.py" "$OUT" "$TAG"
 ls -la "$OUT/summary"

@@ -13,9 +13,9 @@ mkdir -p "$OUT/summary"
 bash "$ROOT/tools/collect_profiles.sh" "$TAG"
 cd /tmp && export TMPDIR=/tmp
 for cfgname in c3 c4 c5; do
-  echo "== kernel trace + stats, bench.py --only $cfgname"
+  echo "== kernel trace + stats, bench.py --full --only $cfgname"
   timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$cfgname" -- \
-    python "$ROOT/bench.py" --no-cpu-baseline --only $cfgname --steps 20 --warmup 5 > "$OUT/summary/${TAG}_bench_${cfgname}_under_kernel_trace.json" 2> "$OUT/trace_$cfgname.log" \
+    python "$ROOT/bench.py" --full --no-cpu-baseline --only $cfgname --steps 20 --warmup 5 > "$OUT/summary/${TAG}_bench_${cfgname}_under_kernel_trace.json" 2> "$OUT/trace_$cfgname.log" \
     || echo "   (failed or timed out)"
   f=$(find "$OUT/trace_$cfgname" -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp "$f" "$OUT/summary/${TAG}_kernel_stats_bench_${cfgname}.csv"

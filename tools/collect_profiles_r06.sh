@@ -19,10 +19,10 @@ cd /tmp && export TMPDIR=/tmp
 if [ -z "${COUNTERS_ONLY:-}" ]; then
   echo "== kernel trace + stats: default bench command"
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_default" -- \
-    python "$ROOT/bench.py" --no-cpu-baseline --no-ik --no-configs > "$OUT/summary/${TAG}_bench_c2_under_kernel_trace.json" 2> "$OUT/trace_default.log" || echo "   (failed)"
+    python "$ROOT/bench.py" --full --no-cpu-baseline --no-ik --no-configs > "$OUT/summary/${TAG}_bench_c2_under_kernel_trace.json" 2> "$OUT/trace_default.log" || echo "   (failed)"
   echo "== kernel trace + stats: the driver's command"
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_driver" -- \
-    python "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-ik --no-configs > "$OUT/summary/${TAG}_bench_driver_cmd_under_kernel_trace.json" 2> "$OUT/trace_driver.log" || echo "   (failed)"
+    python "$ROOT/bench.py" --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-ik --no-configs > "$OUT/summary/${TAG}_bench_driver_cmd_under_kernel_trace.json" 2> "$OUT/trace_driver.log" || echo "   (failed)"
 fi
 echo "== kernel trace + stats: tools/run_kernels_once.py $CFGS"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_kernels" -- \

@@ -61,7 +61,7 @@ def main():
                 continue
             grid, wg = col(r, "Grid_Size", "Grid_Size_X"), col(r, "Workgroup_Size", "Workgroup_Size_X")
             ctr[int(grid or 0) // max(int(wg or 1), 1)][col(r, "Counter_Name")].append(float(col(r, "Counter_Value")))
-    rec = {"command": "rocprofv3 --pmc <group> --kernel-trace --output-format csv -- python bench.py --no-cpu-baseline --no-ik "
+    rec = {"command": "rocprofv3 --pmc <group> --kernel-trace --output-format csv -- python bench.py --full --no-cpu-baseline --no-ik "
                       "--steps 20 --warmup 10 --shards 1 --seeds <trajectories/4> (groups: FETCH_SIZE WRITE_SIZE | TCC_HIT_sum "
                       "TCC_MISS_sum, one per pass; single-stream variant of the default command, see tools/collect_profiles.sh)",
            "kernel": "rollout_trajectory_fused_kernel",
