@@ -23,6 +23,7 @@ from typing import Callable, List, Optional, Tuple
 import torch
 
 from ..backends import optimization as optimization_hip
+from ..util.graph_capture import capture_graph
 
 
 @dataclass
@@ -120,7 +121,7 @@ class LBFGSOpt:
         self.best_iteration, self.current_iteration = z(B, dt=torch.int16), z(B, dt=torch.int16)
         self.converged = z(B, dt=torch.uint8)
         self.exploration_idx, self.selected_idx = z(B, N, dt=torch.int32), z(B, N, dt=torch.int32)
-        self._graph = None
+        self.reset_cuda_graph()
 
     # ------------------------------------------------------------------ one iteration
     def _evaluate_search_points(self) -> None:
@@ -211,39 +212,22 @@ class LBFGSOpt:
             self._prepare_search_points()
 
     def capture(self) -> None:
-        """Warm up on a side stream, then record ``inner_iters`` iterations into one hipGraph."""
-        saved = [t.clone() for t in self._state_tensors()]
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            self._opt_step()
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        torch.cuda.synchronize(self.device)
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            self._opt_iters()
-        for t, s in zip(self._state_tensors(), saved):
-            t.copy_(s)
-        torch.cuda.synchronize(self.device)
+        """one warm-up iteration, then ``inner_iters`` iterations recorded into one hipGraph (state restored after)"""
+        self._graph, _ = capture_graph(self._opt_iters, restore=self._state_tensors(), warmup=self._opt_step, device=self.device)
 
     def make_graph(self, n_iters: int, after=None) -> "torch.cuda.CUDAGraph":
         """a hipGraph of ``n_iters`` iterations (optimiser state is restored after the capture); ``after`` (optional callable)
         is captured behind them"""
-        saved = [t.clone() for t in self._state_tensors()]
-        self._opt_step()  # warm-up outside the capture
-        if after is not None:
-            after()
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            for _ in range(n_iters):
+        def steps(n):
+            for _ in range(n):
                 self._opt_step()
             if after is not None:
                 after()
-        for t, s in zip(self._state_tensors(), saved):
-            t.copy_(s)
-        torch.cuda.synchronize(self.device)
-        return g
+        return capture_graph(lambda: steps(n_iters), restore=self._state_tensors(), warmup=lambda: steps(1), device=self.device)[0]
+
+    def reset_cuda_graph(self) -> None:
+        """the next ``run_inner`` captures again (call after changing anything the recorded launches depend on)"""
+        self._graph = None
 
     def _enough_converged(self) -> bool:
         """reference BestTracker.check_convergence (optim/components/best_tracker.py:109-118); on a seed shard the count is

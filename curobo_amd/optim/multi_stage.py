@@ -78,5 +78,5 @@ class MultiStageOptimizer:
 
     def reset_cuda_graph(self) -> None:
         for opt in self.optimizers:
-            if hasattr(opt, "_graph"):
-                opt._graph = None
+            if hasattr(opt, "reset_cuda_graph"):
+                opt.reset_cuda_graph()

@@ -20,6 +20,7 @@ from typing import Callable, List, Optional, Tuple
 
 import torch
 
+from ..util.graph_capture import capture_graph
 from ..util.stream_scope import forked_stream
 from .lbfgs import LBFGSOpt, LBFGSOptCfg
 
@@ -70,36 +71,26 @@ class PipelinedLBFGS:
         """one iteration of every shard (eager launches)"""
         self._forked(lambda o: o._opt_step())
 
+    def _state_tensors(self) -> List[torch.Tensor]:
+        return [t for o in self.opts for t in o._state_tensors()]
+
     def capture(self) -> None:
-        saved = [[t.clone() for t in o._state_tensors()] for o in self.opts]
-        self.step()  # warm-up outside the capture (lazy module loads, workspace set-up)
-        torch.cuda.synchronize(self.device)
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            self._forked(lambda o: o._opt_iters())
-        for o, sv in zip(self.opts, saved):
-            for t, s in zip(o._state_tensors(), sv):
-                t.copy_(s)
-        torch.cuda.synchronize(self.device)
+        """one warm-up iteration of every shard, then ``inner_iters`` iterations of every shard recorded into one hipGraph"""
+        self._graph, _ = capture_graph(lambda: self._forked(lambda o: o._opt_iters()), restore=self._state_tensors(),
+                                       warmup=self.step, device=self.device)
 
     def make_graph(self, n_iters: int, after: Optional[Callable[[], None]] = None) -> "torch.cuda.CUDAGraph":
         """a hipGraph of ``n_iters`` iterations of every shard (state is restored after the capture); ``after`` is captured
         behind the join of the shards (e.g. the local stage of an arg-min exchange: one replay = iterations + reduction)"""
-        saved = [[t.clone() for t in o._state_tensors()] for o in self.opts]
-        self.step()
-        if after is not None:
-            after()  # warm-up outside the capture
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._forked(lambda o: [o._opt_step() for _ in range(n_iters)])
+        def steps(n):
+            self._forked(lambda o: [o._opt_step() for _ in range(n)])
             if after is not None:
                 after()
-        for o, sv in zip(self.opts, saved):
-            for t, s in zip(o._state_tensors(), sv):
-                t.copy_(s)
-        torch.cuda.synchronize(self.device)
-        return g
+        return capture_graph(lambda: steps(n_iters), restore=self._state_tensors(), warmup=lambda: steps(1), device=self.device)[0]
+
+    def reset_cuda_graph(self) -> None:
+        """the next ``run_inner`` captures again"""
+        self._graph = None
 
     def run_inner(self) -> None:
         if self.use_cuda_graph:

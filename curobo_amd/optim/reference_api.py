@@ -134,7 +134,8 @@ class LBFGSOpt:
         return all(bool(r.update_params(**kwargs)) for r in self.rollout_list)
 
     def reset_cuda_graph(self) -> None:
-        self._opt._graph = None
+        if self._opt is not None:
+            self._opt.reset_cuda_graph()
 
     def reset_seed(self) -> None:
         for r in self.rollout_list:

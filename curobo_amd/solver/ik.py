@@ -23,6 +23,7 @@ from ..optim import LBFGSOpt, LBFGSOptCfg, PipelinedLBFGS
 from ..robot.kinematics_params import KinematicsParams
 from ..rollout.ik_rollout import IKRollout, IKRolloutCfg
 from ..scene.data import SceneData
+from ..util.graph_capture import capture_graph
 from .seed_ik import SeedIKSolver, SeedIKSolverCfg
 
 
@@ -258,18 +259,26 @@ class IKSolver:
         best = self.optimizer.optimize(seeds.reshape(P * S, 1, D))
         return self._get_result(best.reshape(P * S, D).contiguous(), return_seeds)
 
+    def _drop_captures(self) -> None:
+        """every graph this solver replays is recorded again on next use"""
+        self.optimizer.reset_cuda_graph()
+        self._result_graphs.clear()
+
     def _set_envs(self, env_idx: Optional[torch.Tensor]) -> None:
         """``env_idx`` [P]: problem p is checked against scene environment env_idx[p] (reference batch-env
         IK, ``idxs_env`` / ``use_multi_env``); every rollout row takes the environment of its problem."""
         mode = env_idx is not None
         if not mode and getattr(self, "_env_mode", None) is False:
             return  # still "every row in environment 0": the index buffers are zero already (five fill launches per solve otherwise)
-        if mode != getattr(self, "_env_mode", False):
-            self.optimizer._graph = None  # the launches differ between the two modes: capture again
-        self._env_mode = mode
         env = env_idx.to(self.device).long().view(self.P) if mode else None
-        for ro, rows in zip(self.rollouts + [self.metrics_rollout], self._row_goals + [self._mrow_goal]):
+        rollouts = self.rollouts + [self.metrics_rollout]
+        for ro, rows in zip(rollouts, self._row_goals + [self._mrow_goal]):
             ro.update_env_query_idx(env[rows.long()] if mode else None)
+        # the mode and every rollout's choice of its fused launch (made in update_env_query_idx) decide the recorded launches
+        launches = (mode, [ro._env_runs_ok for ro in rollouts])
+        if launches != getattr(self, "_env_launches", (False, [True] * len(rollouts))):
+            self._drop_captures()
+        self._env_mode, self._env_launches = mode, launches
 
     def _get_result(self, q: torch.Tensor, return_seeds: int) -> IKResult:
         """``_get_result_eager`` replayed from a hipGraph when the process is alone (the ~25 small launches of the
@@ -279,15 +288,10 @@ class IKSolver:
 
         if not self._use_graph or (dist.is_available() and dist.is_initialized()):
             return self._get_result_eager(q, return_seeds)
-        key = (return_seeds, bool(getattr(self, "_env_mode", False)), bool(getattr(self, "_cur_on", False)))
+        key = (return_seeds, bool(getattr(self, "_cur_on", False)))
         if key not in self._result_graphs:
-            q_static = torch.empty_like(q)
-            q_static.copy_(q)
-            self._get_result_eager(q_static, return_seeds)  # warm-up outside the capture
-            torch.cuda.synchronize(self.device)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                out = self._get_result_eager(q_static, return_seeds)
+            q_static = q.clone()
+            graph, out = capture_graph(lambda: self._get_result_eager(q_static, return_seeds), device=self.device)
             self._result_graphs[key] = (graph, q_static, out, getattr(self, "_rank_pack", None))
         graph, q_static, out, pack = self._result_graphs[key]
         q_static.copy_(q)

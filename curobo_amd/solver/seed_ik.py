@@ -36,6 +36,7 @@ from ..backends import cost as cost_hip
 from ..backends import kinematics as kinematics_hip
 from ..backends import linalg as linalg_hip
 from ..robot.kinematics_params import KinematicsParams
+from ..util.graph_capture import capture_graph
 
 
 @dataclass
@@ -300,15 +301,8 @@ class SeedIKSolver:
             self._inner_iterations()
             return
         if self._vel_active not in self._graphs:
-            saved = [t.clone() for t in self._state()]
-            self._lm_iteration()  # warm-up outside the capture
-            torch.cuda.synchronize(self.device)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                self._inner_iterations()
-            for t, s in zip(self._state(), saved):
-                t.copy_(s)
-            self._graphs[self._vel_active] = graph
+            self._graphs[self._vel_active], _ = capture_graph(self._inner_iterations, restore=self._state(),
+                                                              warmup=self._lm_iteration, device=self.device)
         self._graphs[self._vel_active].replay()
 
     def _state(self):
@@ -403,11 +397,7 @@ class SeedIKSolver:
                     self._seeds_static = torch.empty_like(seeds)
                 if seeds is not None:  # (None: the broadcast above already filled the buffer)
                     self._seeds_static.copy_(seeds)
-                self._solve_from_seeds(self._seeds_static, return_seeds, None)  # warm-up outside the capture
-                torch.cuda.synchronize(self.device)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    out = self._solve_from_seeds(self._seeds_static, return_seeds, None)
+                graph, out = capture_graph(lambda: self._solve_from_seeds(self._seeds_static, return_seeds, None), device=self.device)
                 self._solve_graphs[return_seeds] = (graph, out, self._select_pack)
             elif seeds is not None:
                 self._seeds_static.copy_(seeds)

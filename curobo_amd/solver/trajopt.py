@@ -41,6 +41,7 @@ from ..optim import LBFGSOpt, LBFGSOptCfg
 from ..robot.kinematics_params import KinematicsParams
 from ..rollout.trajopt_rollout import TrajOptRollout, TrajOptRolloutCfg, joint_limit_vector
 from ..scene.data import SceneData
+from ..util.graph_capture import capture_graph
 from .ik import IKSolver, IKSolverCfg
 
 
@@ -406,11 +407,16 @@ class TrajOptSolver:
             out.append(x.contiguous())
         return out[0], out[1]
 
+    def _drop_captures(self) -> None:
+        """every graph this solver replays is recorded again on next use"""
+        self.optimizer.reset_cuda_graph()
+        self._pass_graphs.clear()
+
     def _set_problem(self, start, goal_position, goal_quat, env_idx, seed_goal, use_implicit_goal) -> None:
         P, S, D, T = self.P, self.S, self.kin.num_dof, self.kin.num_pose_links
         mode = env_idx is not None
         if mode != getattr(self, "_env_mode", False):
-            self.optimizer._graph = None  # the multi-env flag is a kernel argument: capture again
+            self._drop_captures()  # the multi-env flag and the environment index are kernel arguments: capture again
         self._env_mode = mode
         env = env_idx.to(self.device).long().view(P) if mode else None
         gp, gq = self._goal_sets(goal_position, goal_quat)
@@ -500,15 +506,7 @@ class TrajOptSolver:
             buf = dict(knots=knots.clone(), cur_dt=cur_dt.clone(), start=start.to(self.device).reshape(-1, self.kin.num_dof).expand(self.P, -1).clone(),
                        seed_goal=seed_goal.clone())
             run = lambda: self._metrics_pass_eager(buf["knots"], buf["cur_dt"], buf["start"], buf["seed_goal"], use_implicit_goal, static_steps)  # noqa: E731
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):  # warm-up off the capture (allocations, lazily built tables)
-                run()
-                run()
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                out_dt, out = run()
+            graph, (out_dt, out) = capture_graph(run, warmups=2, device=self.device)
             g = self._pass_graphs[key] = dict(graph=graph, buf=buf, out_dt=out_dt, out=out)
         b = g["buf"]
         b["knots"].copy_(knots); b["cur_dt"].copy_(cur_dt); b["seed_goal"].copy_(seed_goal.reshape(b["seed_goal"].shape))

@@ -550,3 +550,59 @@ def test_captured_metrics_pass_is_the_eager_pass(oracle, device):
         torch.testing.assert_close(a.position_error, b.position_error, rtol=1e-3, atol=1e-7)
         for key in ("success", "feasible_interpolated", "in_limits", "no_scene_collision"):
             assert torch.equal(a.all_seeds[key], b.all_seeds[key]), key
+
+
+def test_env_mode_switch_recaptures_the_metrics_pass(oracle, device):
+    """One solver with graphs solves without ``env_idx`` (every problem in env 0, open), then with every problem in env 1, where a
+    block sits across the straight joint-space line from the start to each goal.  The captured metrics pass bakes in the
+    multi-env flag and the environment, so the switch has to record it again: the second solve must check env 1's collisions
+    exactly as an eager pass does."""
+    import dataclasses
+
+    from curobo_amd.robot.kinematics_params import KinematicsParams
+    from curobo_amd.scene import SceneData, cuboid_scene_arrays
+    from curobo_amd.solver import TrajOptSolver, TrajOptSolverCfg
+    from curobo_amd.workloads import start_configuration
+
+    model = load_model("franka")
+    md = model.as_dict()
+    kin = KinematicsParams.from_model(model, device)
+    table = {"dims": [2.0, 2.0, 0.2], "pose": [0.0, 0.0, -0.1, 1, 0, 0, 0]}
+
+    def free(q, envs):
+        sph = oracle.kinematics_forward(q, md)["robot_spheres"].reshape(len(q), 1, -1, 4)
+        return (oracle.self_collision(sph, model.sphere_padding, model.collision_pairs, 1.0)["distance"] == 0) & \
+            (oracle.scene_collision(sph, cuboid_scene_arrays(envs), 1.0, 0.0)["distance"].sum((1, 2)) == 0)
+
+    start = start_configuration(model)
+    cand = sample_q(model, 300, seed=21, scale=0.6)
+    cand = cand[free(cand, [[table]])]
+    # the block: on the tool frame half way along the line to the first goal; goals: free in env 1, line through the block
+    mid = oracle.kinematics_forward(0.5 * (start + cand[:1]), md)["link_pos"][0, 0]
+    env1 = [table, {"dims": [0.15] * 3, "pose": [*map(float, mid), 1, 0, 0, 0]}]
+    assert free(start[None], [env1])[0]
+    line = np.stack([start + s * (cand - start) for s in np.linspace(0, 1, 11)[1:-1]], 1)
+    hit = ~free(line.reshape(-1, model.num_dof), [env1]).reshape(len(cand), -1).all(1)
+    P = 4
+    goals = cand[free(cand, [env1]) & hit][:P]
+    assert len(goals) == P
+    fk = oracle.kinematics_forward(goals, md)
+    gp, gq = torch.as_tensor(fk["link_pos"][:, 0]), torch.as_tensor(fk["link_quat"][:, 0])
+    scene = SceneData.from_arrays(cuboid_scene_arrays([[table], env1]), device)
+    cfg = TrajOptSolverCfg(num_seeds=4)
+    captured = TrajOptSolver(kin, scene, P, dataclasses.replace(cfg, capture_metrics_pass=True))
+    eager = TrajOptSolver(kin, scene, P, dataclasses.replace(cfg, capture_metrics_pass=False))
+    st = torch.as_tensor(start)
+    in_env1 = torch.ones(P, dtype=torch.int32, device=device)
+    for solver in (captured, eager):
+        solver.solve_pose(st, gp, gq)
+    a, b = captured.solve_pose(st, gp, gq, env_idx=in_env1), eager.solve_pose(st, gp, gq, env_idx=in_env1)
+    torch.cuda.synchronize()
+    assert captured._pass_graphs and not eager._pass_graphs
+    assert torch.equal(a.success, b.success) and bool(a.success.any())
+    assert a.finetune_passes == b.finetune_passes
+    torch.testing.assert_close(a.traj_dt, b.traj_dt, rtol=1e-6, atol=0)
+    torch.testing.assert_close(a.knots, b.knots, rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(a.position_error, b.position_error, rtol=1e-3, atol=1e-7)
+    for key in ("success", "feasible_interpolated", "in_limits", "no_scene_collision"):
+        assert torch.equal(a.all_seeds[key], b.all_seeds[key]), key
