@@ -4,9 +4,10 @@ Purpose: the reference's sphere-obst
 kernels, i.e. typed Python functions that Warp compiles for the GPU.  Warp is not installed here and cannot be (no
 network), so those kernels never ran next to the oracle.  Their SOURCE is plain Python though: with this module on
 ``sys.path`` as ``warp``, the reference's own, unmodified kernel functions are imported and executed thread by thread on
-the CPU, in fp32, and their outputs become golden vectors (``tests/golden/make_scene_warp_golden.py``).  What is restated
-here are only Warp's intrinsics (vector / quaternion / transform algebra, C-style integer division, atomics, function
-overloads by struct type): a few lines each, from their published definitions; every branch, activation rule, sweep
+the CPU, in fp32, and their outputs become golden vectors (``tests/golden/make_scene_warp_golden.py``,
+``make_mesh_warp_golden.py``).  What is restated here are only Warp's intrinsics (vector / quaternion / transform algebra,
+C-style integer division, atomics, function overloads by struct type, and the triangle-mesh queries ``Mesh``,
+``mesh_query_point`` and ``mesh_eval_position``): a few lines each, from their published definitions; every branch, activation rule, sweep
 loop and accumulation order that is executed is the reference's.
 
 Test infrastructure only: nothing under ``curobo_amd/`` imports this.
@@ -670,6 +671,129 @@ def sub(a, b):
 
 def launch_tiled(kernel, dim, inputs=(), outputs=(), block_dim=None, **kw):
     return launch(kernel, dim, inputs=inputs, outputs=outputs)
+
+
+# ----------------------------------------------------------------------------- triangle meshes
+_meshes = {}
+
+
+class Mesh:
+    """``wp.Mesh(points=, indices=)``: a triangle mesh whose ``.id`` (uint64) the mesh queries resolve through a registry of
+    this module.  No BVH: the queries below visit every triangle, which finds the same minimum (a BVH changes the order of
+    the visit only, and the callers keep queries off exact ties)."""
+
+    def __init__(self, points=None, indices=None, velocities=None, support_winding_number=False, bvh_constructor=None, **kw):
+        self.points = points if isinstance(points, array) else array(np.asarray(points, np.float32), dtype=vec3)
+        self.indices = indices if isinstance(indices, array) else array(np.asarray(indices, np.int32).reshape(-1), dtype=int32)
+        self._v = np.asarray(self.points.a, np.float32).reshape(-1, 3)
+        self._f = np.asarray(self.indices.a, np.int64).reshape(-1, 3)
+        self.id = uint64(len(_meshes) + 1)
+        _meshes[int(self.id)] = self
+
+    def refit(self):
+        return None
+
+
+class MeshQueryPoint:
+    """result of ``mesh_query_point``: ``result`` (found), ``sign`` (-1 inside / +1 outside), ``face``, barycentrics ``u``, ``v``"""
+
+    def __init__(self, result=False, sign=_F(0.0), face=0, u=_F(0.0), v=_F(0.0)):
+        self.result, self.sign, self.face, self.u, self.v = np.bool_(result), _F(sign), int32(face), _F(u), _F(v)
+
+
+def _closest_barycentrics(a, b, c, p):
+    """warp/native/intersect.h closest_point_to_triangle (Ericson, Real-Time Collision Detection 5.1.5), fp32, vectorised
+    over triangles: (u, v) with closest = u a + v b + (1 - u - v) c"""
+    f = lambda x: x.astype(np.float32)  # noqa: E731
+    dot3 = lambda x, y: f(f(f(x[:, 0] * y[:, 0]) + f(x[:, 1] * y[:, 1])) + f(x[:, 2] * y[:, 2]))  # noqa: E731
+    ab, ac, ap = f(b - a), f(c - a), f(p - a)
+    d1, d2 = dot3(ab, ap), dot3(ac, ap)
+    bp = f(p - b)
+    d3, d4 = dot3(ab, bp), dot3(ac, bp)
+    cp = f(p - c)
+    d5, d6 = dot3(ab, cp), dot3(ac, cp)
+    vc, vb, va = f(f(d1 * d4) - f(d3 * d2)), f(f(d5 * d2) - f(d1 * d6)), f(f(d3 * d6) - f(d5 * d4))
+    one = np.float32(1.0)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        v_ab = f(d1 / f(d1 - d3))
+        w_ca = f(d2 / f(d2 - d6))
+        w_bc = f(f(d4 - d3) / f(f(d4 - d3) + f(d5 - d6)))
+        den = f(one / f(f(va + vb) + vc))
+        v_in, w_in = f(vb * den), f(vc * den)
+        u_in = f(f(one - v_in) - w_in)
+    conds = [(d1 <= 0) & (d2 <= 0),
+             (d3 >= 0) & (d4 <= d3),
+             (vc <= 0) & (d1 >= 0) & (d3 <= 0),
+             (d6 >= 0) & (d5 <= d6),
+             (vb <= 0) & (d2 >= 0) & (d6 <= 0),
+             (va <= 0) & (f(d4 - d3) >= 0) & (f(d5 - d6) >= 0)]
+    zero = np.zeros_like(d1)
+    u = np.select(conds, [zero + one, zero, f(one - v_ab), zero, f(one - w_ca), zero], u_in)
+    v = np.select(conds, [zero, zero + one, v_ab, zero, zero, f(one - w_bc)], v_in)
+    return u, v
+
+
+def _mesh_query_inside(m, p):
+    """warp/native/mesh.h mesh_query_inside: rays along +x, +y, +z; each ray's nearest hit (t > 0) is a back face when the
+    ray leaves through it (dir . (ab x ac) > 0); inside iff all three rays hit a back face.  Moeller-Trumbore over every
+    triangle in double precision (the callers keep rays off edges and vertices, where fp32 and fp64 may part)."""
+    v = m._v.astype(np.float64)
+    a, b, c = v[m._f[:, 0]], v[m._f[:, 1]], v[m._f[:, 2]]
+    ab, ac, tv = b - a, c - a, np.asarray(p, np.float64)[None] - a
+    votes = 0
+    for axis in range(3):
+        d = np.zeros(3)
+        d[axis] = 1.0
+        pv = np.cross(d[None], ac)
+        det = np.einsum("ij,ij->i", ab, pv)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u = np.einsum("ij,ij->i", tv, pv) / det
+            qv = np.cross(tv, ab)
+            w = (qv @ d) / det
+            t = np.einsum("ij,ij->i", ac, qv) / det
+            ok = (det != 0) & (u >= 0) & (u <= 1) & (w >= 0) & (u + w <= 1) & (t > 0)
+        if ok.any():
+            k = np.flatnonzero(ok)[np.argmin(t[ok])]
+            votes += int(det[k] < 0)
+    return votes == 3
+
+
+def mesh_query_point(id, point, max_dist):  # noqa: A002
+    """warp/native/mesh.h mesh_query_point: the closest point of every triangle (fp32 barycentrics, candidate point
+    u p + v q + w r), kept when its squared distance is STRICTLY below the best so far, which starts at max_dist^2; sign by
+    mesh_query_inside when a point was found"""
+    m = _meshes[int(id)]
+    P = m._v[m._f[:, 0]], m._v[m._f[:, 1]], m._v[m._f[:, 2]]
+    pt = np.asarray([float(x) for x in point.v], np.float32)
+    u, v = _closest_barycentrics(*P, pt[None])
+    w = (np.float32(1.0) - u - v).astype(np.float32)
+    c = (u[:, None] * P[0]).astype(np.float32) + (v[:, None] * P[1]).astype(np.float32)
+    c = (c + (w[:, None] * P[2]).astype(np.float32)).astype(np.float32)
+    dd = (c - pt[None]).astype(np.float32)
+    d2 = ((dd[:, 0] * dd[:, 0]).astype(np.float32) + (dd[:, 1] * dd[:, 1]).astype(np.float32)).astype(np.float32)
+    d2 = (d2 + (dd[:, 2] * dd[:, 2]).astype(np.float32)).astype(np.float32)
+    best = _F(_F(max_dist) * _F(max_dist))
+    d2 = np.where(np.isnan(d2), np.float32(np.inf), d2)
+    k = int(np.argmin(d2))  # the first triangle of the minimum: strict < in index order
+    if not d2[k] < best:
+        return MeshQueryPoint()
+    sgn = _F(-1.0) if _mesh_query_inside(m, pt) else _F(1.0)
+    return MeshQueryPoint(True, sgn, k, _F(_F(_F(1.0) - v[k]) - w[k]), v[k])
+
+
+def mesh_eval_position(id, face, bary_u, bary_v):  # noqa: A002
+    """warp/native/mesh.h mesh_eval_position: p u + q v + r (1 - u - v) of triangle ``face``"""
+    m = _meshes[int(id)]
+    i, j, k = (int(x) for x in m._f[int(face)])
+    p, q, r = vec3(m._v[i]), vec3(m._v[j]), vec3(m._v[k])
+    u, v = _F(bary_u), _F(bary_v)
+    return p * u + q * v + r * _F(_F(_F(1.0) - u) - v)
+
+
+def to_torch(a, **kw):
+    import torch
+
+    return torch.as_tensor(np.asarray(a.a if isinstance(a, array) else a))
 
 
 # ----------------------------------------------------------------------------- functions, kernels, structs
