@@ -34,6 +34,7 @@ SOURCES = [
     "trajectory.hip",
     "optimization.hip",
     "cost.hip", "rollout_fused.hip", "dynamics.hip", "linalg.hip", "mppi.hip", "seed_ik.hip", "mesh_bake.hip", "mesh_bvh.hip",
+    "graph_planner.hip",
 ]
 
 

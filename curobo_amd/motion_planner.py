@@ -9,9 +9,10 @@ over the HIP solvers.
   IK with ``return_seeds = num_trajopt_seeds`` -> failed solutions replaced by the first good one -> trajectory
   optimisation seeded with straight lines to those solutions, implicit goal state, one time-optimal finetune
   pass (dt scale 0.55) -> stop at the first attempt with a successful seed.  ``plan_cspace`` (:329-396): joint-space
-  goal, three finetune passes at 0.75.  The PRM graph planner that seeds later attempts in the reference
-  (``_get_graph_seed_trajectories``) is out of scope (graph search), so every attempt is the
-  IK-seeded one.  ``plan_grasp`` (:419-588): goal-set plan to the grasp candidates -> approach pose -> straight-line motion
+  goal, three finetune passes at 0.75.  With ``MotionPlannerCfg.create(use_graph_planner=True)`` the PRM graph
+  planner (``curobo_amd.graph_planner``) seeds the attempts from ``enable_graph_attempt`` on with roadmap paths to the IK
+  solutions / the goal configuration (reference ``_get_graph_seed_trajectories``, :396-417), three finetune passes at
+  0.75; an attempt whose graph query fails is skipped.  Off by default: every attempt is then the IK-seeded one.  ``plan_grasp`` (:419-588): goal-set plan to the grasp candidates -> approach pose -> straight-line motion
   to the chosen grasp -> straight-line lift, with the grasp-contact links' collision spheres switched off where the
   reference switches them off.  The attachment manager is not mirrored.
 * ``BatchMotionPlanner.plan_pose`` / ``plan_cspace`` = ``motion_planner_batch.py:139-289``: ``max_batch_size``
@@ -454,22 +455,25 @@ class TrajectoryOptimizer(ToolPoseTrackingMixin):
 @dataclass
 class MotionPlannerCfg:
     """reference MotionPlannerCfg (motion/motion_planner_cfg.py:28-261): the IK and trajectory-optimisation
-    configurations of one robot in one (set of) world(s); no graph planner here"""
+    configurations of one robot in one (set of) world(s), and the graph planner's when it is switched on"""
 
     trajopt_solver_config: TrajectoryOptimizerCfg = None
     num_ik_seeds: int = 32
     device_cfg: DeviceCfg = field(default_factory=DeviceCfg)
+    #: PRM graph planner settings (``curobo_amd.graph_planner.PRMGraphPlannerCfg``); None = no graph planner
+    graph_planner_config: Optional[object] = None
 
     @staticmethod
     def create(robot: Union[str, Dict, KinematicsCfg], scene_model: Union[str, Dict, List, None] = None,
                self_collision_check: bool = True, device_cfg: Optional[DeviceCfg] = None, num_ik_seeds: int = 32,
                num_trajopt_seeds: int = 4, position_tolerance: float = 0.005, orientation_tolerance: float = 0.05,
                use_cuda_graph: bool = True, random_seed: int = 123, optimizer_collision_activation_distance: float = 0.01,
-               max_batch_size: int = 1, multi_env: bool = False, max_goalset: int = 1, assets_root: str = "", **unused
-               ) -> "MotionPlannerCfg":
-        """Arguments of the reference's ``MotionPlannerCfg.create`` (:37-66); task / graph-planner yaml arguments are
-        accepted and ignored.  ``multi_env``: ``scene_model`` is a list of ``max_batch_size`` worlds, problem p of a batch
-        plans in world p."""
+               max_batch_size: int = 1, multi_env: bool = False, max_goalset: int = 1, assets_root: str = "",
+               use_graph_planner: bool = False, graph_planner_config=None, **unused) -> "MotionPlannerCfg":
+        """Arguments of the reference's ``MotionPlannerCfg.create`` (:37-66); task yaml arguments are accepted and
+        ignored.  ``multi_env``: ``scene_model`` is a list of ``max_batch_size`` worlds, problem p of a batch plans in world p.
+        ``use_graph_planner``: build the PRM graph planner (``graph_planner_config``: a ``PRMGraphPlannerCfg``, default
+        the reference's ``exact_graph_planner.yml``); single environment only -- ``multi_env`` planners get none."""
         device_cfg = device_cfg or DeviceCfg()
         to = TrajectoryOptimizerCfg.create(
             robot, scene_model, num_seeds=num_trajopt_seeds, position_tolerance=position_tolerance,
@@ -481,7 +485,12 @@ class MotionPlannerCfg:
                                                                                   "collision_cache")})
         if multi_env and (to.scene is None or to.scene.num_envs < max_batch_size):
             raise ValueError(f"multi_env needs a list of {max_batch_size} scene models (one world per problem)")
-        return MotionPlannerCfg(trajopt_solver_config=to, num_ik_seeds=num_ik_seeds, device_cfg=device_cfg)
+        gp = None
+        if use_graph_planner and not multi_env:
+            from .graph_planner import PRMGraphPlannerCfg
+
+            gp = graph_planner_config if graph_planner_config is not None else PRMGraphPlannerCfg()
+        return MotionPlannerCfg(trajopt_solver_config=to, num_ik_seeds=num_ik_seeds, device_cfg=device_cfg, graph_planner_config=gp)
 
 
 class _PlannerBase(ToolPoseTrackingMixin):
@@ -490,6 +499,7 @@ class _PlannerBase(ToolPoseTrackingMixin):
         self.device_cfg = config.device_cfg
         self.trajopt_solver = TrajectoryOptimizer(config.trajopt_solver_config)
         self._ik: Optional[IKSolver] = None
+        self.graph_planner = None
 
     @property
     def batch_size(self) -> int:
@@ -533,11 +543,21 @@ class _PlannerBase(ToolPoseTrackingMixin):
         """reference ``update_world(scene_cfg)`` (:605-608): a ``SceneData`` or a scene description"""
         self.trajopt_solver.update_world(scene)
         self._ik = None
+        self._reset_graph()
 
     def reset_seed(self) -> None:
         self.trajopt_solver.reset_seed()
         if self._ik is not None:
             self._ik.reset_seed()
+        if self.graph_planner is not None:
+            self.graph_planner.reset_seed()
+            self.graph_planner.reset_buffer()
+
+    def _reset_graph(self) -> None:
+        """empty roadmap, checked against the current world (reference :604-620)"""
+        if self.graph_planner is not None:
+            self.graph_planner.checker.update_world(self.config.trajopt_solver_config.scene)
+            self.graph_planner.reset_buffer()
 
     def clear_scene_cache(self) -> None:
         """reference ``clear_scene_cache`` (:606-609): the obstacle buffers are emptied; here the solvers are rebuilt
@@ -546,12 +566,17 @@ class _PlannerBase(ToolPoseTrackingMixin):
 
     # ---- robot model edits (reference :590-640); all in place on tensors the captured graphs read
     def enable_link_collision(self, enable_collision_links: List[str]) -> None:
+        """(also empties the graph planner's roadmap: its edges were checked with the other sphere set; the reference keeps
+        it)"""
         for name in enable_collision_links:
             self.kinematics.config.kinematics_config.enable_link_spheres(name)
+        self._reset_graph()
 
     def disable_link_collision(self, disable_collision_links: List[str]) -> None:
+        """(empties the graph planner's roadmap, as ``enable_link_collision``)"""
         for name in disable_collision_links:
             self.kinematics.config.kinematics_config.disable_link_spheres(name)
+        self._reset_graph()
 
     def update_link_inertial(self, link_name: str, mass: Optional[float] = None, com=None, inertia=None) -> None:
         self.kinematics.config.kinematics_config.update_link_inertial(link_name, mass, com, inertia)
@@ -618,6 +643,27 @@ class MotionPlanner(_PlannerBase):
         if config.trajopt_solver_config.max_batch_size != 1:
             raise ValueError("MotionPlanner plans one problem at a time (max_batch_size must be 1); use BatchMotionPlanner")
         super().__init__(config)
+        if config.graph_planner_config is not None:
+            from .collision_checking import RobotCollisionChecker
+            from .graph_planner import PRMGraphPlanner
+
+            to = config.trajopt_solver_config
+            checker = RobotCollisionChecker(to.kinematics, to.scene, 0.0)
+            self.graph_planner = PRMGraphPlanner(config.graph_planner_config, checker,
+                                                 self.default_joint_state.position.view(-1), self.joint_names)
+
+    def _get_graph_seed_trajectories(self, current_state: JointState, seed_config: torch.Tensor) -> Optional[torch.Tensor]:
+        """reference :396-417: roadmap paths from the current state to each goal configuration [1, n, dof], linearly
+        interpolated to the trajectory's knots -> [1, n_success, n_knots, dof], None when no query succeeded"""
+        D = self.action_dim
+        goals = seed_config.reshape(-1, D).to(self.device_cfg.device, torch.float32)
+        starts = current_state.position.reshape(1, D).to(goals.device, torch.float32).expand(goals.shape[0], D)
+        r = self.graph_planner.find_path(starts.clone(), goals.clone(), interpolate_waypoints=True,
+                                         interpolation_steps=self.trajopt_solver.action_horizon,
+                                         validate_interpolated_trajectory=False)
+        if int(r.success.sum()) == 0:
+            return None
+        return r.interpolated_waypoints[r.success].unsqueeze(0)
 
     def warmup(self, enable_graph: bool = True, warmup_joint_index: int = 0, warmup_joint_delta: float = 0.2,
                num_warmup_iterations: int = 2) -> bool:
@@ -627,6 +673,11 @@ class MotionPlanner(_PlannerBase):
             goal = cur.clone()
             goal.position[..., warmup_joint_index] += warmup_joint_delta
             self.plan_pose(self.compute_kinematics(goal).tool_poses.as_goal(), cur, max_attempts=1)
+            if enable_graph and self.graph_planner is not None:
+                self.graph_planner.find_path(cur.position.view(1, -1).to(self.device_cfg.device),
+                                             goal.position.view(1, -1).to(self.device_cfg.device))
+        if self.graph_planner is not None:
+            self.graph_planner.reset_buffer()
         return True
 
     def plan_pose(self, goal_tool_poses: GoalToolPose, current_state: JointState, use_implicit_goal: bool = True,
@@ -637,15 +688,23 @@ class MotionPlanner(_PlannerBase):
         t0 = time.perf_counter()
         result = None
         solve_time = 0.0
-        for _ in range(max_attempts):
+        use_graph = self.graph_planner is not None and goal_tool_poses.num_goalset == 1
+        for attempt in range(max_attempts):
             ok, seed_config = self._ik_seed_configs(goal_tool_poses, 1, current_state)
             if int(ok.sum()) == 0:
                 continue
             if int(ok.sum()) < ok.shape[1]:  # failed solutions are replaced by the first good one (:265-267)
                 good = seed_config[ok][0:1]
                 seed_config = torch.where(ok.unsqueeze(-1), seed_config, good.view(1, 1, -1))
-            result = self.trajopt_solver.solve_pose(goal_tool_poses, current_state, seed_config=seed_config,
-                                                    use_implicit_goal=True, finetune_attempts=1, finetune_dt_scale=0.55)
+            if use_graph and attempt >= enable_graph_attempt:  # roadmap seeds (:268-279)
+                seed_traj = self._get_graph_seed_trajectories(current_state, seed_config)
+                if seed_traj is None:
+                    continue
+                result = self.trajopt_solver.solve_pose(goal_tool_poses, current_state, seed_config=seed_config, seed_traj=seed_traj,
+                                                        use_implicit_goal=True, finetune_attempts=3, finetune_dt_scale=0.75)
+            else:
+                result = self.trajopt_solver.solve_pose(goal_tool_poses, current_state, seed_config=seed_config,
+                                                        use_implicit_goal=True, finetune_attempts=1, finetune_dt_scale=0.55)
             solve_time += result.solve_time
             if int(result.success.sum()) > 0:
                 break
@@ -765,8 +824,16 @@ class MotionPlanner(_PlannerBase):
             raise ValueError("current_state and goal_state must be 2D tensors")
         t0 = time.perf_counter()
         result, solve_time = None, 0.0
-        for _ in range(max_attempts):
-            result = self.trajopt_solver.solve_cspace(goal_state, current_state, finetune_attempts=3, finetune_dt_scale=0.75)
+        for attempt in range(max_attempts):
+            if self.graph_planner is not None and attempt >= enable_graph_attempt:  # roadmap seeds (:359-368)
+                goals = goal_state.position.reshape(1, 1, -1).expand(1, self.config.trajopt_solver_config.num_seeds, -1)
+                seed_traj = self._get_graph_seed_trajectories(current_state, goals)
+                if seed_traj is None:
+                    continue
+                result = self.trajopt_solver.solve_cspace(goal_state, current_state, seed_traj=seed_traj, finetune_attempts=3,
+                                                          finetune_dt_scale=0.75)
+            else:
+                result = self.trajopt_solver.solve_cspace(goal_state, current_state, finetune_attempts=3, finetune_dt_scale=0.75)
             solve_time += result.solve_time
             if int(result.success.sum()) > 0:
                 break

@@ -874,6 +874,35 @@ int curobo_hip_trajectory_cost_sum(float *out_cost, const float *self_cost,
                                    const float *scene_cost, int batch_size, int horizon,
                                    int num_spheres, curobo_hip_stream_t stream);
 
+/* ---- PRM graph planner (curobo_amd/graph_planner) ---------------------------------------------
+ * Edge steering (reference LinearConnector.steer_until_infeasible): rows start[n, ld] -> target[n, ld]
+ * (first dof columns) are walked at the batch-wide step count max_steps = max over edges of
+ * ceil(max_k |w_k (t_k - s_k)| / cspace_similarity_threshold) + 1, reduced on the device into
+ * max_steps_ws[1] ahead of the walk (no host sync).  Point k of an edge is s + (k / max_steps)(t - s);
+ * a point is feasible when its scene cost, self-collision cost and joint-bound cost are all exactly 0
+ * with activation distance 0.  Outputs: out_node[n, dof + 1] = the point before the first infeasible
+ * one (clamped to index 0; the end point when none is infeasible), index column 0; out_index[n] =
+ * its step index.  point_mode != 0: start rows only (target, weight, threshold, out_node, out_index
+ * and max_steps_ws unused), out_feasible[n] = 1 where the configuration is feasible.  Scenes of
+ * cuboids, primitives and voxel grids (meshes are not covered). */
+int curobo_hip_graph_steer(float *out_node, int32_t *out_index, uint8_t *out_feasible, int32_t *max_steps_ws,
+                           const float *start, const float *target, int ld, const float *cspace_distance_weight,
+                           float cspace_similarity_threshold, int n, int point_mode, const float *p_b,
+                           const float *fixed_transform, const float *robot_spheres, const int8_t *joint_map_type,
+                           const int16_t *joint_map, const int16_t *link_map, const int16_t *link_sphere_map,
+                           const int16_t *link_chain_data, const int16_t *link_chain_offsets,
+                           const float *joint_offset_map, const float *sphere_padding,
+                           const int16_t *pair_locations, const curobo_hip_scene *scene, int dof, int num_links,
+                           int num_spheres, int num_collision_pairs, int link_chain_len, curobo_hip_stream_t stream);
+
+/* Weighted k nearest neighbours (reference DistanceNeighborCalculator.jit_find_nearest_neighbors):
+ * for each query row of queries[n_queries, ld_q], the indices of the k closest of the first n_nodes
+ * rows of nodes[*, ld_n] under the distance || w * (x - q) || over the first dof columns, nearest
+ * first, ties to the lower node index -> out_idx[n_queries, k].  1 <= k <= min(64, n_nodes). */
+int curobo_hip_graph_knn(int32_t *out_idx, const float *queries, int ld_q, const float *nodes, int ld_n,
+                         const float *cspace_distance_weight, int n_queries, int n_nodes, int dof, int k,
+                         curobo_hip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
