@@ -2,7 +2,7 @@
 
 The library ships a handful of pre-built shapes (``csrc/fused_shapes.hpp``: Franka and UR10e at the BASELINE horizons); any
 other robot, horizon or knot count runs the generic kernel, which is ~20 % slower (every dimension a run-time value).  This
-module builds the missing shape on demand -- ``hipcc`` on ``csrc/rollout_fused.hip`` with the shape and its kernel list on the
+module builds the missing shape on demand -- ``hipcc`` on ``csrc/rollout_fused_shape.hip`` with the shape and its kernel list on the
 command line (5-10 s, cached on disk by a hash of the sources, the shape, the flags and the compiler), the object loaded and its
 launcher handed to ``curobo_hip_rollout_fused_register_shape`` -- which is what the reference does for every kernel and every
 robot with NVRTC (``curobo/_src/curobolib/backends/cuda_core_backend/kernel_cache.py:89-119,161-235``: SHA-256 of sources + name
@@ -49,7 +49,7 @@ def _flags():
 
 def _sources_digest() -> str:
     h = hashlib.sha256()
-    names = ["rollout_fused.hip"] + sorted(n for n in os.listdir(_CSRC) if n.endswith(".hpp"))
+    names = ["rollout_fused_shape.hip"] + sorted(n for n in os.listdir(_CSRC) if n.endswith(".hpp"))
     for n in names:
         with open(os.path.join(_CSRC, n), "rb") as fh:
             h.update(n.encode())
@@ -84,7 +84,7 @@ def compile_shape(spec: str, kernels: Iterable[Tuple[int, int, int, bool]] = DEF
         return out
     tmp = f"{out}.{os.getpid()}.tmp"
     cmd = [cc, *flags, "-shared", "-DCUROBO_FUSED_SHAPE_TU=99", f"-DCUROBO_FUSED_JIT_SHAPE={spec}", f"-DCUROBO_FUSED_JIT_KERNELS(K)={klist}",
-           "-x", "hip", os.path.join(_CSRC, "rollout_fused.hip"), "-o", tmp]
+           "-x", "hip", os.path.join(_CSRC, "rollout_fused_shape.hip"), "-o", tmp]
     if verbose:
         print(" ".join(cmd))
     p = subprocess.run(cmd, capture_output=True, text=True)

@@ -1,5 +1,5 @@
-"""HIP backend of the PRM graph planner (``csrc/rollout_fused.hip`` graph_steer_kernel,
-``csrc/graph_planner.hip`` graph_knn_kernel).  Same conventions as the other backends:
+"""HIP backend of the PRM graph planner (``csrc/graph_planner.hip``: graph_steer_kernel
+and graph_knn_kernel).  Same conventions as the other backends:
 pre-allocated tensors in, mutated in place, current stream."""
 
 from __future__ import annotations

@@ -24,7 +24,7 @@ OBJ_DIR = os.path.join(_PKG, "build")
 ARCH = "gfx950"
 
 HEADERS = ["common.hpp", "cost_device.hpp", "scene_device.hpp", "fk_device.hpp", "self_device.hpp",
-           "bspline_device.hpp", "dynamics_device.hpp", "mesh_device.hpp", "fused_shapes.hpp"]
+           "bspline_device.hpp", "dynamics_device.hpp", "mesh_device.hpp", "fused_shapes.hpp", "fused_device.hpp"]
 
 SOURCES = [
     "runtime.cpp",
@@ -33,7 +33,7 @@ SOURCES = [
     "scene_collision.hip",
     "trajectory.hip",
     "optimization.hip",
-    "cost.hip", "rollout_fused.hip", "dynamics.hip", "linalg.hip", "mppi.hip", "seed_ik.hip", "mesh_bake.hip", "mesh_bvh.hip",
+    "cost.hip", "rollout_fused.hip", "rollout_ik_fused.hip", "dynamics.hip", "linalg.hip", "mppi.hip", "seed_ik.hip", "mesh_bake.hip", "mesh_bvh.hip",
     "graph_planner.hip",
 ]
 
@@ -47,10 +47,10 @@ def fused_shape_ids() -> List[int]:
 
 
 def compile_units() -> List[tuple]:
-    """(source, object stem, extra flags): every source once, plus rollout_fused.hip once more per compile-time shape
-    (-DCUROBO_FUSED_SHAPE_TU=k holds only that shape's instantiations and its launcher: the shapes compile in parallel)."""
+    """(source, object stem, extra flags): every source once, plus rollout_fused_shape.hip once per compile-time shape
+    (-DCUROBO_FUSED_SHAPE_TU=k: that shape's instantiations and its launcher; the shapes compile in parallel)."""
     units = [(s, s.rsplit(".", 1)[0], []) for s in SOURCES]
-    units += [("rollout_fused.hip", f"rollout_fused_shape{k}", [f"-DCUROBO_FUSED_SHAPE_TU={k}"]) for k in fused_shape_ids()]
+    units += [("rollout_fused_shape.hip", f"rollout_fused_shape{k}", [f"-DCUROBO_FUSED_SHAPE_TU={k}"]) for k in fused_shape_ids()]
     return units
 
 

@@ -4,7 +4,7 @@
 //
 // Both are tiny elementwise maps (one lane per (batch, horizon, link) resp. (batch, horizon,
 // dof)); they exist as stand-alone entry points for the drop-in API and are also inlined into
-// the fused IK rollout kernel (rollout_fused.hip) where launch latency matters.
+// the fused IK rollout kernel (rollout_ik_fused.hip) where launch latency matters.
 #include "cost_device.hpp"
 
 namespace curobo_hip {

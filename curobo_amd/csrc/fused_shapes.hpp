@@ -1,4 +1,4 @@
-// fused_shapes.hpp -- compile-time shapes of the fused rollout launch (rollout_fused.hip).
+// fused_shapes.hpp -- compile-time shapes of the fused rollout launch (fused_device.hpp; one unit per shape: rollout_fused_shape.hip).
 //
 // The generic kernel reads every dimension (horizon, dof, links, spheres, pairs, workgroup size ...) from its arguments:
 // loop trip counts, the divisors of the flat-index decodes and the LDS carve are run-time values, so every phase carries

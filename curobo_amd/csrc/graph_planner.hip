@@ -1,4 +1,6 @@
-// Weighted k-nearest neighbours of the PRM graph planner (reference DistanceNeighborCalculator
+// graph_planner.hip -- kernels of the PRM graph planner: weighted k-nearest neighbours, then edge steering (further down).
+//
+// Weighted k-nearest neighbours (reference DistanceNeighborCalculator
 // .jit_find_nearest_neighbors, graph_planner/graph/node_distance.py:128-155: cdist over
 // weighted configurations, then a stable top-k, smallest first).
 //
@@ -10,7 +12,7 @@
 // index order and a node only displaces strictly larger keys, so equal distances keep the lower
 // node index first, as a stable top-k does.  fp64 keeps the order that of exact arithmetic for
 // fp32 inputs up to ties that are ties in fp32 too (duplicated nodes).
-#include "common.hpp"
+#include "fused_device.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -82,6 +84,209 @@ CUROBO_EXPORT int curobo_hip_graph_knn(int32_t *out_idx, const float *queries, i
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(graph_knn_kernel, dim3((unsigned)ceil_div(n_queries, 4)), dim3(256), 0, st, queries, ld_q, nodes, ld_n,
                      cspace_distance_weight, n_queries, n_nodes, dof, k, out_idx);
+  return check_launch(what, st);
+}
+
+// ------------------------------------------------------------------------------------------
+// Graph-planner edge steering (reference LinearConnector.steer_until_infeasible,
+// graph_planner/graph/connector_linear.py:75-192) without materialising the interpolated points:
+// a workgroup walks one edge's points k = 0 .. max_steps (coefficient k / max_steps, max_steps the
+// batch-wide count of graph_steer_max_steps_kernel) in chunks of 16 -- one 16-lane row per point,
+// the same FK / self / scene device functions and LDS tables as the IK launch (fused_device.hpp, rollout_ik_fused.hip) -- and stops
+// at the first chunk holding an infeasible point.  Feasible = scene cost, self-collision cost and
+// joint-bound cost all exactly 0 with activation distance 0 (RobotCollisionChecker.validate).
+// point_mode: 16 configurations per workgroup (start rows only), out_feasible[n] per configuration.
+struct FusedSteerArgs {
+  FusedTrajArgs r;             // robot / self / scene members (no outputs)
+  const float *start, *target;  // [n, ld] rows, the first dof columns used
+  const float *p_b;             // joint limits [2, dof]
+  const int32_t *max_steps;     // [1] batch-wide step count (edge mode)
+  float *out_node;              // [n, dof + 1] last feasible point, index column 0 (edge mode)
+  int32_t *out_index;           // [n] its step index (edge mode)
+  uint8_t *out_feasible;        // [n] (point mode)
+  int n, ld, point_mode;
+};
+
+// num_steps = ceil(max_k |w_k (t_k - s_k)| / threshold) + 1, reduced over the batch in one workgroup (no host sync)
+__global__ void __launch_bounds__(1024) graph_steer_max_steps_kernel(const float *start, const float *target, const float *w,
+                                                                      float threshold, int n, int ld, int dof, int32_t *out) {
+  __shared__ int red[16];
+  int m = 0;
+  for (int e = threadIdx.x; e < n; e += blockDim.x) {
+    float mx = 0.0f;
+    for (int d = 0; d < dof; d++) mx = fmaxf(mx, fabsf(__fmul_rn(target[(size_t)e * ld + d] - start[(size_t)e * ld + d], w[d])));
+    m = max(m, (int)ceilf(__fdiv_rn(mx, threshold)) + 1);
+  }
+  m = -wave64_min(-m);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < (int)(blockDim.x >> 6); i++) m = max(m, red[i]);
+    out[0] = max(m, red[0]);
+  }
+}
+
+// point of step k of edge e: start + (k / max_steps) * (target - start), each operation rounded on its own as in torch
+__device__ __forceinline__ float steer_point(const float *s, const float *t, int d, int k, int max_steps) {
+  const float cf = __fdiv_rn((float)k, (float)max_steps);
+  return __fadd_rn(s[d], __fmul_rn(cf, t[d] - s[d]));
+}
+
+template <int KINDS>
+__global__ void __launch_bounds__(256, 4) graph_steer_kernel(const FusedSteerArgs ga) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __shared__ int first_bad;
+  const FusedTrajArgs &a = ga.r;
+  const int H = kIkPoints, D = a.bs.dof, L = a.nlinks, S = a.nspheres, P = a.npairs;
+  const int n_rec = a.sc.max_cuboids + a.sc.max_voxel_grids;
+  const FusedLayout lay = fused_layout(H, D, L, S, a.chain_len, P, n_rec, 0, 0, 1, 0, false);
+  const int tid = threadIdx.x;
+  FusedCtx c;
+  fused_ctx_carve(c, smem, lay, H, D, L, S, P);
+  c.env = 0;
+  c.w_self = 1.0f; c.w_scene = 1.0f; c.eta = 0.0f;
+  c.speed_metric = false; c.speed_dt = 0.0f;
+  fused_stage_tables(c, a, lay, reinterpret_cast<const float4 *>(a.robot_spheres), n_rec);
+  __syncthreads();
+  fused_derive_tables(c);
+  const int h = tid / kFkLanes, lane = tid % kFkLanes;
+  const int max_steps = ga.point_mode ? 1 : ga.max_steps[0];
+  const int n_pts = max_steps + 1;  // points per edge
+  const int n_items = ga.point_mode ? (ga.n + H - 1) / H : ga.n;
+  for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
+    const int e = ga.point_mode ? -1 : item;
+    const float *s = ga.start + (size_t)(ga.point_mode ? 0 : e) * ga.ld, *t = ga.target + (size_t)(ga.point_mode ? 0 : e) * ga.ld;
+    int result = n_pts;  // first infeasible step (n_pts = none)
+    for (int k0 = 0; k0 < (ga.point_mode ? 1 : n_pts); k0 += H) {
+      const int k = k0 + h;
+      const int row = ga.point_mode ? item * H + h : e;
+      const bool live = ga.point_mode ? row < ga.n : k < n_pts;
+      __syncthreads();  // the previous chunk's readers of q / spheres / first_bad are done
+      if (tid == 0) first_bad = 0x7fffffff;
+      if (live && lane < D)
+        for (int d = lane; d < D; d += kFkLanes)
+          c.q[h * D + d] = ga.point_mode ? ga.start[(size_t)row * ga.ld + d] : steer_point(s, t, d, k, max_steps);
+      __syncthreads();
+      bool bad = false;
+      if (live) {
+        point_fk_locals(c, h, lane);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        float *const cm[1] = {c.cumul + (size_t)h * L * 12};
+        const float *const lc[1] = {c.work + (size_t)h * c.ws};
+        fk_chain_16_multi<1>(cm, lc, c.parent, c.fixed, L, lane);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        for (int sp = lane; sp < S; sp += kFkLanes) point_sphere(c, a, 0, h, sp);
+        if (lane == 0) reinterpret_cast<float4 *>(c.work + (size_t)h * c.ws)[S] = make_float4(0.f, 0.f, 0.f, __builtin_nanf(""));
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        // joint bounds (cspace_bound_term with unit weight and no activation margin, as RobotCollisionChecker.get_bound)
+        float viol = 0.0f;
+        for (int d = lane; d < D; d += kFkLanes) {
+          float g;
+          viol += cspace_bound_term(c.q[h * D + d], ga.p_b[d], ga.p_b[D + d], 1.0f, g);
+        }
+        // self collision: the largest pair penetration of the row (the IK launch's first pass)
+        float pen = 0.0f;
+        if (a.use_self) {
+          const float4 *sph = c.spheres(h);
+          const int P_pad = (P + 63) & ~63;
+          for (int k1 = lane; k1 < P_pad; k1 += kFkLanes) pen = fmaxf(pen, staged_pair_penetration(sph, c.pairs[k1]));
+        }
+        // scene cost of every sphere (activation distance 0)
+        float dsc = 0.0f;
+        if (a.use_scene) {
+          point_link_masks<0, KINDS>(c, a.sc, h, lane);
+          const float *wr = c.wrench + (size_t)h * c.wl;
+          for (int s0 = 0; s0 < S; s0 += kFkLanes) {
+            const int sp = s0 + lane;
+            float d = 0.0f;
+            f3 g = make_f3(0.f, 0.f, 0.f);
+            const uint32_t mask = sp < S ? __float_as_uint(wr[c.sph_link[sp] * kWrench + 6]) : 0u;
+            if (sp < S && (mask != 0u || n_rec > 32)) scene_sphere<0, KINDS>(c, a.sc, h, sp, d, g, mask);
+            dsc += d;
+          }
+        }
+        const float tot = row16_max(fmaxf(fmaxf(viol, pen), dsc));
+        bad = tot > 0.0f;
+      }
+      if (ga.point_mode) {
+        if (live && lane == 0) ga.out_feasible[row] = bad ? 0 : 1;
+        continue;
+      }
+      if (bad && lane == 0) atomicMin(&first_bad, k);
+      __syncthreads();
+      if (first_bad != 0x7fffffff) { result = first_bad; break; }
+    }
+    if (ga.point_mode) continue;
+    // the point before the first infeasible one (clamped to 0); the end point when there is none
+    const int idx = result < n_pts ? max(result - 1, 0) : n_pts - 1;
+    for (int d = tid; d <= D; d += blockDim.x)
+      ga.out_node[(size_t)e * (D + 1) + d] = d < D ? steer_point(s, t, d, idx, max_steps) : 0.0f;
+    if (tid == 0) ga.out_index[e] = idx;
+  }
+}
+
+CUROBO_EXPORT int curobo_hip_graph_steer(
+    float *out_node, int32_t *out_index, uint8_t *out_feasible, int32_t *max_steps_ws, const float *start, const float *target,
+    int ld, const float *cspace_distance_weight, float cspace_similarity_threshold, int n, int point_mode, const float *p_b,
+    const float *fixed_transform, const float *robot_spheres, const int8_t *joint_map_type, const int16_t *joint_map,
+    const int16_t *link_map, const int16_t *link_sphere_map, const int16_t *link_chain_data, const int16_t *link_chain_offsets,
+    const float *joint_offset_map, const float *sphere_padding, const int16_t *pair_locations, const curobo_hip_scene *scene,
+    int dof, int num_links, int num_spheres, int num_collision_pairs, int link_chain_len, curobo_hip_stream_t stream) {
+  const char *what = "graph_steer";
+  CUROBO_REQUIRE(num_links >= 1 && num_links <= 128 && dof >= 1 && dof <= 64 && ld >= dof, "%s: bad dimensions", what);
+  CUROBO_REQUIRE(link_chain_len >= 1, "%s: link_chain_len must be >= 1", what);
+  CUROBO_REQUIRE(num_spheres < 4096, "%s: at most 4095 spheres", what);
+  CUROBO_REQUIRE(((uintptr_t)pair_locations & 3) == 0, "%s: pair_locations must be 4-byte aligned", what);
+  CUROBO_REQUIRE(point_mode ? out_feasible != nullptr : (out_node && out_index && max_steps_ws && cspace_distance_weight
+                 && target && cspace_similarity_threshold > 0.0f), "%s: missing outputs / inputs for this mode", what);
+  if (n == 0) return CUROBO_HIP_OK;
+  FusedSteerArgs ga{};
+  FusedTrajArgs &a = ga.r;
+  a.bs.dof = dof;
+  a.fixed_transform = fixed_transform; a.robot_spheres = robot_spheres; a.joint_offset = joint_offset_map;
+  a.joint_map_type = joint_map_type; a.joint_map = joint_map; a.link_map = link_map; a.link_sphere_map = link_sphere_map;
+  a.link_chain_data = link_chain_data; a.link_chain_offsets = link_chain_offsets;
+  a.sphere_padding = sphere_padding; a.pairs = pair_locations;
+  a.use_self = (pair_locations && num_collision_pairs > 0) ? 1 : 0;
+  a.use_scene = scene ? 1 : 0;
+  if (scene) a.sc = *scene;
+  if (!a.use_scene) { a.sc.max_cuboids = 0; a.sc.max_voxel_grids = 0; }
+  a.batch = n; a.nlinks = num_links; a.nspheres = num_spheres; a.npairs = a.use_self ? num_collision_pairs : 0;
+  a.chain_len = link_chain_len; a.num_envs = 1; a.use_multi_env = 0;
+  ga.start = start; ga.target = point_mode ? start : target; ga.p_b = p_b; ga.max_steps = max_steps_ws;
+  ga.out_node = out_node; ga.out_index = out_index; ga.out_feasible = out_feasible;
+  ga.n = n; ga.ld = ld; ga.point_mode = point_mode ? 1 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  const int n_rec = a.sc.max_cuboids + a.sc.max_voxel_grids;
+  const FusedLayout lay = fused_layout(kIkPoints, dof, num_links, num_spheres, link_chain_len, a.npairs, n_rec, 0, 0, 1, 0, false);
+  const size_t lds = (size_t)lay.total * sizeof(float);
+  CUROBO_REQUIRE(lds <= 160 * 1024 - 64, "%s: 16 configurations do not fit in LDS (%zu bytes)", what, lds);
+  if (!point_mode) {
+    hipLaunchKernelGGL(graph_steer_max_steps_kernel, dim3(1), dim3(1024), 0, st, start, target, cspace_distance_weight,
+                       cspace_similarity_threshold, n, ld, dof, max_steps_ws);
+    const int err = check_launch("graph_steer_max_steps", st);
+    if (err != CUROBO_HIP_OK) return err;
+  }
+  const int kinds = (a.sc.max_cuboids > 0 && a.sc.cuboid_has_primitives) ? 7 : ((a.sc.max_cuboids > 0 ? 1 : 0) | (a.sc.max_voxel_grids > 0 ? 2 : 0));
+  const int items = point_mode ? ceil_div(n, kIkPoints) : n;
+  const dim3 grid((unsigned)(items < 2048 ? items : 2048)), block(kIkPoints * kFkLanes);
+#define CUROBO_STEER_LAUNCH(KD)                                                                                 \
+  do {                                                                                                          \
+    auto kfn = graph_steer_kernel<KD>;                                                                          \
+    if (lds > 60 * 1024) {                                                                                      \
+      hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+      if (e != hipSuccess) return set_error(CUROBO_HIP_ERR_LAUNCH, "%s: cannot raise LDS limit: %s", what, hipGetErrorString(e)); \
+    }                                                                                                           \
+    hipLaunchKernelGGL(kfn, grid, block, lds, st, ga);                                                          \
+  } while (0)
+  if (kinds == 2) CUROBO_STEER_LAUNCH(2);
+  else if (kinds == 3) CUROBO_STEER_LAUNCH(3);
+  else if (kinds == 7) CUROBO_STEER_LAUNCH(7);
+  else CUROBO_STEER_LAUNCH(1);
+#undef CUROBO_STEER_LAUNCH
   return check_launch(what, st);
 }
 

@@ -1,6 +1,6 @@
 // mesh_device.hpp -- device functions of the triangle-mesh obstacle kind: the closest-point / sign query through the
 // linear BVH of mesh_bvh.hip and the cost of one sphere against one mesh (centre + sweep), shared by the mesh launch
-// (mesh_bvh.hip) and the fused rollout kernels (rollout_fused.hip).
+// (mesh_bvh.hip) and the fused rollout kernels (fused_device.hpp).
 //
 // Reference: curobo/_src/geom/data/data_mesh.py:555-700 (wp.mesh_query_point per query sphere: closest surface point,
 // signed distance, unit vector to the point) and geom/collision/wp_sweep_collision_kernel.py:176-254 (the sweep).  What

@@ -1,0 +1,238 @@
+// rollout_ik_fused.hip -- horizon-1 ("teleport") rollout of the IK solver in one launch: q -> FK -> tool-pose goal-set
+// cost + c-space bound cost + self + scene collision -> cost[b] and d cost / d q[b].  Replaces
+// the seven launches of curobo_amd/rollout/ik_rollout.py (reference RobotRollout with
+// StateFromPositionTeleport and the cost set of content/configs/task/ik/lbfgs_ik.yml); same
+// device functions, intermediates in LDS.  16 configurations per 256-thread workgroup (one
+// 16-lane row each) share the staged robot / scene tables.  The tool-pose gradient enters the
+// link-wrench VJP as a force at the tool link's origin plus the free torque omega = 1/2 E(q)^T g
+// (reference kinematics_backward_helper.cuh:102-183, quaternion_util.cuh:86-102).
+#include "fused_device.hpp"
+
+namespace curobo_hip {
+
+struct FusedIkArgs {
+  FusedTrajArgs r;  // robot / self / scene members, out_cost, out_position (= nothing), out_spheres
+  const float *x;   // [n_points, dof]
+  float *out_grad_q;
+  ToolPoseArgs tp;  // current_position / current_quat unused (computed here); out_* optional
+  const float *p_b, *cs_weight, *cs_eta;  // c-space bound term: limits [2, dof], weight[>=1], activation[>=1]
+  float *out_cspace_cost;                 // optional [n_points, dof]
+  const int16_t *tool_frame_map;
+  float *out_link_pos, *out_link_quat;  // optional [n_points, T, 3|4]
+  int n_tool_frames, n_points;
+};
+
+template <int KINDS>
+__global__ void __launch_bounds__(256, 4) rollout_ik_fused_kernel(const FusedIkArgs ia) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const FusedTrajArgs &a = ia.r;
+  const int H = kIkPoints, D = a.bs.dof, L = a.nlinks, S = a.nspheres, P = a.npairs, T = ia.n_tool_frames;
+  const int n_rec = a.sc.max_cuboids + a.sc.max_voxel_grids;
+  const FusedLayout lay = fused_layout(H, D, L, S, a.chain_len, P, n_rec, 0, 0, 1, 0, false);
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int pt0 = blockIdx.x * kIkPoints;
+  const int npts = min(kIkPoints, ia.n_points - pt0);
+  FusedCtx c;
+  fused_ctx_carve(c, smem, lay, H, D, L, S, P);
+  // the 16 configurations of a workgroup share ONE environment (scene and sphere set): that of its first configuration.
+  // The caller checks that env_query_idx is constant over aligned runs of 16 (seeds of one problem: IkRollout).
+  const int wg_env = (a.use_multi_env || a.num_envs > 1) ? a.env_query_idx[pt0] : 0;
+  c.env = a.use_multi_env ? wg_env : 0;
+  c.w_self = a.use_self ? a.w_self[0] : 0.0f;
+  c.w_scene = a.use_scene ? a.w_scene[0] : 0.0f;
+  c.eta = a.use_scene ? a.eta[0] : 0.0f;
+  c.speed_metric = false;
+  c.speed_dt = 0.0f;
+  fused_stage_tables(c, a, lay, reinterpret_cast<const float4 *>(a.robot_spheres) + (size_t)(a.num_envs > 1 ? wg_env : 0) * S, n_rec);
+  for (int e = rotated_tid((nt >> 6) / 2); e < npts * D; e += nt) c.q[e] = ia.x[(size_t)pt0 * D + e];
+  __syncthreads();
+  fused_derive_tables(c);
+
+  const int h = tid / kFkLanes, lane = tid % kFkLanes, lane64 = tid & 63;
+  const bool live = h < npts;
+  const int n = pt0 + h;
+  // ---- FK
+  if (live) {
+    point_fk_locals(c, h, lane);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    float *const cm[1] = {c.cumul + (size_t)h * L * 12};
+    const float *const lc[1] = {c.work + (size_t)h * c.ws};
+    fk_chain_16_multi<1>(cm, lc, c.parent, c.fixed, L, lane);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int s = lane; s < S; s += kFkLanes) point_sphere(c, a, blockIdx.x, h, s);
+    if (lane == 0) reinterpret_cast<float4 *>(c.work + (size_t)h * c.ws)[S] = make_float4(0.f, 0.f, 0.f, __builtin_nanf(""));
+  }
+  __syncthreads();  // derived tables (other waves) + this row's spheres
+  if (!live) return;
+
+  // ---- costs + wrenches
+  const float4 *sph = c.spheres(h);
+  float *wr = c.wrench + (size_t)h * c.wl;
+  float cost_pt = 0.0f;
+  bool any_grad = false;
+  if (a.use_self) {  // reference self_collision_kernel.cuh:19-111 (same loop as the trajectory kernel)
+    constexpr int U = 4;
+    const int P_pad = (P + 63) & ~63;
+    float best = 0.0f;
+    int best_k0 = 0x7fffffff;
+    for (int k0 = lane; k0 < P_pad; k0 += kFkLanes * U) {
+      uint32_t ij[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) ij[u] = c.pairs[k0 + u * kFkLanes];
+      float gmax = staged_pair_penetration(sph, ij[0]);
+#pragma unroll
+      for (int u = 1; u < U; u++) gmax = fmaxf(gmax, staged_pair_penetration(sph, ij[u]));
+      if (gmax > best) { best = gmax; best_k0 = k0; }
+    }
+    float m = row16_max(best);
+    if (m > 0.0f) {
+      int best_k = 0x7fffffff;
+      if (best == m) {
+        float f_best = 0.0f;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          const float f = staged_pair_penetration(sph, c.pairs[best_k0 + u * kFkLanes]);
+          if (f > f_best) { f_best = f; best_k = best_k0 + u * kFkLanes; }
+        }
+        best = f_best;
+      } else {
+        best = 0.0f;
+      }
+      m = row16_max(best);
+      const int kmin = row16_min((best == m && best > 0.0f) ? best_k : 0x7fffffff);
+      if (kmin != 0x7fffffff && m > 0.0f) {
+        any_grad = true;
+        if (lane == 0) cost_pt += self_pair_apply(c, h, m, kmin);
+      }
+    }
+  }
+  if (a.use_scene) {
+    point_link_masks<0, KINDS>(c, a.sc, h, lane);
+    for (int s0 = 0; s0 < S; s0 += kFkLanes) {
+      const int s = s0 + lane;
+      float d = 0.0f;
+      f3 g = make_f3(0.f, 0.f, 0.f);
+      float4 c4 = make_float4(0.f, 0.f, 0.f, -1.f);
+      const uint32_t mask = s < S ? __float_as_uint(wr[c.sph_link[s] * kWrench + 6]) : 0u;
+      if (s < S && (mask != 0u || n_rec > 32)) c4 = scene_sphere<0, KINDS>(c, a.sc, h, s, d, g, mask);
+      cost_pt += d;
+      any_grad = wrench_add_serialised(c, h, s, make_f3(c4.x, c4.y, c4.z), g, lane64) || any_grad;
+    }
+  }
+  // tool-pose goal-set cost (wp_tool_pose.py:456-692), one tool frame per lane
+  point_tool_pose(c, ia.tp, ia.tool_frame_map, T, n, 0, h, (size_t)n * T, ia.out_link_pos, ia.out_link_quat, lane, lane64,
+                  cost_pt, any_grad);
+  // c-space bound cost (wp_cspace_position.py:232-362): its gradient is already in joint space
+  float gp_joint[kDofIters];
+#pragma unroll
+  for (int it = 0; it < kDofIters; it++) {
+    const int d = it * kFkLanes + lane;
+    float g = 0.0f;
+    if (d < D) {
+      float pl = ia.p_b[d], pu = ia.p_b[D + d];
+      { const float r = pu - pl, eta_p = ia.cs_eta[0]; pl = pl + eta_p * r; pu = pu - eta_p * r; }
+      const float cc = cspace_bound_term(c.q[h * D + d], pl, pu, ia.cs_weight[0], g);
+      cost_pt += cc;
+      if (ia.out_cspace_cost) ia.out_cspace_cost[(size_t)n * D + d] = cc;
+    }
+    gp_joint[it] = g;
+  }
+  cost_pt = row16_sum(cost_pt);
+  if (lane == 0) a.out_cost[n] = cost_pt;
+  point_vjp_gather(c, h, any_grad, lane);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int it = 0; it < kDofIters; it++) {
+    const int d = it * kFkLanes + lane;
+    if (d < D) ia.out_grad_q[(size_t)n * D + d] = c.q[h * D + d] + gp_joint[it];
+  }
+}
+
+}  // namespace curobo_hip
+
+using namespace curobo_hip;
+
+CUROBO_EXPORT int curobo_hip_rollout_ik_fused_lds_bytes(int dof, int num_links, int num_spheres, int num_collision_pairs,
+                                                        int link_chain_len, int num_obstacles) {
+  const FusedLayout lay = fused_layout(kIkPoints, dof, num_links, num_spheres, link_chain_len, num_collision_pairs, num_obstacles, 0, 0, 1, 0, false);
+  return lay.total * (int)sizeof(float);
+}
+
+CUROBO_EXPORT int curobo_hip_rollout_ik_fused(
+    float *out_cost, float *out_grad_q, float *out_pose_distance, float *out_position_distance,
+    float *out_rotation_distance, int32_t *out_goalset_idx, float *out_link_pos, float *out_link_quat,
+    float *out_robot_spheres, float *out_cspace_cost, const float *q, const float *goal_position, const float *goal_quat,
+    const int32_t *idxs_goal, const float *position_orientation_weight, const float *terminal_pose_axes_weight_factor,
+    const float *terminal_pose_convergence_tolerance, const uint8_t *project_distance_to_goal, int num_goalset,
+    int rotation_method, const float *p_b, const float *cspace_weight, const float *cspace_activation_distance,
+    const float *fixed_transform, const float *robot_spheres, const int8_t *joint_map_type, const int16_t *joint_map,
+    const int16_t *link_map, const int16_t *tool_frame_map, const int16_t *link_sphere_map,
+    const int16_t *link_chain_data, const int16_t *link_chain_offsets, const float *joint_offset_map,
+    const float *sphere_padding, const float *self_collision_weight, const int16_t *pair_locations,
+    const curobo_hip_scene *scene, const float *scene_collision_weight, const float *activation_distance,
+    int batch_size, int dof, int num_links, int n_tool_frames, int num_spheres, int num_collision_pairs,
+    int link_chain_len, const int32_t *env_query_idx, int num_envs, int use_multi_env, curobo_hip_stream_t stream) {
+  const char *what = "rollout_ik_fused";
+  CUROBO_REQUIRE((!use_multi_env && num_envs <= 1) || env_query_idx, "%s: per-environment scenes / sphere sets need env_query_idx", what);
+  CUROBO_REQUIRE(num_links >= 1 && num_links <= 128 && dof >= 1 && dof <= 64, "%s: bad dimensions", what);
+  CUROBO_REQUIRE(n_tool_frames >= 1 && num_goalset >= 1, "%s: need at least one tool frame / goal", what);
+  CUROBO_REQUIRE(link_chain_len >= 1, "%s: link_chain_len must be >= 1", what);
+  CUROBO_REQUIRE(num_spheres < 4096, "%s: at most 4095 spheres", what);
+  CUROBO_REQUIRE(((uintptr_t)pair_locations & 3) == 0, "%s: pair_locations must be 4-byte aligned", what);
+  if (batch_size == 0) return CUROBO_HIP_OK;
+  FusedIkArgs ia{};
+  FusedTrajArgs &a = ia.r;
+  a.out_cost = out_cost; a.out_spheres = out_robot_spheres;
+  a.bs.dof = dof;
+  a.fixed_transform = fixed_transform; a.robot_spheres = robot_spheres; a.joint_offset = joint_offset_map;
+  a.joint_map_type = joint_map_type; a.joint_map = joint_map; a.link_map = link_map; a.link_sphere_map = link_sphere_map;
+  a.link_chain_data = link_chain_data; a.link_chain_offsets = link_chain_offsets;
+  a.sphere_padding = sphere_padding; a.w_self = self_collision_weight; a.pairs = pair_locations;
+  a.use_self = (pair_locations && self_collision_weight && num_collision_pairs > 0) ? 1 : 0;
+  a.use_scene = (scene && scene_collision_weight) ? 1 : 0;
+  if (scene) a.sc = *scene;
+  if (!a.use_scene) { a.sc.max_cuboids = 0; a.sc.max_voxel_grids = 0; }
+  a.w_scene = scene_collision_weight; a.eta = activation_distance;
+  a.batch = batch_size; a.nlinks = num_links; a.nspheres = num_spheres; a.npairs = a.use_self ? num_collision_pairs : 0;
+  a.chain_len = link_chain_len; a.num_envs = num_envs > 1 ? num_envs : 1; a.use_multi_env = use_multi_env ? 1 : 0;
+  a.env_query_idx = env_query_idx;
+  ia.x = q; ia.out_grad_q = out_grad_q; ia.tool_frame_map = tool_frame_map; ia.n_tool_frames = n_tool_frames;
+  ia.n_points = batch_size; ia.out_link_pos = out_link_pos; ia.out_link_quat = out_link_quat;
+  ToolPoseArgs &tp = ia.tp;
+  tp.out_distance = out_pose_distance; tp.out_position_distance = out_position_distance;
+  tp.out_rotation_distance = out_rotation_distance; tp.out_goalset_idx = out_goalset_idx;
+  tp.goal_position = goal_position; tp.goal_quat = goal_quat; tp.idxs_goal = idxs_goal;
+  tp.position_orientation_weight = position_orientation_weight;
+  tp.terminal_axes_weight = terminal_pose_axes_weight_factor; tp.non_terminal_axes_weight = terminal_pose_axes_weight_factor;
+  tp.terminal_tolerance = terminal_pose_convergence_tolerance; tp.non_terminal_tolerance = terminal_pose_convergence_tolerance;
+  tp.project_distance_to_goal = project_distance_to_goal;
+  tp.batch = batch_size; tp.horizon = 1; tp.num_links = n_tool_frames; tp.num_goalset = num_goalset; tp.rotation_method = rotation_method;
+  CUROBO_REQUIRE(rotation_method >= 0 && rotation_method <= 2, "%s: rotation_method must be 0, 1 or 2", what);
+  // c-space bound term only (no effort, target or velocity-limited bounds in the IK cost set)
+  ia.p_b = p_b; ia.cs_weight = cspace_weight; ia.cs_eta = cspace_activation_distance; ia.out_cspace_cost = out_cspace_cost;
+  hipStream_t st = (hipStream_t)stream;
+  const int n_rec = a.sc.max_cuboids + a.sc.max_voxel_grids;
+  const FusedLayout lay = fused_layout(kIkPoints, dof, num_links, num_spheres, link_chain_len, a.npairs, n_rec, 0, 0, 1, 0, false);
+  const size_t lds = (size_t)lay.total * sizeof(float);
+  CUROBO_REQUIRE(lds <= 160 * 1024, "%s: 16 configurations do not fit in LDS (%zu bytes); use the unfused kernels", what, lds);
+  const int kinds = (a.sc.max_cuboids > 0 && a.sc.cuboid_has_primitives) ? 7 : ((a.sc.max_cuboids > 0 ? 1 : 0) | (a.sc.max_voxel_grids > 0 ? 2 : 0));
+  const dim3 grid((unsigned)ceil_div(batch_size, kIkPoints)), block(kIkPoints * kFkLanes);
+#define CUROBO_IK_LAUNCH(KD)                                                                                    \
+  do {                                                                                                          \
+    auto kfn = rollout_ik_fused_kernel<KD>;                                                                     \
+    if (lds > 64 * 1024) {                                                                                      \
+      hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+      if (e != hipSuccess) return set_error(CUROBO_HIP_ERR_LAUNCH, "%s: cannot raise LDS limit: %s", what, hipGetErrorString(e)); \
+    }                                                                                                           \
+    hipLaunchKernelGGL(kfn, grid, block, lds, st, ia);                                                          \
+  } while (0)
+  if (kinds == 2) CUROBO_IK_LAUNCH(2);
+  else if (kinds == 3) CUROBO_IK_LAUNCH(3);
+  else if (kinds == 7) CUROBO_IK_LAUNCH(7);
+  else CUROBO_IK_LAUNCH(1);
+#undef CUROBO_IK_LAUNCH
+  return check_launch(what, st);
+}

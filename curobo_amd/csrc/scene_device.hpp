@@ -1,5 +1,5 @@
 // scene_device.hpp -- device functions of the sphere-vs-scene collision cost, shared by
-// scene_collision.hip and the fused rollout kernels (rollout_fused.hip).
+// scene_collision.hip and the fused rollout kernels (fused_device.hpp).
 // Reference (NVIDIA Warp): geom/collision/wp_collision_kernel.py:70-166,
 // wp_sweep_collision_kernel.py:83-260, wp_speed_metric.py:10-93, wp_collision_common.py:11-96,
 // geom/data/data_cuboid.py:461-628, geom/data/data_voxel.py:709-1215, geom/data/helper_pose.py.

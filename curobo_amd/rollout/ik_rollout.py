@@ -34,7 +34,7 @@ class IKRolloutCfg:
     scene_collision_weight: float = 5000.0
     scene_activation_distance: float = 0.0
     self_collision_weight: float = 5000.0
-    #: one fused launch (csrc/rollout_fused.hip, rollout_ik_fused_kernel) for cost + gradient when 16
+    #: one fused launch (csrc/rollout_ik_fused.hip, rollout_ik_fused_kernel) for cost + gradient when 16
     #: configurations fit in LDS; False = the seven drop-in launches
     use_fused: bool = True
 

@@ -738,7 +738,7 @@ int curobo_hip_rollout_fused_shape_id(int padded_horizon, int n_knots, int dof, 
                                       int max_voxel_grids, int bspline_degree, int sweep_steps, int kinds,
                                       int with_trajopt_terms, int plain_launch);
 int curobo_hip_rollout_fused_set_shapes_enabled(int enabled);
-/* Shapes compiled at run time (curobo_amd/backends/fused_jit.py: hipcc on csrc/rollout_fused.hip with the shape on the command
+/* Shapes compiled at run time (curobo_amd/backends/fused_jit.py: hipcc on csrc/rollout_fused_shape.hip with the shape on the command
  * line, as the reference compiles its kernels per robot with NVRTC): `launcher` = the object's curobo_fused_jit_launch,
  * args_bytes = its curobo_fused_jit_args_bytes() (an object built from other sources is refused).  Registered shapes are tried
  * before the built-in table and report ids >= 100 from curobo_hip_rollout_fused_shape_id.

@@ -67,7 +67,7 @@ def test_table_rows_are_consistent_with_the_build():
     assert [int(m) for m in re.findall(r"X\((\d+)\)", each)] == ids
     for k in ids:
         assert re.search(rf"#define CUROBO_FUSED_SHAPE_{k}_KERNELS\(K\)", text)
-        assert ("rollout_fused.hip", f"rollout_fused_shape{k}", [f"-DCUROBO_FUSED_SHAPE_TU={k}"]) in compile_units()
+        assert ("rollout_fused_shape.hip", f"rollout_fused_shape{k}", [f"-DCUROBO_FUSED_SHAPE_TU={k}"]) in compile_units()
 
 
 @pytest.mark.gpu

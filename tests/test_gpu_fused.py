@@ -1,4 +1,4 @@
-"""Parity of the fused rollout kernel (csrc/rollout_fused.hip) against the drop-in kernel
+"""Parity of the fused rollout kernel (csrc/fused_device.hpp, launched through csrc/rollout_fused.hip) against the drop-in kernel
 sequence (same device functions, different summation order) and against the oracle."""
 
 import numpy as np
