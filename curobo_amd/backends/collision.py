@@ -63,10 +63,14 @@ def make_scene(
     return s
 
 
-def build_voxel_coarse_min(voxel_features: torch.Tensor, voxel_params, block: int = 4, dilate: int = 3) -> torch.Tensor:
+def build_voxel_coarse_min(voxel_features: torch.Tensor, voxel_params, block: int = 4, dilate: int = 3,
+                           out: Optional[torch.Tensor] = None, only=None) -> torch.Tensor:
     """fp16 [E, n, n_coarse]: per grid the ESDF minimum over every ``block``^3 block of voxels dilated by ``dilate``
     voxels (``curobo_hip_scene.voxel_coarse_min``).  ``voxel_params`` [E, n, 4] = (nx, ny, nz, voxel_size) on the
-    host.  A min-pool on the device (scene upload time, not the hot path); fp16 minima of fp16 values are exact."""
+    host.  A min-pool on the device (scene upload time, not the hot path); fp16 minima of fp16 values are exact.
+    ``out``: rebuild into this [E, n, n_coarse] buffer in place (the one a scene descriptor and captured graphs already
+    point at) instead of allocating; a grid whose coarse cells do not fit its row raises.  ``only`` = (e, g): just that
+    grid's row (a live update of one grid)."""
     import numpy as np
     import torch.nn.functional as F
 
@@ -78,8 +82,8 @@ def build_voxel_coarse_min(voxel_features: torch.Tensor, voxel_params, block: in
         row = []
         for g in range(n):
             nx, ny, nz = (int(v) for v in prm[e, g, :3])
-            if nx * ny * nz == 0:  # padding slot (environments with fewer grids): its coarse row stays "never culls"
-                row.append(None)
+            if nx * ny * nz == 0 or (only is not None and (e, g) != tuple(only)):
+                row.append(None)  # padding slot (environments with fewer grids): its coarse row stays "never culls"
                 continue
             x = feats[e, g, : nx * ny * nz].reshape(1, 1, nx, ny, nz).float()
             c = -F.max_pool3d(-x, kernel_size=block + 2 * dilate, stride=block, padding=dilate, ceil_mode=True)
@@ -89,11 +93,16 @@ def build_voxel_coarse_min(voxel_features: torch.Tensor, voxel_params, block: in
             row.append(c.reshape(-1).half())
             n_coarse = max(n_coarse, cx * cy * cz)
         grids.append(row)
-    out = torch.full((E, n, n_coarse), -65504.0, dtype=torch.float16, device=voxel_features.device)  # padding never culls
+    if out is None:
+        out = torch.full((E, n, n_coarse), -65504.0, dtype=torch.float16, device=voxel_features.device)  # padding never culls
+    elif tuple(out.shape[:2]) != (E, n) or out.shape[2] < n_coarse or out.dtype != torch.float16:
+        raise ValueError(f"coarse grid needs {n_coarse} cells per grid, the buffer holds {tuple(out.shape)}")
     for e in range(E):
         for g in range(n):
             if grids[e][g] is not None:
-                out[e, g, : grids[e][g].numel()] = grids[e][g]
+                k = grids[e][g].numel()
+                out[e, g, :k] = grids[e][g]
+                out[e, g, k:] = -65504.0
     return out
 
 

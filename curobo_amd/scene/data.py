@@ -87,9 +87,10 @@ def cuboid_scene_arrays(envs: List[List[Dict]], max_n: Optional[int] = None) -> 
 
 def voxel_grid_from_sdf(sdf_fn: Callable[[np.ndarray], np.ndarray], grid_shape: Sequence[int],
                         voxel_size: float, pose7: Sequence[float] = (0, 0, 0, 1, 0, 0, 0),
-                        max_distance: float = 10000.0) -> Dict[str, np.ndarray]:
+                        max_distance: float = 10000.0, name: Optional[str] = None) -> Dict[str, np.ndarray]:
     """One fp16 ESDF grid sampled at voxel centres (align-corners convention of the reference:
-    voxel (i,j,k) centre = ((i,j,k) + 0.5 - n/2) * voxel_size in the grid frame)."""
+    voxel (i,j,k) centre = ((i,j,k) + 0.5 - n/2) * voxel_size in the grid frame).  ``name``: what
+    ``SceneData.update_voxel_features`` / ``update_voxel_data`` find the grid by later."""
     nx, ny, nz = [int(v) for v in grid_shape]
     ax = [(np.arange(n) + 0.5 - n / 2.0) * voxel_size for n in (nx, ny, nz)]
     X, Y, Z = np.meshgrid(*ax, indexing="ij")
@@ -106,7 +107,7 @@ def voxel_grid_from_sdf(sdf_fn: Callable[[np.ndarray], np.ndarray], grid_shape: 
     return {
         "voxel_params": params, "voxel_inv_pose": inv_pose, "voxel_enable": np.ones((1, 1), np.uint8),
         "voxel_count": np.ones((1,), np.int32), "voxel_features": vals,
-        "voxel_max_distance": float(max_distance),
+        "voxel_max_distance": float(max_distance), **({"voxel_names": [[name]]} if name is not None else {}),
     }
 
 
@@ -232,6 +233,87 @@ class SceneData:
         self._write("cuboid_count", (env_idx,), n + 1)
         self.arrays.setdefault("cuboid_names", [[None] * cap for _ in range(self.num_envs)])[env_idx][n] = obstacle.get("name")
         return n
+
+    # ------------------------------------------------------------------ live voxel grids (reference VoxelData.update_features /
+    # update_data, geom/data/data_voxel.py:477-533): what a mapper calls once per frame.  Everything is written into the
+    # tensors the scene descriptor and captured graphs already point at; no pointer changes.
+    def _voxel_slot(self, name: str, env_idx: int) -> int:
+        if self.tensors.get("voxel_features") is None:
+            raise ValueError("the scene has no voxel store")
+        names = list(self._names("voxel", env_idx))[: self._count("voxel", env_idx)]
+        if name not in names:
+            raise ValueError(f"Voxel grid '{name}' not found in environment {env_idx}")
+        return names.index(name)
+
+    def _write_voxel_features(self, env_idx: int, slot: int, features) -> None:
+        import torch
+
+        feats = self.tensors["voxel_features"]
+        E, n = self.tensors["voxel_params"].shape[:2]
+        row = feats.view(E, n, -1)[env_idx, slot]
+        new = torch.as_tensor(features).reshape(-1)
+        capacity, n_new = int(row.numel()), int(new.numel())
+        if n_new > capacity:
+            raise ValueError(f"Feature tensor too large for buffer: capacity={capacity} new={n_new}. Increase max_voxels_per_layer.")
+        row[:n_new].copy_(new.to(device=row.device, dtype=torch.float16))
+        if n_new < capacity:
+            row[n_new:] = 0
+        host = self.arrays.get("voxel_features")
+        if isinstance(host, np.ndarray):
+            h = host.reshape(E, n, -1)[env_idx, slot]
+            h[:n_new] = new.detach().to(torch.float16).cpu().numpy()
+            h[n_new:] = 0
+        elif torch.is_tensor(host) and host.data_ptr() != feats.data_ptr():
+            host.view(E, n, -1)[env_idx, slot].copy_(row)
+
+    def _rebuild_voxel_coarse(self, env_idx: int, slot: int) -> None:
+        """the min-pooled culling grid of one voxel grid, rebuilt into the buffer ``struct.voxel_coarse_min`` points at"""
+        coarse = self.tensors.get("voxel_coarse_min")
+        if coarse is None:
+            return
+        from ..backends.collision import build_voxel_coarse_min
+
+        build_voxel_coarse_min(self.tensors["voxel_features"], self.arrays["voxel_params"], int(self.struct.voxel_coarse_block),
+                               int(self.struct.voxel_coarse_dilate), out=coarse, only=(env_idx, slot))
+
+    def update_voxel_features(self, name: str, features, env_idx: int = 0) -> None:
+        """new ESDF values of a voxel grid of unchanged shape ([nx ny nz] values, x slowest; any float dtype, stored as fp16),
+        in place; the culling grid follows.  Planners and captured optimiser graphs see the new grid on their next call."""
+        slot = self._voxel_slot(name, env_idx)
+        nx, ny, nz = (int(v) for v in self.arrays["voxel_params"][env_idx, slot, :3])
+        n_new = int(np.prod(tuple(features.shape)))
+        if n_new != nx * ny * nz:
+            raise ValueError(f"Feature tensor size {n_new} doesn't match grid dims [{nx}, {ny}, {nz}] = {nx * ny * nz}")
+        self._write_voxel_features(env_idx, slot, features)
+        self._rebuild_voxel_coarse(env_idx, slot)
+
+    def update_voxel_data(self, voxel_grid, env_idx: int = 0, name: Optional[str] = None) -> None:
+        """features, grid shape / voxel size, pose and enable flag of a voxel grid from a ``VoxelGrid`` (looked up by ``name``,
+        default the grid's own); the new grid must fit the feature buffer and the culling buffer the scene was built with"""
+        slot = self._voxel_slot(name if name is not None else voxel_grid.name, env_idx)
+        shape = voxel_grid.get_grid_shape()[0]
+        if voxel_grid.feature_tensor is None:
+            raise ValueError(f"voxel grid '{voxel_grid.name}' has no feature_tensor (the ESDF)")
+        n_new, dims_count = int(np.prod(tuple(voxel_grid.feature_tensor.shape))), int(shape[0] * shape[1] * shape[2])
+        E, n = self.tensors["voxel_params"].shape[:2]
+        capacity = int(self.tensors["voxel_features"].numel() // (E * n))
+        if n_new > capacity:
+            raise ValueError(f"Feature tensor too large for buffer: capacity={capacity} new={n_new}. Increase max_voxels_per_layer.")
+        if n_new != dims_count:
+            raise ValueError(f"Feature tensor size {n_new} doesn't match grid dims {list(shape)} = {dims_count}")
+        coarse = self.tensors.get("voxel_coarse_min")
+        if coarse is not None:
+            b = int(self.struct.voxel_coarse_block)
+            need = int(np.prod([-(-int(v) // b) for v in shape]))
+            if need > int(coarse.shape[2]):
+                raise ValueError(f"Culling grid too large for buffer: capacity={int(coarse.shape[2])} new={need}. "
+                                 "Build the scene with a grid of the largest shape it will hold.")
+        self._write_voxel_features(env_idx, slot, voxel_grid.feature_tensor)
+        self._write("voxel_params", (env_idx, slot), np.array([*shape, voxel_grid.voxel_size], np.float32))
+        pose = voxel_grid.pose if voxel_grid.pose is not None else [0, 0, 0, 1, 0, 0, 0]
+        self._write("voxel_inv_pose", (env_idx, slot, slice(0, 7)), inverse_pose7(self._pose7(pose)).astype(np.float32))
+        self._write("voxel_enable", (env_idx, slot), 1)
+        self._rebuild_voxel_coarse(env_idx, slot)
 
     def clear(self, env_idx: Optional[int] = None) -> None:
         """Remove every cuboid / voxel-grid / mesh obstacle of one environment (``None``: of all), in place (the kernels and

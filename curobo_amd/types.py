@@ -610,6 +610,99 @@ class Pose:
         return self.inverse().multiply(world_pose)
 
 
+@dataclass
+class CameraObservation:
+    """one (or a batch of) camera frame(s) (reference ``_src/types/camera.py``, without file I/O): images are B x H x W
+    (x channels), ``intrinsics`` [b, 3, 3] = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]], ``pose`` the camera in the robot / world
+    frame, ``depth_to_meter`` the factor from depth units to metres (folded into the projection rays)"""
+
+    name: str = "camera_image"
+    rgb_image: Optional[torch.Tensor] = None
+    depth_image: Optional[torch.Tensor] = None
+    image_segmentation: Optional[torch.Tensor] = None
+    projection_matrix: Optional[torch.Tensor] = None
+    projection_rays: Optional[torch.Tensor] = None
+    resolution: Optional[List[int]] = None
+    pose: Optional["Pose"] = None
+    intrinsics: Optional[torch.Tensor] = None
+    timestamp: Optional[torch.Tensor] = None
+    depth_to_meter: float = 0.001
+    feature_grid: Optional[torch.Tensor] = None
+
+    _TENSORS = ("rgb_image", "depth_image", "image_segmentation", "projection_matrix", "projection_rays", "intrinsics",
+                "timestamp", "feature_grid")
+
+    def filter_depth(self, distance: float = 0.01) -> None:
+        """depths below ``distance`` become 0 (no measurement)"""
+        if self.depth_image is None:
+            raise ValueError("depth_image is None, cannot filter depth")
+        self.depth_image = torch.where(self.depth_image < distance, 0, self.depth_image)
+
+    @property
+    def shape(self):
+        if self.rgb_image is None:
+            raise ValueError("rgb_image is None, cannot get shape")
+        return self.rgb_image.shape
+
+    def copy_(self, new_data: "CameraObservation") -> None:
+        """in place, into the tensors this observation already holds"""
+        for k in ("rgb_image", "depth_image", "image_segmentation", "projection_matrix", "projection_rays", "timestamp"):
+            if getattr(self, k) is not None:
+                getattr(self, k).copy_(getattr(new_data, k))
+        if self.pose is not None:
+            self.pose.copy_(new_data.pose)
+        if self.feature_grid is not None and new_data.feature_grid is not None:
+            self.feature_grid.copy_(new_data.feature_grid)
+        self.depth_to_meter = new_data.depth_to_meter
+        self.resolution = new_data.resolution
+
+    def clone(self) -> "CameraObservation":
+        kw = {k: (None if getattr(self, k) is None else getattr(self, k).clone()) for k in self._TENSORS}
+        return CameraObservation(name=self.name, resolution=self.resolution, pose=None if self.pose is None else self.pose.clone(),
+                                 depth_to_meter=self.depth_to_meter, **kw)
+
+    def to(self, device) -> "CameraObservation":
+        for k in self._TENSORS:
+            if getattr(self, k) is not None:
+                setattr(self, k, getattr(self, k).to(device=device))
+        if self.pose is not None:
+            self.pose = self.pose.to(device=device)
+        return self
+
+    def update_projection_rays(self) -> None:
+        from .util.cv import get_projection_rays
+
+        if self.depth_image is None:
+            raise ValueError("depth_image is None, cannot update projection rays")
+        if self.intrinsics is None:
+            raise ValueError("intrinsics is None, cannot update projection rays")
+        intrinsics = self.intrinsics.unsqueeze(0) if self.intrinsics.dim() == 2 else self.intrinsics
+        rays = get_projection_rays(self.depth_image.shape[-2], self.depth_image.shape[-1], intrinsics, depth_to_meter=self.depth_to_meter)
+        if self.projection_rays is None:
+            self.projection_rays = rays
+        self.projection_rays.copy_(rays)
+
+    def get_pointcloud(self, project_to_pose: bool = False) -> torch.Tensor:
+        """points [b, h w, 3] of the depth image in the camera frame, or moved by ``pose``"""
+        from .util.cv import project_depth_using_rays
+
+        if self.depth_image is None:
+            raise ValueError("depth_image is None, cannot generate pointcloud")
+        if self.projection_rays is None:
+            self.update_projection_rays()
+        depth = self.depth_image.unsqueeze(0) if self.depth_image.dim() == 2 else self.depth_image
+        points = project_depth_using_rays(depth, self.projection_rays)
+        if project_to_pose and self.pose is not None:
+            points = self.pose.batch_transform_points(points)
+        return points
+
+    def stack(self, new_observation: "CameraObservation", dim: int = 0) -> "CameraObservation":
+        kw = {k: (None if getattr(self, k) is None else torch.stack((getattr(self, k), getattr(new_observation, k)), dim=dim))
+              for k in self._TENSORS if k != "feature_grid"}
+        return CameraObservation(name=self.name, resolution=self.resolution,
+                                 pose=None if self.pose is None else self.pose.stack(new_observation.pose), **kw)
+
+
 class _FramePoseMembers:
     """what the reference's ``ToolPose`` [batch, horizon, links, 3 | 4] and ``GoalToolPose`` [batch, horizon, links, goal set, 3 | 4]
     share (types/tool_pose.py:54-163, 214-357): the per-frame accessors and the tensor-wise copies, on ``tool_frames`` /

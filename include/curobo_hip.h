@@ -903,6 +903,35 @@ int curobo_hip_graph_knn(int32_t *out_idx, const float *queries, int ld_q, const
                          const float *cspace_distance_weight, int n_queries, int n_nodes, int dof, int k,
                          curobo_hip_stream_t stream);
 
+/* ---- perception (curobo_amd/perception) ---------------------------------------------------------
+ * Depth filter (reference FilterDepth: perception/filter_depth.py): (batch, height, width) fp32 depth ->
+ * depth_out (rejected pixels 0) and valid_mask_out u8 (1 = kept).  Range check (finite, minimum / maximum
+ * distance), flying-pixel rejection (enable_flying_pixel != 0: largest 4-neighbour difference against
+ * flying_tolerance * depth, the tolerance computed by the caller as 0.08 (0.005 / 0.08)^threshold) and
+ * bilateral smoothing (bilateral_kernel_size odd, 0 = off; sigma_*_sq2 = 2 sigma^2).  Kernel sizes below 7 are
+ * one launch; from 7 on the reference's three passes (the fused pass without smoothing into temp_a, a
+ * horizontal pass into temp_b, a vertical pass into depth_out): temp_a / temp_b are (batch, height, width)
+ * fp32 scratch images then, unused (may be NULL) otherwise.  depth_out must not alias depth_in. */
+int curobo_hip_filter_depth(float *depth_out, uint8_t *valid_mask_out, const float *depth_in, float *temp_a,
+                            float *temp_b, int batch, int height, int width, float depth_minimum_distance,
+                            float depth_maximum_distance, int enable_flying_pixel, float flying_tolerance,
+                            int bilateral_kernel_size, float sigma_spatial_sq2, float sigma_depth_sq2,
+                            curobo_hip_stream_t stream);
+
+/* Robot mask (reference RobotSegmenter._mask_op): pixel point = depth * projection_rays[pixel] moved by the
+ * camera pose (position + wxyz quaternion) into the robot frame; mask_out u8 = depth > 0 and some sphere
+ * with radius >= 0 has radius - |point - centre| > -distance_threshold; depth_out = depth with the masked
+ * pixels set to 0.  depth (batch, height, width); projection_rays (ray_batch, height * width, 3),
+ * camera_position (pose_batch, 3), camera_quaternion (pose_batch, 4), robot_spheres (sphere_batch,
+ * num_spheres, 4) = x y z radius, 16-byte aligned; each of the three batches is 1 or batch.  bf16_ops != 0
+ * is the reference's default arithmetic (ops_dtype = bfloat16): depth, rays and spheres rounded to bf16
+ * (nearest even), depth * ray rounded to bf16, everything after that fp32.  One launch; nothing of size
+ * pixels x spheres is written. */
+int curobo_hip_robot_mask(uint8_t *mask_out, float *depth_out, const float *depth, const float *projection_rays,
+                          const float *camera_position, const float *camera_quaternion, const float *robot_spheres,
+                          int batch, int height, int width, int num_spheres, int ray_batch, int pose_batch,
+                          int sphere_batch, float distance_threshold, int bf16_ops, curobo_hip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
