@@ -140,16 +140,16 @@ class GraphFeasibility:
     def uses_fused(self) -> bool:
         """the fused launch covers the scene (no meshes) and 16 of the robot's configurations fit in LDS"""
         from ..backends import rollout as rollout_hip
+        from ..rollout.base import obstacle_slots, scene_has_meshes
 
         s = self.checker.scene
-        if s is not None and (getattr(s, "meshes", None) is not None or getattr(s.struct, "mesh_set", None) is not None):
+        if scene_has_meshes(s) or getattr(s, "meshes", None) is not None:
             return False
         k = self.kin
         sc = k.self_collision
         pairs = 0 if sc is None or sc.collision_pairs is None else int(sc.collision_pairs.shape[0])
-        n_obs = 0 if s is None else s.struct.max_cuboids + s.struct.max_voxel_grids
         L, S = int(k.fixed_transforms.shape[0]), int(k.link_sphere_idx_map.shape[0])
-        need = rollout_hip.rollout_ik_fused_lds_bytes(k.num_dof, L, S, pairs, int(k.link_chain_data.shape[0]), n_obs)
+        need = rollout_hip.rollout_ik_fused_lds_bytes(k.num_dof, L, S, pairs, int(k.link_chain_data.shape[0]), obstacle_slots(s))
         return need <= rollout_hip.FUSED_LDS_LIMIT - 64 and k.num_dof <= 64 and L <= 128 and S < 4096
 
     def _struct(self):

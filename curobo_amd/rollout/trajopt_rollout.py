@@ -23,13 +23,11 @@ import torch
 from ..backends import collision as collision_hip
 from ..backends import cost as cost_hip
 from ..backends import dynamics as dynamics_hip
-from ..backends import geometry as geometry_hip
-from ..backends import kinematics as kinematics_hip
 from ..backends import rollout as rollout_hip
-from ..backends import trajectory as trajectory_hip
 from ..robot.kinematics_params import KinematicsParams
-from ..scene.data import SceneData, validate_env_query_idx
+from ..scene.data import SceneData
 from ..util.stream_scope import inside_forked_stream
+from .base import BSplineHorizon, BSplineRolloutBase, PoseTerms
 
 
 _limit_vectors: dict = {}
@@ -58,7 +56,7 @@ def joint_limit_vector(value, dof: int, device, name: str = "limit") -> torch.Te
 
 
 @dataclass
-class TrajOptRolloutCfg:
+class TrajOptRolloutCfg(BSplineHorizon):
     n_knots: int = 12
     interpolation_steps: int = 2
     bspline_degree: int = 3
@@ -116,34 +114,20 @@ class TrajOptRolloutCfg:
     cspace_target_weight: float = 0.0
     cspace_non_terminal_weight_factor: float = 1.0
 
-    @property
-    def horizon(self) -> int:
-        return (self.n_knots + self.bspline_degree + 1) * self.interpolation_steps
 
-    @property
-    def padded_horizon(self) -> int:
-        return self.horizon + 1
-
-
-class TrajOptRollout:
+class TrajOptRollout(PoseTerms, BSplineRolloutBase):
     """cost[B] and d cost / d knots [B, n_knots * D] of B trajectories from one shared start state
     towards per-row goal poses (goal joint state = implicit rest at the last knot)."""
 
+    with_trajopt_terms = True
+
     def __init__(self, kin: KinematicsParams, scene: Optional[SceneData], batch_size: int,
                  cfg: Optional[TrajOptRolloutCfg] = None):
-        self.kin, self.scene, self.cfg = kin, scene, cfg or TrajOptRolloutCfg()
-        self.device = kin.device
-        self.action_horizon, self.action_dim = self.cfg.n_knots, kin.num_dof
-        d, T, D, c = self.device, kin.num_pose_links, kin.num_dof, self.cfg
+        c = cfg or TrajOptRolloutCfg()
+        super().__init__(kin, scene, c, c.self_collision_weight, c.scene_collision_weight, c.scene_activation_distance)
+        d, D = self.device, kin.num_dof
         f = lambda v: torch.tensor(v, device=d, dtype=torch.float32)  # noqa: E731
-        self._w_self, self._w_scene = f([c.self_collision_weight]), f([c.scene_collision_weight])
-        self._eta_scene, self._speed_dt = f([c.scene_activation_distance]), f([c.traj_dt])
-        self._traj_dt, self._implicit_goal = f([c.traj_dt]), torch.zeros(1, dtype=torch.uint8, device=d)
-        self._pose_w = f(c.pose_weight)
-        self._axes_w, self._axes_w0 = torch.ones(T, 6, device=d), torch.full((T, 6), float(c.non_terminal_pose_factor), device=d)
-        self._tol = f([c.pose_convergence_tolerance] * T)
-        self._tol0 = self._tol.clone()
-        self._project = torch.zeros(T, dtype=torch.uint8, device=d)
+        self._init_pose_terms(c.pose_weight, c.pose_convergence_tolerance, c.non_terminal_pose_factor)
         self._cs_w, self._cs_eta, self._cs_reg = f(c.cspace_weight), f(c.cspace_activation_distance), f(c.cspace_regularization)
         self._p_b, self._v_b = kin.joint_limits_position.contiguous(), kin.joint_limits_velocity.contiguous()
         ones = torch.ones(D, device=d)
@@ -161,67 +145,22 @@ class TrajOptRollout:
         # joint-position tracking: _cs_target [B, D] holds every trajectory's target (allocated with the batch buffers); weight 0 = off
         self._cs_tw = torch.zeros(1, device=d)  # (off until enable_cspace_target)
         self._cs_nt, self._cs_dofw = f([c.cspace_non_terminal_weight_factor]), torch.ones(D, device=d)
-        self.batch_size = 0
-        self._fused_ok: Optional[bool] = None
-        self._dispatch = None
         self._terms = None
         self.update_batch_size(batch_size)
         self.update_start_state(None)
 
-    def update_batch_size(self, B: int) -> None:
-        if B == self.batch_size:
-            return
-        k, d, c = self.kin, self.device, self.cfg
-        H, D, S, L, T = c.padded_horizon, k.num_dof, k.num_spheres, k.num_links, k.num_pose_links
-        z = lambda *s, dt=torch.float32: torch.zeros(*s, device=d, dtype=dt)  # noqa: E731
-        self.batch_size = B
-        self._fused_ok = None  # (the choice between the fused launch and the kernel sequence depends on the batch)
-        self.position, self.velocity, self.acceleration, self.jerk = z(B, H, D), z(B, H, D), z(B, H, D), z(B, H, D)
-        self.out_dt, self.state_dt = z(B), torch.full((B,), c.traj_dt, device=d)
-        self.start_idx, self.goal_idx, self.env_query_idx = z(B, dt=torch.int32), z(B, dt=torch.int32), z(B, dt=torch.int32)
-        self.link_pos, self.link_quat = z(B, H, T, 3), z(B, H, T, 4)
-        self.robot_spheres, self.cumul_mat, self.com = z(B, H, S, 4), z(B, H, L, 3, 4), z(B, H, 4)
-        self.pose_cost, self.pose_pos_dist, self.pose_rot_dist = z(B, H, 2 * T), z(B, H, T), z(B, H, T)
-        self.pose_grad_pos, self.pose_grad_quat = z(B, H, T, 3), z(B, H, T, 4)
-        self.goalset_idx = z(B, H, T, dt=torch.int32)
+    def _alloc(self, B: int) -> None:
+        c, z = self.cfg, self._zeros
+        H, D = c.padded_horizon, self.action_dim
+        self._alloc_bspline_buffers(B)
+        self._alloc_robot_buffers(B, H)
+        self._alloc_pose_buffers(B, H, 1)
+        self.state_dt = torch.full((B,), c.traj_dt, device=self.device)
         self.cspace_cost = z(B, H, D)
         self.cs_gp, self.cs_gv, self.cs_ga, self.cs_gj = z(B, H, D), z(B, H, D), z(B, H, D), z(B, H, D)
-        self.self_dist, self.self_grad, self.self_sparse = z(B, H, 1), z(B, H, S, 4), z(B, H, S, dt=torch.uint8)
-        self.scene_dist, self.scene_grad = z(B, H, S), z(B, H, S, 4)
-        self._pd, self._bbmv, self._bbmi = z(1), z(1), z(2, dt=torch.int16)
-        self.point_cost, self.cost = z(B, H, 1), z(B)
-        self.grad_q, self.grad_knots = z(B, H, D), z(B, c.n_knots, D)
-        self.idxs_goal, self._idx0 = z(B, dt=torch.int32), z(B, dt=torch.int32)
+        self.point_cost = z(B, H, 1)
         self._cs_target = z(B, D)  # the target of every trajectory (update_cspace_target gathers its rows here)
-        self._cs_target_idx = torch.arange(B, device=d, dtype=torch.int32)
-        self.goal_position, self.goal_quat = z(1, T, 1, 3), z(1, T, 1, 4)
-        self.goal_quat[..., 0] = 1.0
-
-    def update_start_state(self, start_position: Optional[torch.Tensor], start_velocity: Optional[torch.Tensor] = None,
-                           start_acceleration: Optional[torch.Tensor] = None, start_idx: Optional[torch.Tensor] = None) -> None:
-        """Start state(s) of the trajectories: position [n, D] (+ velocity / acceleration for a robot in motion: the
-        B-spline's fixed knots reproduce them, bspline_boundary_constraint.cuh:330-367); ``start_idx`` [B] picks the
-        start state of every trajectory (reference ``idxs_start``; default: state 0)."""
-        D, d = self.action_dim, self.device
-        if start_position is None:
-            start_position = torch.zeros(1, D, device=d)
-        sp = start_position.to(d, torch.float32).reshape(-1, D).contiguous()
-        if start_idx is not None:
-            self.start_idx.copy_(start_idx.to(device=d, dtype=torch.int32).reshape(-1))
-        if getattr(self, "start_pos", None) is not None and self.start_pos.shape == sp.shape:
-            self.start_pos.copy_(sp)  # keep the pointers a captured hipGraph holds
-            self.start_vel.copy_(start_velocity.to(d, torch.float32).reshape(-1, D)) if start_velocity is not None else self.start_vel.zero_()
-            self.start_acc.copy_(start_acceleration.to(d, torch.float32).reshape(-1, D)) if start_acceleration is not None else self.start_acc.zero_()
-            return
-        self.start_pos = sp.clone()
-        n = self.start_pos.shape[0]
-        self.start_vel, self.start_acc, self.start_jerk = (torch.zeros(n, D, device=d) for _ in range(3))
-        if start_velocity is not None:
-            self.start_vel.copy_(start_velocity.to(d, torch.float32).reshape(-1, D))
-        if start_acceleration is not None:
-            self.start_acc.copy_(start_acceleration.to(d, torch.float32).reshape(-1, D))
-        if getattr(self, "goal_pos", None) is None:
-            self.goal_pos, self.goal_vel, self.goal_acc, self.goal_jerk = (torch.zeros(1, D, device=d) for _ in range(4))
+        self._cs_target_idx = torch.arange(B, device=self.device, dtype=torch.int32)
 
     def update_goal_state(self, goal_joint_position: Optional[torch.Tensor], goal_idx: Optional[torch.Tensor] = None,
                           implicit: bool = True) -> None:
@@ -269,37 +208,13 @@ class TrajOptRollout:
 
     def compute_state_from_action(self, act_seq: torch.Tensor) -> None:
         """knots -> position / velocity / acceleration / jerk buffers only (reference ``compute_state_from_action``)"""
-        c, B = self.cfg, self.batch_size
-        trajectory_hip.launch_bspline_interpolation_forward_kernel(
-            self.position, self.velocity, self.acceleration, self.jerk, self.out_dt, act_seq, self.start_pos,
-            self.start_vel, self.start_acc, self.start_jerk, self.goal_pos, self.goal_vel, self.goal_acc, self.goal_jerk,
-            self.start_idx, self.goal_idx, self._traj_dt, self._implicit_goal, B, c.padded_horizon, self.action_dim, c.n_knots,
-            c.bspline_degree)
-
-    use_multi_env = False
-
-    def update_env_query_idx(self, env_query_idx: Optional[torch.Tensor]) -> None:
-        """Scene environment of every trajectory (reference ``idxs_env`` / ``use_multi_env``,
-        cost/cost_scene_collision.py:58-198; batch-env planning, motion_planner_batch.py):
-        trajectory b collides with the obstacles of environment ``env_query_idx[b]``; ``None`` = env 0.
-        Switching between ``None`` and indices changes a kernel argument: re-capture graphs after it."""
-        self.use_multi_env = env_query_idx is not None
-        if env_query_idx is None:
-            self.env_query_idx.zero_()
-        else:
-            validate_env_query_idx(env_query_idx, self.scene, self.kin.num_envs)
-            self.env_query_idx.copy_(env_query_idx.to(device=self.device, dtype=torch.int32).reshape(-1))
+        self._bspline_forward(act_seq)
 
     def update_goals(self, goal_position: torch.Tensor, goal_quat: torch.Tensor, idxs_goal: torch.Tensor) -> None:
         """goal_position [G, T, num_goalset, 3], goal_quat (wxyz) [G, T, num_goalset, 4], idxs_goal [B]: every point is
         scored against the closest member of its row's goal set (reference goal sets, cost/tool_pose kernels)."""
-        if goal_position.shape == self.goal_position.shape:
-            self.goal_position.copy_(goal_position)
-            self.goal_quat.copy_(goal_quat)
-        else:  # new buffers (and a new goal-set size): the fused launch's argument block is rebuilt on the next evaluation
-            self.goal_position = goal_position.to(self.device, torch.float32).contiguous().clone()
-            self.goal_quat = goal_quat.to(self.device, torch.float32).contiguous().clone()
-            self._terms = None
+        if self._update_goal_poses(goal_position, goal_quat):
+            self._terms = None  # (a new goal-set size: the fused launch's argument block is rebuilt on the next evaluation)
         self.idxs_goal.copy_(idxs_goal.to(torch.int32))
 
     def update_cspace_target(self, target_position: torch.Tensor, idxs_target: Optional[torch.Tensor] = None,
@@ -329,27 +244,11 @@ class TrajOptRollout:
     def disable_cspace_target(self) -> None:
         self._cs_tw.zero_()
 
-    def update_tool_pose_criteria(self, criteria) -> None:
-        """``{tool frame: ToolPoseCriteria}`` -> the per-frame factor / tolerance / projection rows the pose cost reads
-        (reference ToolPoseCost.update_tool_pose_criteria); written in place, so captured graphs see the new values"""
-        for name, c in criteria.items():
-            if name not in self.kin.tool_frames:
-                raise ValueError(f"tool frame {name} not in {self.kin.tool_frames}")
-            i, f = self.kin.tool_frames.index(name), lambda v: torch.tensor(v, device=self.device, dtype=torch.float32)  # noqa: E731
-            self._axes_w[i].copy_(f(c.terminal_pose_axes_weight_factor))
-            self._axes_w0[i].copy_(f(c.non_terminal_pose_axes_weight_factor))
-            self._tol[i].copy_(f(c.terminal_pose_convergence_tolerance))
-            self._tol0[i].copy_(f(c.non_terminal_pose_convergence_tolerance))
-            self._project[i] = int(bool(c.project_distance_to_goal))
-
     # ------------------------------------------------------------------ forward + backward
     def evaluate_action(self, act_seq: torch.Tensor, with_gradient: bool = True) -> torch.Tensor:
         k, c, B = self.kin, self.cfg, self.batch_size
         H, D, S, T = c.padded_horizon, k.num_dof, k.num_spheres, k.num_pose_links
-        trajectory_hip.launch_bspline_interpolation_forward_kernel(
-            self.position, self.velocity, self.acceleration, self.jerk, self.out_dt, act_seq, self.start_pos,
-            self.start_vel, self.start_acc, self.start_jerk, self.goal_pos, self.goal_vel, self.goal_acc, self.goal_jerk,
-            self.start_idx, self.goal_idx, self._traj_dt, self._implicit_goal, B, H, D, c.n_knots, c.bspline_degree)
+        self._bspline_forward(act_seq)
         tq = c.use_torque_limits
         # The joint-space chain (inverse dynamics -> c-space STATE cost -> RNEA VJP) reads the B-spline samples only, the
         # task-space chain (FK -> tool pose -> self / scene collision -> FK VJP) the joint positions only: with torque
@@ -403,35 +302,14 @@ class TrajOptRollout:
                     self.cs_ga.view(n, D).add_(self._rnea_g[2])
         # (the task-space chain is enqueued AFTER the joint-space chain: the few, long-running workgroups of the tree walks
         # take their slots on an empty chip; started behind the collision kernels they wait for LDS that those keep taking)
-        kinematics_hip.launch_kinematics_forward_spheres(
-            self.link_pos, self.link_quat, self.robot_spheres, self.com, self.cumul_mat, self.position,
-            k.fixed_transforms, k.link_spheres, k.link_masses_com, k.joint_map_type, k.joint_map, k.link_map,
-            k.tool_frame_map, k.link_sphere_idx_map, k.joint_offset_map, self.env_query_idx, k.num_envs, B * H, H, D, S,
-            32, True, False)
-        cost_hip.tool_pose_distance(
-            self.pose_cost, self.pose_pos_dist, self.pose_rot_dist, self.pose_grad_pos, self.pose_grad_quat,
-            self.goalset_idx, self.link_pos, self.link_quat, self.goal_position, self.goal_quat, self.idxs_goal,
-            self._pose_w, self._axes_w, self._axes_w0, self._tol, self._tol0, self._project, B, H, T, int(self.goal_position.shape[2]),
-            c.rotation_method)
-        sc = k.self_collision
-        geometry_hip.self_collision_distance(
-            self.self_dist, self.self_grad, self._pd, self.self_sparse, self.robot_spheres, sc.sphere_padding,
-            self._w_self, sc.collision_pairs, self._bbmv, self._bbmi, 1, 256, B, H, S, sc.collision_pairs.shape[0],
-            False, True)
+        self._fk_forward(self.position)
+        self._pose_term()
+        self._self_collision()
         use_scene = self.scene is not None
         if use_scene:
-            collision_hip.sphere_obstacle_collision(
-                self.scene_dist, self.scene_grad, self.robot_spheres, self.scene.struct, self._w_scene, self._eta_scene,
-                self.env_query_idx, B, H, S, self.use_multi_env, 3 if c.use_sweep else 0, c.use_sweep and c.use_speed_metric,
-                self._speed_dt)
+            self._scene_collision(c.use_sweep, c.use_speed_metric, self._speed_dt)
         if with_gradient:
-            kinematics_hip.launch_kinematics_backward(
-                self.grad_q, self.pose_grad_pos, self.pose_grad_quat, self.self_grad, self.com, self.com,
-                self.pose_grad_pos, self.cumul_mat, k.link_spheres, k.link_masses_com, k.link_map, k.joint_map,
-                k.joint_map_type, k.tool_frame_map, k.link_sphere_idx_map, k.link_chain_data, k.link_chain_offsets,
-                k.joint_links_data, k.joint_links_offsets, k.joint_affects_endeffector, k.joint_offset_map,
-                self.env_query_idx, k.num_envs, B * H, H, D, S, False, False,
-                grad_spheres_b=self.scene_grad if use_scene else None)
+            self._fk_backward(self.pose_grad_pos, self.pose_grad_quat, self.self_grad, self.scene_grad if use_scene else None)
         if side is not None:
             torch.cuda.current_stream(self.device).wait_stream(side)
         # per-point totals (+ the c-space position gradient into grad_q), then the sum over the horizon
@@ -440,45 +318,18 @@ class TrajOptRollout:
             self.cs_gp if with_gradient else None, self.self_dist, self.scene_dist if use_scene else None, B * H, T, D, S)
         collision_hip.trajectory_cost_sum(self.cost, None, self.point_cost, B, H, 1)
         if with_gradient:
-            trajectory_hip.launch_bspline_interpolation_backward_kernel(
-                self.grad_knots, self.grad_q, self.cs_gv, self.cs_ga, self.cs_gj, self._traj_dt, self.goal_idx,
-                self._implicit_goal, B, H, D, c.n_knots, c.bspline_degree, False)
+            self._bspline_backward(self.cs_gv, self.cs_ga, self.cs_gj)
         return self.cost
 
     # ------------------------------------------------------------------ fused
     def fused_available(self) -> bool:
         k, c = self.kin, self.cfg
-        n_obs = (self.scene.struct.max_cuboids + self.scene.struct.max_voxel_grids) if self.scene is not None else 0
-        need = rollout_hip.rollout_trajopt_fused_lds_bytes(
-            c.padded_horizon, k.num_dof, k.num_links, k.num_spheres, int(k.self_collision.collision_pairs.shape[0]),
-            int(k.link_chain_data.shape[0]), n_obs, True)
-        ok = need <= rollout_hip.FUSED_LDS_LIMIT and k.num_links <= 128 and k.num_dof <= 64
-        if self.scene is not None and getattr(self.scene.struct, "mesh_set", None) is not None:
-            ok = False  # mesh obstacles are queried by their own launch (BVH): the kernel sequence runs
+        shape = (c.padded_horizon, k.num_dof, k.num_links, k.num_spheres, int(k.self_collision.collision_pairs.shape[0]),
+                 int(k.link_chain_data.shape[0]), self._obstacle_slots())
+        ok = k.num_dof <= 64 and self._fused_fits(rollout_hip.rollout_trajopt_fused_lds_bytes(*shape, True))
         if ok and c.use_torque_limits:  # inverse dynamics inside the launch borrows LDS regions that are dead by then
-            ok = rollout_hip.rollout_trajopt_fused_torque_fits(
-                c.padded_horizon, k.num_dof, k.num_links, k.num_spheres, int(k.self_collision.collision_pairs.shape[0]),
-                int(k.link_chain_data.shape[0]), n_obs)
+            ok = rollout_hip.rollout_trajopt_fused_torque_fits(*shape)
         return ok
-
-    def _maybe_jit_shape(self) -> None:
-        from ..backends import fused_jit
-
-        if not (self.cfg.jit_shape or fused_jit.enabled_by_env()):
-            return
-        k, c = self.kin, self.cfg
-        lanes = getattr(k.self_collision.collision_pairs, "_self_lane_lists", None)
-        n_obs = (self.scene.struct.max_cuboids + self.scene.struct.max_voxel_grids) if self.scene is not None else 0
-        fused_jit.ensure_shape(c.padded_horizon, c.n_knots, k.num_dof, k.num_links, k.num_spheres,
-                               int(k.self_collision.collision_pairs.shape[0]), int(k.link_chain_data.shape[0]),
-                               int(lanes[1]) if lanes is not None else 0, n_obs, with_trajopt_terms=True)
-
-    def _dispatch_order(self):
-        if not self.cfg.longest_first_dispatch:
-            return None
-        if self._dispatch is None:
-            self._dispatch = rollout_hip.DispatchOrder(self.batch_size, self.cost.device)
-        return self._dispatch
 
     def cost_and_gradient_fused(self, act_seq: torch.Tensor, with_metrics: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """Same numbers as ``evaluate_action`` from one launch (the struct of optional terms is
@@ -508,10 +359,8 @@ class TrajOptRollout:
                if c.use_torque_limits else {}))
         rollout_hip.rollout_trajopt_fused(
             self._terms, self.cost, self.grad_knots, self.position if m else None, self.robot_spheres if m else None,
-            act_seq, self.start_pos, self.start_vel, self.start_acc, self.start_jerk, self.goal_pos, self.goal_vel,
-            self.goal_acc, self.goal_jerk, self.start_idx, self.goal_idx, self._traj_dt, self._implicit_goal,
-            k.fixed_transforms, k.link_spheres, k.joint_map_type, k.joint_map, k.link_map, k.link_sphere_idx_map,
-            k.link_chain_data, k.link_chain_offsets, k.joint_offset_map, sc.sphere_padding, self._w_self,
+            act_seq, *self._bspline_args(), k.fixed_transforms, k.link_spheres, k.joint_map_type, k.joint_map, k.link_map,
+            k.link_sphere_idx_map, k.link_chain_data, k.link_chain_offsets, k.joint_offset_map, sc.sphere_padding, self._w_self,
             sc.collision_pairs, self.scene.struct if use_scene else None, self._w_scene if use_scene else None,
             self._eta_scene, self._speed_dt, self.env_query_idx, k.num_envs, self.use_multi_env, B, c.padded_horizon, self.action_dim,
             c.n_knots, c.bspline_degree, 3 if c.use_sweep else 0, c.use_sweep and c.use_speed_metric,
@@ -519,15 +368,11 @@ class TrajOptRollout:
         return self.cost, self.grad_knots.view(B, -1)
 
     def cost_and_gradient(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        act = x.view(self.batch_size, self.cfg.n_knots, self.action_dim)
-        if self.cfg.use_fused:
-            if self._fused_ok is None:
-                c = self.cfg
-                too_big = c.use_torque_limits and c.overlap_dynamics and self.batch_size > c.fused_torque_max_batch
-                self._fused_ok = self.fused_available() and not too_big
-                if self._fused_ok:
-                    self._maybe_jit_shape()
-            if self._fused_ok:
-                return self.cost_and_gradient_fused(act)
+        c = self.cfg
+        act = x.view(self.batch_size, c.n_knots, self.action_dim)
+        # (with torque limits the fused launch loses to the kernel sequence and its side stream beyond fused_torque_max_batch)
+        too_big = c.use_torque_limits and c.overlap_dynamics and self.batch_size > c.fused_torque_max_batch
+        if c.use_fused and self._fused_chosen(veto=too_big):
+            return self.cost_and_gradient_fused(act)
         cost = self.evaluate_action(act, with_gradient=True)
         return cost, self.grad_knots.view(self.batch_size, -1)

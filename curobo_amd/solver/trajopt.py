@@ -39,6 +39,7 @@ import torch
 from ..distributed import global_topk, shard_range
 from ..optim import LBFGSOpt, LBFGSOptCfg
 from ..robot.kinematics_params import KinematicsParams
+from ..rollout.base import RobotRolloutBase, fk_forward_spheres
 from ..rollout.trajopt_rollout import TrajOptRollout, TrajOptRolloutCfg, joint_limit_vector
 from ..scene.data import SceneData
 from ..util.graph_capture import capture_graph
@@ -374,17 +375,12 @@ class TrajOptSolver:
 
     def _tool_pose_of(self, q: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """forward kinematics of q [n, D] -> tool-frame position [n, T, 3] and quaternion [n, T, 4]"""
-        from ..backends import kinematics as kinematics_hip
-
         k, n, dev = self.kin, q.shape[0], self.device
         T, S, L = k.num_pose_links, k.num_spheres, k.num_links
         pos, quat = torch.zeros(n, 1, T, 3, device=dev), torch.zeros(n, 1, T, 4, device=dev)
         sph, com, cumul = torch.zeros(n, 1, max(S, 1), 4, device=dev), torch.zeros(n, 1, 4, device=dev), torch.zeros(n, 1, L, 3, 4, device=dev)
         env = torch.zeros(n, dtype=torch.int32, device=dev)
-        kinematics_hip.launch_kinematics_forward_spheres(
-            pos, quat, sph, com, cumul, q.contiguous(), k.fixed_transforms, k.link_spheres, k.link_masses_com, k.joint_map_type,
-            k.joint_map, k.link_map, k.tool_frame_map, k.link_sphere_idx_map, k.joint_offset_map, env, k.num_envs, n, 1,
-            k.num_dof, S, 32, True, False)
+        fk_forward_spheres(k, pos, quat, sph, com, cumul, q.contiguous(), env, n, 1)
         return pos.view(n, T, 3), quat.view(n, T, 4)
 
     def _goal_sets(self, goal_position: torch.Tensor, goal_quat: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -641,35 +637,23 @@ class TrajOptSolver:
         return out, last, traj_dt
 
 
-class _InterpolatedCheck:
+class _InterpolatedCheck(RobotRolloutBase):
     """Feasibility of optimised seeds on the trajectory re-sampled at the interpolation dt (reference
     ``_interpolate_and_compute_metrics`` + the ``interpolated_rollout`` constraints, solver_trajopt.py:475-497):
     single-dt B-spline re-interpolation -> FK -> self and (discrete) scene collision, joint limits on position /
-    velocity / acceleration / jerk.  Samples after a trajectory's last step repeat its final state."""
+    velocity / acceleration / jerk.  Samples after a trajectory's last step repeat its final state.  A rollout without a
+    gradient: unit weights, zero activation distance."""
 
     def __init__(self, kin: KinematicsParams, scene: Optional[SceneData], rc: TrajOptRolloutCfg):
-        self.kin, self.scene, self.rc = kin, scene, rc
-        self._shape = None
+        super().__init__(kin, scene, rc, 1.0, 1.0, 0.0)
+        self.rc = rc
 
-    def _alloc(self, B: int, n: int) -> None:
-        if self._shape == (B, n):
-            return
-        k, d = self.kin, self.kin.device
-        S, L, T = k.num_spheres, k.num_links, k.num_pose_links
-        z = lambda *s, dt=torch.float32: torch.zeros(*s, device=d, dtype=dt)  # noqa: E731
-        self.link_pos, self.link_quat, self.com = z(B, n, T, 3), z(B, n, T, 4), z(B, n, 4)
-        self.spheres, self.cumul = z(B, n, S, 4), z(B, n, L, 3, 4)
-        self.self_dist, self.self_grad, self.sparse = z(B, n, 1), z(B, n, S, 4), z(B, n, S, dt=torch.uint8)
-        self.scene_dist, self.scene_grad = z(B, n, S), z(B, n, S, 4)
-        self._pd, self._bbmv, self._bbmi = z(1), z(1), z(2, dt=torch.int16)
-        self._one, self._zero = torch.ones(1, device=d), z(1)
-        self._env0 = z(B, dt=torch.int32)
-        self._shape = (B, n)
+    def _resize(self, B: int, n: int) -> None:
+        if (self.batch_size, self._H) != (B, n):
+            self._alloc_robot_buffers(B, n)
+            self._env0 = self.env_query_idx
 
     def feasible(self, knots, dt, start, start_rows, goal, implicit, interpolation_dt, env_query_idx, static_steps=None) -> torch.Tensor:
-        from ..backends import collision as collision_hip
-        from ..backends import geometry as geometry_hip
-        from ..backends import kinematics as kinematics_hip
         from ..util.trajectory import calculate_traj_steps, interpolate_bspline_knots
 
         k, rc, dev = self.kin, self.rc, self.kin.device
@@ -689,22 +673,14 @@ class _InterpolatedCheck:
         (pos, vel, acc, jerk), last = interpolate_bspline_knots(knots, knot_dt, interpolation_dt, st, gl if implicit else None,
                                                                 imp if implicit else None, rc.bspline_degree, out_steps=n,
                                                                 out_steps_is_bound=static_steps is not None)
-        self._alloc(B, n)
-        S = k.num_spheres
-        env = self._env0 if env_query_idx is None else env_query_idx
-        kinematics_hip.launch_kinematics_forward_spheres(
-            self.link_pos, self.link_quat, self.spheres, self.com, self.cumul, pos, k.fixed_transforms, k.link_spheres,
-            k.link_masses_com, k.joint_map_type, k.joint_map, k.link_map, k.tool_frame_map, k.link_sphere_idx_map,
-            k.joint_offset_map, env, k.num_envs, B * n, n, D, S, 32, True, False)
-        sc = k.self_collision
-        geometry_hip.self_collision_distance(
-            self.self_dist, self.self_grad, self._pd, self.sparse, self.spheres, sc.sphere_padding, self._one,
-            sc.collision_pairs, self._bbmv, self._bbmi, 1, 256, B, n, S, sc.collision_pairs.shape[0], False, True)
+        self._resize(B, n)
+        # (the caller's index tensor is read where it lies: no copy inside a captured pass)
+        self.env_query_idx, self.use_multi_env = self._env0 if env_query_idx is None else env_query_idx, env_query_idx is not None
+        self._fk_forward(pos)
+        self._self_collision()
         ok = self.self_dist.view(B, -1).sum(-1) <= 0.0
         if self.scene is not None:
-            collision_hip.sphere_obstacle_collision(
-                self.scene_dist, self.scene_grad, self.spheres, self.scene.struct, self._one, self._zero, env, B, n, S,
-                env_query_idx is not None, 0, False, None)
+            self._scene_collision()
             ok &= self.scene_dist.view(B, -1).sum(-1) <= 0.0
         lo, hi = k.joint_limits_position[0], k.joint_limits_position[1]
         ok &= ((pos >= lo - 1e-4) & (pos <= hi + 1e-4)).all(-1).all(-1)

@@ -305,3 +305,32 @@ def test_rollout_protocol_members(device):
     assert ro.cost.data_ptr() == ptr
     torch.testing.assert_close(c2, m["self_collision_cost"], rtol=2e-5, atol=1e-3)  # only self collision is left
     assert float(ro.compute_metrics_from_action(x)["scene_collision_cost"].abs().max()) == 0.0
+
+
+def test_update_batch_size_after_a_fused_launch(device):
+    """A rollout that made a fused launch and is then given another batch size evaluates like a freshly built rollout of that
+    batch, bit for bit: the longest-first dispatch workspace and the fused / kernel-sequence choice belong to one batch size."""
+    from curobo_amd.rollout import CollisionRollout, CollisionRolloutCfg, TrajOptRollout, TrajOptRolloutCfg
+
+    model, kin, arrays, _, knots, start, first = _setup(device, seeds=40, fused=True)
+    x = torch.as_tensor(knots, device=device).reshape(40, -1)
+    start = torch.as_tensor(start, device=device)
+    T = kin.num_pose_links
+    goal_position = torch.tensor([0.4, 0.2, 0.4], device=device).expand(1, T, 1, 3).contiguous()
+    goal_quat = torch.tensor([0.0, 1.0, 0.0, 0.0], device=device).expand(1, T, 1, 4).contiguous()
+
+    def ready(ro):  # (the state a change of batch size resets)
+        ro.update_start_state(start)
+        if isinstance(ro, TrajOptRollout):
+            ro.update_goals(goal_position, goal_quat, torch.zeros(ro.batch_size, dtype=torch.int32, device=device))
+        return ro
+
+    for cls, cfg in ((CollisionRollout, CollisionRolloutCfg()), (TrajOptRollout, TrajOptRolloutCfg())):
+        ro = ready(cls(kin, first.scene, 24, cfg))
+        assert cfg.use_fused and cfg.longest_first_dispatch and ro.fused_available()
+        ro.cost_and_gradient(x[:24].contiguous())
+        ro.update_batch_size(40)
+        cost, grad = [t.clone() for t in ready(ro).cost_and_gradient(x)]
+        assert cost.shape == (40,) and grad.shape == x.shape
+        fresh_cost, fresh_grad = ready(cls(kin, first.scene, 40, cfg)).cost_and_gradient(x)
+        assert torch.equal(cost, fresh_cost) and torch.equal(grad, fresh_grad), cls.__name__
