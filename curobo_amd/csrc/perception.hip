@@ -25,7 +25,10 @@ namespace curobo_hip {
 //             exp(-(dn - dc)^2 / 2 sigma_d^2), rows outer / columns inner; the centre is kept when the weights sum to <= 1e-8
 //             (or to NaN)
 //   separable (kernel sizes >= 7) the fused pass without smoothing, then a horizontal and a vertical 1-d bilateral pass;
-//             their centre test is the range test WITHOUT the finite test, and the valid mask is that of the first pass
+//             their centre test is the range test WITHOUT the finite test, and the valid mask is that of the first pass.
+//             A rejected pixel carries 0 into both 1-d passes; with min <= 0 that 0 is in range there, is smoothed like any
+//             other pixel and is a tap of its neighbours (as in the reference), but the image that leaves the last pass holds
+//             0 wherever the valid mask does: "rejected pixels are 0" holds for every kernel size
 constexpr int kTileW = 64, kTileH = 16, kFilterThreads = 256, kRowsPerLane = kTileH / (kFilterThreads / kTileW);
 constexpr int kMaxFilterRadius = 15;
 
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(kFilterThreads) void filter_depth_kernel(FilterArgs
         a.out[o] = dc;
         continue;
       }
-    } else if (out_of_range(dc, a.dmin, a.dmax)) {
+    } else if (out_of_range(dc, a.dmin, a.dmax) || (MODE == FILTER_COLS && !a.valid[o])) {
       a.out[o] = 0.0f;
       continue;
     }

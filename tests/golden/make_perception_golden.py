@@ -29,6 +29,15 @@ Excluded sets (the ONLY pixels a test may skip), computed from the inputs and th
   mask     pixels whose recorded reference distance max_s(r_s - |p - c_s|) is within 1e-5 m of -distance_threshold.
            Asserted <= 0.1 % of every case.
 Output: tests/golden/perception_golden.npz.
+
+edges      a second file, tests/golden/perception_edges_golden.npz (``edge_cases``), by the same code at the shapes where the HIP
+           kernels change how they index.  Filter: widths 64, 65 and 130 x heights 15 .. 20 (a tile is 64 x 16), kernel sizes 1
+           (accepted by the reference: radius 0) and 31 with a small and a large spatial sigma, minimum distance 0 with kernel
+           sizes 7 and 9 (the 0 a rejected pixel carries is in range in the two 1-d passes: the reference returns non-zero
+           depth at such pixels, printed below), a NaN and an out-of-range pixel on each side of x = 63 | 64.  Mask, through
+           ``reference_mask`` as it stands: 1 pixel, 1023 pixels, 2049 spheres (enabled at 0, 2047, 2048: each asserted to mask
+           pixels of its own), rays shared with pose and spheres per image and the reverse; no sphere at all, which the
+           reference refuses (its max over an empty dimension raises: the message is recorded with the inputs).  Same caps.
 """
 import os
 import sys
@@ -183,7 +192,7 @@ def render(H, W, K, eye, R, spheres, border=4):
     depth = np.where(np.isfinite(t_best), t_best, 0.0).reshape(H, W)
     label = label.reshape(H, W)
     label[depth == 0] = 0
-    for arr in (depth, label):
+    for arr in (depth, label) if border else ():
         arr[:border] = 0
         arr[-border:] = 0
         arr[:, :border] = 0
@@ -309,14 +318,169 @@ def pipeline_case(out, depth, label, K, cam_p, cam_q, spheres):
                 "pipe/survivors": survivors, "pipe/kept_fraction": np.float64(kept)})
 
 
+# ----------------------------------------------------------------------------------------------------- edge cases
+def edge_filter_image(rng, H, W, dmin, variant):
+    """any H >= 15, W >= 64: the features of filter_image moved onto the x = 63 / 64 (and 127 / 128) tile seams of the HIP
+    kernel and the y = 15 / 16 one, a NaN and an out-of-range pixel on each side of every seam in view; with dmin = 0 a near
+    surface (0.3 m: within a few sigma_depth of the zeros that rejected pixels carry) with rejected pixels inside"""
+    v, u = np.mgrid[0:H, 0:W]
+    d = 2.0 + 0.004 * u + 0.002 * v
+    d[3:11, 8:24] = 1.0                                   # 1 m step
+    d[2:H - 2, 58:70] -= 0.015                            # 1.5 cm step, across the seam
+    d[6:H, 61:64] = 1.3                                   # a near strip that ends ON the seam: flying pixels at x = 63 | 64
+    d[0:4, W - 9:W] = 0.8                                 # top / right border
+    d[H - 1, 20:30] = 0.6
+    if W > 128:
+        d[4:12, 120:128] = 1.2 + 0.012 * (u[4:12, 120:128] - 120)  # a ramp that ends on the second seam
+    if variant:
+        d = d * 1.1
+        d[12:H, 30:52] = 0.9 + 0.03
+    if dmin == 0.0:
+        d[4:14, 30:50] = 0.3 + 0.001 * (u[4:14, 30:50] - 30) + 0.0005 * (v[4:14, 30:50] - 4)
+    d = d + rng.normal(0.0, 0.001, d.shape)
+    below, above = dmin - 0.05, 12.0
+    for s in [63] + ([127] if W > 128 else []):           # (row, column): left of the seam, right of it
+        for (i, j, val) in [(1, s, np.nan), (1, s + 1, below), (8, s, above), (8, s + 1, np.nan), (12, s, np.inf), (13, s + 1, -np.inf),
+                            (H - 1, s, below), (H - 2, s + 1, 0.0 if dmin > 0 else below)]:
+            if j < W:
+                d[i, j] = val
+    for (i, j, val) in [(0, 0, np.nan), (H - 1, W - 1, below), (5, 12, np.nan), (0, W - 1, above), (9, 40, np.nan), (7, 36, below),
+                        (11, 45, np.inf)]:
+        d[i, j] = val
+    d[5:7, 33:35] = 0.0 if dmin > 0 else below            # a hole (an input of exactly 0 = dmin would lie in the excluded band)
+    if H > 16:
+        d[15:17, 10:14] = 11.0                            # beyond the maximum, across y = 15 | 16
+    return d.astype(np.float32)
+
+
+# name: H, W, B, min distance, flying_pixel_threshold, kernel size, sigma_spatial, sigma_depth
+EDGE_FILTER_CASES = [
+    ("w64_k5", 16, 64, 1, 0.1, 0.5, 5, 2.0, 0.05),
+    ("w65_k7", 17, 65, 2, 0.1, 0.5, 7, 2.0, 0.05),
+    ("w65_k3", 15, 65, 1, 0.1, 0.8, 3, 10.0, 0.1),
+    ("w130_k5", 18, 130, 1, 0.1, 0.5, 5, 10.0, 0.1),
+    ("w130_k9", 20, 130, 1, 0.1, None, 9, 2.0, 0.05),
+    ("w64_k31_small_sigma", 19, 64, 1, 0.1, 0.5, 31, 2.0, 0.05),
+    ("w130_k31_large_sigma", 17, 130, 1, 0.1, None, 31, 10.0, 0.1),
+    ("w65_k1", 16, 65, 1, 0.1, 0.5, 1, 2.0, 0.05),
+    ("w65_k7_min0", 18, 65, 2, 0.0, 0.5, 7, 2.0, 0.1),
+    ("w130_k9_min0_noflying", 16, 130, 1, 0.0, None, 9, 10.0, 0.05),
+]
+
+
+def edge_filter_cases(out):
+    rng = np.random.default_rng(2032)
+    names, params = [], []
+    for name, H, W, B, dmin, flying, ksize, ss, sd in EDGE_FILTER_CASES:
+        depth = np.stack([edge_filter_image(rng, H, W, dmin, b) for b in range(B)])
+        kw = dict(depth_minimum_distance=dmin, depth_maximum_distance=10.0, flying_pixel_threshold=flying, bilateral_kernel_size=ksize,
+                  bilateral_sigma_spatial=ss, bilateral_sigma_depth=sd)
+        fd = FilterDepth(image_shape=(H, W), device="cpu", num_batch=B, **kw)  # (kernel size 1 is accepted: radius 0, one launch)
+        filtered, valid = fd(torch.as_tensor(depth))
+        name = "filter_" + name
+        names.append(name)
+        params.append([dmin, 10.0, -1.0 if flying is None else flying, ksize, ss, sd, fd._enable_flying, fd._flying_tolerance,
+                       fd._enable_bilateral, fd._bilateral_radius, fd._sigma_spatial_sq2, fd._sigma_depth_sq2, float(fd._use_separable)])
+        band = filter_band(depth, dmin, 10.0, fd._enable_flying, fd._flying_tolerance)
+        assert band.mean() <= 0.005, (name, band.mean())
+        out[f"{name}/depth"], out[f"{name}/filtered"] = depth, filtered.numpy().copy()
+        out[f"{name}/valid"], out[f"{name}/excluded"] = valid.numpy().astype(np.uint8), band
+        v, f = valid.numpy(), filtered.numpy()
+        print(name, (B, H, W), "flying", flying, "kernel", ksize, "valid", int(v.sum()), "of", v.size, "band", int(band.sum()),
+              "changed", int((np.abs(f - depth)[v] > 1e-6).sum()), "rejected pixels the later passes left non-zero", int((f[~v] != 0).sum()),
+              "largest", float(np.abs(f[~v]).max()))
+    out["filter_case_names"] = np.array(names)
+    out["filter_case_params"] = np.array(params, np.float64)  # columns as in perception_golden.npz
+
+
+def edge_segmenter_cases(out, K, cam_p, cam_q, spheres, eyes, Rq):
+    """small images through reference_mask as it stands: 1 pixel, 1023 pixels, no sphere, 2049 spheres (three enabled: the first,
+    the last of the HIP kernel's first chunk of 2048 and the first of its second), and the two batched / shared combinations
+    perception_golden.npz lacks"""
+    def scaled(k, f):
+        k = k.astype(np.float64).copy()
+        k[:2] *= f
+        return k.astype(np.float32)
+
+    def shot(H, W, f, c, sph, border=2):
+        return render(H, W, scaled(K[c], f).astype(np.float64), eyes[c], Rq[c][0], sph, border)[0]
+
+    cases = {}
+    # one pixel whose ray goes through the centre of a robot sphere of camera 0's view, once at the robot, once 2 m behind it
+    c = Rq[0][0].T @ (spheres[0, 30, :3].astype(np.float64) - eyes[0])
+    k1 = np.array([[50.0, 0, -50.0 * c[0] / c[2]], [0, 50.0, -50.0 * c[1] / c[2]], [0, 0, 1]], np.float32)
+    hit = render(1, 1, k1.astype(np.float64), eyes[0], Rq[0][0], spheres[0], 0)[0]
+    cases["px1"] = (np.stack([hit, hit + 2.0]).astype(np.float32), k1[None], cam_p[[0]], cam_q[[0]], spheres[[0]])
+    cases["px1023"] = (shot(31, 33, 1.0 / 3.0, 0, spheres[0])[None], scaled(K[0], 1.0 / 3.0)[None], cam_p[[0]], cam_q[[0]], spheres[[0]])
+    cases["s0"] = (shot(24, 32, 1.0 / 3.0, 0, spheres[0])[None], scaled(K[0], 1.0 / 3.0)[None], cam_p[[0]], cam_q[[0]],
+                   np.zeros((1, 0, 4), np.float32))
+    many = np.zeros((1, 2049, 4), np.float32)
+    many[..., :3] = np.random.default_rng(7).uniform([-0.2, -0.5, 0.0], [0.7, 0.5, 0.6], (1, 2049, 3))  # where enabled ones WOULD mask
+    many[..., 3] = -100.0
+    alone = {0: [0.45, -0.1, 0.02, 0.1], 2047: [0.3, 0.3, 0.02, 0.1], 2048: [-0.1, -0.3, 0.02, 0.1]}
+    for k, s in alone.items():
+        many[0, k] = s
+    cases["s2049"] = (shot(24, 32, 1.0 / 3.0, 0, many[0])[None], scaled(K[0], 1.0 / 3.0)[None], cam_p[[0]], cam_q[[0]], many)
+    half = np.stack([scaled(K[0], 0.5), scaled(K[1], 0.5)])
+    # rays shared, pose and spheres per image: image c is pose c looking at configuration c through camera 0's intrinsics
+    d = np.stack([render(36, 48, half[0].astype(np.float64), eyes[c], Rq[c][0], spheres[c], 2)[0] for c in (0, 1)])
+    cases["rays_shared"] = (d, half[[0]], cam_p, cam_q, spheres)
+    # rays per image, pose and spheres shared: pose 0 and configuration 0 through both cameras' intrinsics
+    d = np.stack([render(36, 48, half[c].astype(np.float64), eyes[0], Rq[0][0], spheres[0], 2)[0] for c in (0, 1)])
+    cases["rays_each"] = (d, half, cam_p[[0]], cam_q[[0]], spheres[[0]])
+    names = []
+    for name, (depth, k, p, q, sph) in cases.items():
+        key = f"seg_{name}"
+        out.update({f"{key}/depth": depth, f"{key}/intrinsics": k, f"{key}/cam_position": p, f"{key}/cam_quaternion": q, f"{key}/spheres": sph})
+        names.append(key)
+        if sph.shape[1] == 0:  # the reference's max over the spheres refuses an empty set: recorded as that, with the inputs
+            try:
+                reference_mask(depth, k, 1.0, p, q, sph, torch.float32)
+            except IndexError as ex:
+                out[f"{key}/reference_raises"] = np.array(f"{type(ex).__name__}: {ex}")
+                out[f"{key}/rays"] = get_projection_rays(depth.shape[1], depth.shape[2], torch.as_tensor(k), 1.0).numpy()
+                print(key, "the reference raises", out[f"{key}/reference_raises"])
+                continue
+            raise AssertionError("the reference accepts an empty sphere set: record its output")
+        for mode, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+            r = reference_mask(depth, k, 1.0, p, q, sph, dt)
+            for k2 in ("mask", "filtered", "distance", "excluded"):
+                out[f"{key}/{mode}/{k2}"] = r[k2]
+            out[f"{key}/rays"] = r["rays"]
+            print(key, mode, depth.shape, "spheres", sph.shape, "masked", int(r["mask"].sum()), "of", int((depth > 0).sum()), "with depth, band",
+                  int(r["excluded"].sum()))
+            if name == "s2049":  # every enabled sphere masks pixels no other sphere does
+                for k3 in alone:
+                    less = sph.copy()
+                    less[0, k3, 3] = -100.0
+                    lost = int((reference_mask(depth, k, 1.0, p, q, less, dt)["mask"] != r["mask"]).sum())
+                    print("   without sphere", k3, "the mask loses", lost, "pixels")
+                    assert lost >= 3
+    assert out["seg_px1/fp32/mask"].reshape(-1).tolist() == [1, 0]
+    out["seg_case_names"] = np.array(names)
+    out["seg/distance_threshold"] = np.float32(THRESHOLD)
+
+
+def edge_cases(K, cam_p, cam_q, spheres, eyes, Rq):
+    """tests/golden/perception_edges_golden.npz: the shapes at which the HIP kernels change how they index"""
+    out = {}
+    edge_filter_cases(out)
+    edge_segmenter_cases(out, K, cam_p, cam_q, spheres, eyes, Rq)
+    path = os.path.join(HERE, "perception_edges_golden.npz")
+    np.savez_compressed(path, **out)
+    print(path, os.path.getsize(path))
+    assert os.path.getsize(path) < 1 << 20
+
+
 def main():
     out = {}
     filter_cases(out)
-    depth, label, K, cam_p, cam_q, spheres, _, _ = segmenter_cases(out)
+    depth, label, K, cam_p, cam_q, spheres, eyes, Rq = segmenter_cases(out)
     pipeline_case(out, depth, label, K, cam_p, cam_q, spheres)
     path = os.path.join(HERE, "perception_golden.npz")
     np.savez_compressed(path, **out)
     print(path, os.path.getsize(path))
+    edge_cases(K, cam_p, cam_q, spheres, eyes, Rq)
 
 
 if __name__ == "__main__":

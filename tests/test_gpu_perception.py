@@ -4,7 +4,9 @@ scenes built from scratch.
 
 Tolerances: filtered depth relative 1e-5 on pixels valid in both (the project's tolerance for fp32 kernels); valid mask and
 robot mask identical except on the pixel sets the golden script stored (decisive comparison within 1e-6 m / 1e-5 m of its
-threshold, computed there from the reference's values alone)."""
+threshold, computed there from the reference's values alone).  The same holds on perception_edges_golden.npz: images wider
+than one 64 x 16 tile of the filter, kernel sizes 1 and 31, minimum distance 0, and for the mask 1 and 1023 pixels, no sphere,
+more spheres than one pass holds and the batched / shared combinations the first file lacks."""
 
 import os
 
@@ -19,6 +21,9 @@ pytestmark = pytest.mark.gpu
 G = np.load(os.path.join(GOLDEN_DIR, "perception_golden.npz"))
 FILTER_CASES = [str(n) for n in G["filter_case_names"]]
 SEG_CASES = [str(n) for n in G["seg_case_names"]]
+E = np.load(os.path.join(GOLDEN_DIR, "perception_edges_golden.npz"))
+EDGE_FILTER_CASES = [str(n) for n in E["filter_case_names"]]
+EDGE_SEG_CASES = [str(n) for n in E["seg_case_names"]]
 
 
 def _filter_from_params(prm, shape, B, device):
@@ -28,17 +33,16 @@ def _filter_from_params(prm, shape, B, device):
     return FilterDepth(shape, dmin, dmax, None if fly < 0 else fly, None if ksize == 0 else int(ksize), ss, sd, device=str(device), num_batch=B)
 
 
-@pytest.mark.parametrize("name", FILTER_CASES)
-def test_filter_depth_matches_reference(name, device):
-    prm = G["filter_case_params"][FILTER_CASES.index(name)]
-    depth = G[f"{name}/depth"]
+def _check_filter(g, cases, name, device):
+    prm = g["filter_case_params"][cases.index(name)]
+    depth = g[f"{name}/depth"]
     B, H, W = depth.shape
     fd = _filter_from_params(prm, (H, W), B, device)
     filtered, valid = fd(torch.as_tensor(depth, device=device))
     torch.cuda.synchronize()
     assert valid.dtype == torch.bool and filtered.data_ptr() == fd._depth_out.data_ptr()
     filtered, valid = filtered.cpu().numpy(), valid.cpu().numpy()
-    ref_f, ref_v, excluded = G[f"{name}/filtered"], G[f"{name}/valid"].astype(bool), G[f"{name}/excluded"]
+    ref_f, ref_v, excluded = g[f"{name}/filtered"], g[f"{name}/valid"].astype(bool), g[f"{name}/excluded"]
     both = valid & ref_v
     rel = np.abs(filtered[both] - ref_f[both]) / np.abs(ref_f[both])
     print(f"{name}: valid {int(valid.sum())} ref {int(ref_v.sum())} mask mismatches outside the excluded set "
@@ -51,6 +55,19 @@ def test_filter_depth_matches_reference(name, device):
     f1, v1 = fd(torch.as_tensor(depth[:1], device=device), out, msk)
     assert f1.data_ptr() == out.data_ptr()
     assert np.array_equal(f1.cpu().numpy()[0], filtered[0]) and np.array_equal(v1.cpu().numpy()[0], valid[0])
+
+
+@pytest.mark.parametrize("name", FILTER_CASES)
+def test_filter_depth_matches_reference(name, device):
+    _check_filter(G, FILTER_CASES, name, device)
+
+
+@pytest.mark.parametrize("name", EDGE_FILTER_CASES)
+def test_filter_depth_matches_reference_at_the_edges(name, device):
+    """widths 64, 65 and 130 (the x halo reads the neighbouring tile), kernel sizes 1 and 31 (the halo is wider than a tile is
+    high), and minimum distance 0 with a separable size: the 0 of a rejected pixel is in range in the two 1-d passes, which
+    smooth it like any pixel (the reference returns up to 1.9 cm there, valid 0); the launch returns 0 where valid is 0"""
+    _check_filter(E, EDGE_FILTER_CASES, name, device)
 
 
 class _FixedSpheres:
@@ -105,6 +122,35 @@ def test_robot_mask_matches_reference(name, mode, graph, device):
         assert np.array_equal(mask[~excluded], ref_m[~excluded])
         assert np.array_equal(filtered[~excluded], ref_f[~excluded])
         assert not mask[obs.depth_image.cpu().numpy() == 0].any()
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16"])
+@pytest.mark.parametrize("name", EDGE_SEG_CASES)
+def test_robot_mask_matches_reference_at_the_edges(name, mode, device):
+    """the launch itself on the recorded rays: 1 and 1023 pixels (less than the 1024 of a workgroup), 2049 spheres with enabled
+    ones at 0, 2047 and 2048 (the second pass over the sphere table), rays shared with poses and spheres per image and the
+    reverse.  No sphere at all: the reference raises (recorded); the launch masks nothing."""
+    from curobo_amd.backends import perception as P
+
+    t = lambda k: torch.as_tensor(E[f"{name}/{k}"], device=device)  # noqa: E731
+    depth = t("depth")
+    m, o = torch.full(depth.shape, 7, dtype=torch.uint8, device=device), torch.full_like(depth, -7.0)
+    P.robot_mask(m, o, depth, t("rays"), t("cam_position"), t("cam_quaternion"), t("spheres"), float(E["seg/distance_threshold"]),
+                 P.MASK_FP32 if mode == "fp32" else P.MASK_BF16_OPS)
+    torch.cuda.synchronize()
+    assert set(np.unique(m.cpu().numpy())) <= {0, 1}
+    mask, filtered = m.cpu().numpy().astype(bool), o.cpu().numpy()
+    if f"{name}/reference_raises" in E:
+        assert E[f"{name}/spheres"].shape[1] == 0
+        assert not mask.any() and np.array_equal(filtered, E[f"{name}/depth"])
+        return
+    key = f"{name}/{mode}"
+    ref_m, ref_f, excluded = E[f"{key}/mask"].astype(bool), E[f"{key}/filtered"], E[f"{key}/excluded"]
+    print(f"{key}: masked {int(mask.sum())} ref {int(ref_m.sum())} mismatches outside the excluded set "
+          f"{int((mask != ref_m)[~excluded].sum())} (excluded {int(excluded.sum())})")
+    assert np.array_equal(mask[~excluded], ref_m[~excluded])
+    assert np.array_equal(filtered[~excluded], ref_f[~excluded])
+    assert not mask[E[f"{name}/depth"] == 0].any()
 
 
 def test_disabled_sphere_masks_nothing_and_enabled_it_would(device):
