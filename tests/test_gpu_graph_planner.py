@@ -1,4 +1,5 @@
-"""PRM graph planner on the GPU: the fused steering launch against the materialised reference path, the k-NN launch
+"""PRM graph planner on the GPU: the fused steering launch against the materialised reference path and against the float64 oracle
+(oracle/graph_ref.py, batches of tests/graph_cases.py, conditions held on the CPU by tests/test_oracle_graph.py), the k-NN launch
 against fp64 NumPy, a narrow-passage query and the MotionPlanner wiring."""
 
 import numpy as np
@@ -24,11 +25,9 @@ def _checker(device, robot, world):
     elif world == "primitives":
         from curobo_amd.scene.config import scene_from_config
 
-        scene = scene_from_config({"cuboid": {"table": {"dims": [2.0, 2.0, 0.2], "pose": [0.0, 0.0, -0.1, 1, 0, 0, 0]}},
-                                   "sphere": {"ball": {"radius": 0.2, "pose": [0.45, 0.3, 0.5, 1, 0, 0, 0]}},
-                                   "capsule": {"rod": {"radius": 0.08, "base": [0, 0, -0.3], "tip": [0, 0, 0.3],
-                                                       "pose": [-0.3, -0.45, 0.6, 0.9238795, 0.3826834, 0, 0]}},
-                                   "cylinder": {"post": {"radius": 0.1, "height": 0.8, "pose": [0.1, -0.6, 0.4, 1, 0, 0, 0]}}}, device)
+        from graph_cases import PRIMITIVE_WORLD
+
+        scene = scene_from_config(PRIMITIVE_WORLD, device)
         assert scene.struct.cuboid_has_primitives
     else:
         scene = None
@@ -100,6 +99,147 @@ def test_knn_matches_fp64_numpy(device, D):
     out = torch.empty(Q, 4, dtype=torch.int32, device=device)
     graph_hip.graph_knn(out, tq, tn, tw, 1000, D, 4)
     np.testing.assert_array_equal(out.cpu().numpy(), np.argsort(dist[:, :1000], axis=1, kind="stable")[:, :4])
+
+
+# ---------------------------------------------------------------------------------------------- against the float64 oracle
+_CHECKERS = {}
+
+
+def _oracle_checker(device, robot, scene):
+    import graph_cases as gc
+
+    if (robot, scene) not in _CHECKERS:
+        _CHECKERS[(robot, scene)] = gc.build_checker(device, robot, scene)
+    return _CHECKERS[(robot, scene)]
+
+
+def _oracle_pairs():
+    import graph_cases as gc
+
+    return gc.oracle_pairs()
+
+
+@pytest.mark.parametrize("robot,scene", _oracle_pairs(), ids=lambda v: str(v))
+def test_steering_matches_the_oracle(device, robot, scene):
+    """max_steps exact; out_index equal to the oracle's on every edge its band decides and inside the band's span on the others
+    (at most 5 % of the batch, asserted again here); out_node the fp32 point formula at the returned index.  The cases lie on both
+    sides of the launch's 60 KiB LDS branch: dual_ur10e with the 64-slot scene needs 62 400 bytes, every other pair less
+    (tests/test_oracle_graph.py::test_cases_lie_on_both_sides_of_the_60_kib_launch_path; of the packaged robots none comes nearer,
+    unitree_g1 does not fit the fused launch at all and is left out by ``GraphFeasibility.uses_fused``)."""
+    import graph_cases as gc
+    from curobo_amd.graph_planner.prm import GraphFeasibility
+
+    checker = _oracle_checker(device, robot, scene)
+    case = gc.oracle_case(robot, scene)
+    assert GraphFeasibility(checker, case["threshold"], torch.as_tensor(case["weight"], device=device), 2000).uses_fused()
+    lds = [gc.fused_lds_bytes(*p) for p in gc.oracle_pairs()]
+    assert min(lds) < 60 * 1024 < max(lds)
+    ref = gc.steering_reference(case)
+    node, idx, ms = gc.run_steer(checker, case)
+    share = gc.check_steer(ref, node, idx, ms)
+    print(f"{robot} / {scene}: max_steps {ms}, undecided {100 * share:.2f} %, LDS {gc.fused_lds_bytes(robot, scene)} bytes")
+    # the planner's entry point gives the same answer
+    feas = GraphFeasibility(checker, case["threshold"], torch.as_tensor(case["weight"], device=device), 2000)
+    node2, idx2 = feas.steer(torch.as_tensor(case["start"], device=device), torch.as_tensor(case["target"], device=device))
+    np.testing.assert_array_equal(idx2.cpu().numpy(), idx)
+    np.testing.assert_array_equal(node2.cpu().numpy().view(np.int32), node.view(np.int32))
+
+
+@pytest.mark.parametrize("n_pts", [16, 17, 40])
+def test_steering_placed_crossings(device, n_pts):
+    """one joint crosses a limit with the first violating step k* placed at 0, 1, 15, 16, 17, 31, 32 and max_steps (those that the
+    point count admits): index max(k* - 1, 0), as literals"""
+    import graph_cases as gc
+
+    literal = {16: [15] + 8 * [0] + 4 * [14], 17: [16] + 8 * [0] + 4 * [14] + 4 * [15],
+               40: [39] + 8 * [0] + 4 * [14] + 4 * [15] + 4 * [16] + 4 * [30] + 4 * [31] + 4 * [38]}[n_pts]
+    case = gc.placed_crossings(n_pts)
+    ref = gc.steering_reference(case)
+    assert ref["band"]["decided"].all() and ref["band"]["index"].tolist() == literal
+    node, idx, ms = gc.run_steer(_oracle_checker(device, "franka", "none"), case)
+    assert ms == n_pts - 1
+    assert idx.tolist() == literal, (case["kstar"].tolist(), idx.tolist())
+    gc.check_steer(ref, node, idx, ms)
+
+
+def test_steering_zero_length_batch(device):
+    import graph_cases as gc
+    from oracle.graph_ref import FEASIBLE
+
+    case = gc.zero_length_batch()
+    ref = gc.steering_reference(case)
+    node, idx, ms = gc.run_steer(_oracle_checker(device, "franka", "c2"), case)
+    assert ms == 1
+    gc.check_steer(ref, node, idx, ms)
+    dec = ref["band"]["decided"]
+    np.testing.assert_array_equal(idx[dec], np.where(ref["band"]["state"][dec, 0] == FEASIBLE, 1, 0))
+    assert set(idx.tolist()) == {0, 1}
+    np.testing.assert_array_equal(node[:, :7], case["start"])  # (t == s: every point is the start, bit for bit)
+
+
+def test_steering_beyond_the_grid(device):
+    """2048 + 37 edges: the first 37 workgroups walk a second edge, carrying ``first_bad`` and the barrier handshake over"""
+    import graph_cases as gc
+
+    case = gc.beyond_the_grid()
+    ref = gc.steering_reference(case)
+    node, idx, ms = gc.run_steer(_oracle_checker(device, "franka", "c2"), case)
+    gc.check_steer(ref, node, idx, ms)
+    dec, want = ref["band"]["decided"], ref["band"]["index"]
+    for part in (slice(0, gc.GRID_CAP), slice(gc.GRID_CAP, None)):
+        assert (want[part][dec[part]] == 0).any() and (want[part][dec[part]] == ms).any() and ((want[part][dec[part]] > 0) & (want[part][dec[part]] < ms)).any()
+
+
+@pytest.mark.parametrize("pad", [1, 3])
+def test_steering_row_stride(device, pad):
+    """rows of ld = D + 1 and D + 3 floats with NaN in the padding: bit-identical to contiguous rows, edge and point mode"""
+    import graph_cases as gc
+
+    case = gc.row_stride_case()
+    checker = _oracle_checker(device, "franka", "c2")
+    node, idx, ms = gc.run_steer(checker, case)
+    gc.check_steer(gc.steering_reference(case), node, idx, ms)
+    D = case["weight"].shape[0]
+    node_p, idx_p, ms_p = gc.run_steer(checker, case, ld=D + pad)
+    assert ms_p == ms
+    np.testing.assert_array_equal(idx_p, idx)
+    np.testing.assert_array_equal(node_p.view(np.int32), node.view(np.int32))
+    np.testing.assert_array_equal(gc.run_points(checker, case["start"], ld=D + pad), gc.run_points(checker, case["start"]))
+
+
+@pytest.mark.parametrize("n", [1, 15, 16, 17, 1000, 32768 + 5])
+def test_point_feasibility_matches_the_oracle(device, n):
+    """16 configurations per workgroup: partly filled workgroups, and 32768 + 5 points for a second pass of the 2048 workgroups"""
+    import graph_cases as gc
+    from curobo_amd.graph_planner.prm import GraphFeasibility
+
+    assert n in gc.POINT_SIZES
+    c = gc.point_batch(n)
+    checker = _oracle_checker(device, c["robot"], c["scene"])
+    flags = gc.run_points(checker, c["q"])
+    share = gc.check_points(gc.points_reference(n), flags)
+    print(f"points {n}: undecided {100 * share:.3f} %")
+    feas = GraphFeasibility(checker, gc.THRESHOLD, torch.ones(7, device=device), 2000)
+    np.testing.assert_array_equal(feas.feasible(torch.as_tensor(c["q"], device=device)).cpu().numpy(), flags.astype(bool))
+
+
+def _knn_ids():
+    import graph_cases as gc
+
+    return gc.knn_ids()
+
+
+@pytest.mark.parametrize("name", _knn_ids())
+def test_knn_edges(device, name):
+    """1 / 63 / 64 / 65 nodes, k = 64 and k == n_nodes, 1 / 5 / 255 queries, 1 / 7 / 12 joints, queries as rows of the node buffer
+    (ld_q = D + 1) past the searched prefix, exact grid values with plentiful ties: equal to the stable float64 reference"""
+    import graph_cases as gc
+
+    c = gc.knn_set(name)
+    got = gc.run_knn(device, c)
+    gc.check_knn(c, got)
+    if name == "identical":
+        np.testing.assert_array_equal(got, np.tile(np.arange(64, dtype=np.int32), (got.shape[0], 1)))
 
 
 WALL = {"table": {"dims": [2.0, 2.0, 0.2], "pose": [0.0, 0.0, -0.1, 1, 0, 0, 0]},
