@@ -71,3 +71,79 @@ def robot_mask(mask_out: torch.Tensor, depth_out: torch.Tensor, depth: torch.Ten
         ptr(mask_out), ptr(depth_out), ptr(depth), ptr(projection_rays), ptr(pos), ptr(quat), ptr(robot_spheres), B, H, W,
         int(robot_spheres.shape[1]), int(projection_rays.shape[0]), int(pos.shape[0]), int(robot_spheres.shape[0]),
         float(distance_threshold), int(mode), current_stream(depth)))
+
+
+# ---------------------------------------------------------------------------------------------------- pose refinement
+import ctypes as _C  # noqa: E402
+
+POSE_LM_INIT, POSE_LM_UPDATE = 0, 1  # ``mode`` of ``curobo_hip_pose_lm_step``
+POSE_WS_ROW = 32                     # CUROBO_HIP_POSE_WS_ROW
+
+
+class PoseLMState(_C.Structure):
+    """``curobo_hip_pose_lm_state``: used for its field offsets; the state itself is a device tensor of 4-byte words"""
+
+    _fields_ = [("best_position", _C.c_float * 3), ("best_quaternion", _C.c_float * 4), ("best_error", _C.c_float),
+                ("best_sum_sq", _C.c_float), ("best_n_valid", _C.c_int32), ("lambda_damping", _C.c_float),
+                ("best_JtJ", _C.c_float * 36), ("best_Jtr", _C.c_float * 6), ("cand_position", _C.c_float * 3),
+                ("cand_quaternion", _C.c_float * 4), ("pred_reduction", _C.c_float), ("delta", _C.c_float * 6),
+                ("cand_sum_sq", _C.c_float), ("cand_n_valid", _C.c_int32), ("trust_ratio", _C.c_float), ("accepted", _C.c_int32)]
+
+
+POSE_STATE_WORDS = _C.sizeof(PoseLMState) // 4
+#: int32 fields of the state (every other word is a float)
+POSE_STATE_INT_FIELDS = ("best_n_valid", "cand_n_valid", "accepted")
+
+
+def pose_state_slice(name: str) -> slice:
+    """the words of field ``name`` in a state tensor"""
+    f = getattr(PoseLMState, name)
+    return slice(f.offset // 4, (f.offset + f.size) // 4)
+
+
+def pose_sdf_ws_bytes(n_points: int) -> int:
+    """``curobo_hip_pose_sdf_ws_bytes``"""
+    nbytes = _C.c_int64(0)
+    check(load().curobo_hip_pose_sdf_ws_bytes(int(n_points), _C.cast(_C.pointer(nbytes), _C.c_void_p)))
+    return int(nbytes.value)
+
+
+def pose_sdf_evaluate(workspace: torch.Tensor, points: torch.Tensor, position: torch.Tensor, quaternion: torch.Tensor, mesh_struct,
+                      max_distance: float, distance_threshold: float, use_huber: bool, huber_delta: float,
+                      out_distance: Optional[torch.Tensor] = None, out_gradient: Optional[torch.Tensor] = None,
+                      out_valid: Optional[torch.Tensor] = None) -> None:
+    """``curobo_hip_pose_sdf_evaluate``: points [N, 3] (world frame) against the mesh ``mesh_struct`` (``backends.mesh.Mesh``) at
+    the pose ``position`` [3] / ``quaternion`` [4] wxyz on the device -> one row of partial sums per workgroup in ``workspace``
+    (uint8 or 4-byte words), and optionally the per-point distance [N], world gradient [N, 3] and valid [N] int32."""
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"pose_sdf_evaluate: points must be (N, 3), got {tuple(points.shape)}")
+    _require(points, "points", torch.float32)
+    _require(position, "position", torch.float32, points)
+    _require(quaternion, "quaternion", torch.float32, points)
+    if position.numel() != 3 or quaternion.numel() != 4:
+        raise ValueError("pose_sdf_evaluate: position must hold 3 and quaternion 4 values")
+    n = int(points.shape[0])
+    for name, t, dt, shape in (("out_distance", out_distance, torch.float32, (n,)), ("out_gradient", out_gradient, torch.float32, (n, 3)),
+                               ("out_valid", out_valid, torch.int32, (n,))):
+        _require(t, name, dt, points)
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"pose_sdf_evaluate: {name} must have shape {shape}, got {tuple(t.shape)}")
+    if not workspace.is_contiguous() or workspace.device != points.device:
+        raise ValueError("pose_sdf_evaluate: workspace must be a contiguous tensor on the points' device")
+    check(load().curobo_hip_pose_sdf_evaluate(
+        ptr(out_distance), ptr(out_gradient), ptr(out_valid), ptr(workspace), int(workspace.numel() * workspace.element_size()),
+        ptr(points), ptr(position), ptr(quaternion), _C.addressof(mesh_struct), float(max_distance), float(distance_threshold),
+        int(bool(use_huber)), float(huber_delta), n, current_stream(points)))
+
+
+def pose_lm_step(state: torch.Tensor, workspace: torch.Tensor, n_points: int, mode: int, lambda_initial: float, lambda_factor: float,
+                 lambda_min: float, lambda_max: float, rho_min: float, minimum_valid_count: int = 10) -> None:
+    """``curobo_hip_pose_lm_step`` on ``state`` (float32 [POSE_STATE_WORDS], the layout of ``PoseLMState``)"""
+    _require(state, "state", torch.float32)
+    if state.numel() != POSE_STATE_WORDS:
+        raise ValueError(f"pose_lm_step: state must hold {POSE_STATE_WORDS} words, got {state.numel()}")
+    if not workspace.is_contiguous() or workspace.device != state.device:
+        raise ValueError("pose_lm_step: workspace must be a contiguous tensor on the state's device")
+    check(load().curobo_hip_pose_lm_step(
+        ptr(state), ptr(workspace), int(workspace.numel() * workspace.element_size()), int(n_points), int(mode), float(lambda_initial),
+        float(lambda_factor), float(lambda_min), float(lambda_max), float(rho_min), int(minimum_valid_count), current_stream(state)))

@@ -36,6 +36,7 @@ SOURCES = [
     "cost.hip", "rollout_fused.hip", "rollout_ik_fused.hip", "dynamics.hip", "linalg.hip", "mppi.hip", "seed_ik.hip", "mesh_bake.hip", "mesh_bvh.hip",
     "graph_planner.hip",
     "perception.hip",
+    "pose_detect.hip",
 ]
 
 

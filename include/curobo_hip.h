@@ -932,6 +932,70 @@ int curobo_hip_robot_mask(uint8_t *mask_out, float *depth_out, const float *dept
                           int batch, int height, int width, int num_spheres, int ray_batch, int pose_batch,
                           int sphere_batch, float distance_threshold, int bf16_ops, curobo_hip_stream_t stream);
 
+/* ---- mesh-SDF pose refinement (curobo_amd/perception/pose_estimation; reference SDFPoseDetector:
+ * perception/pose_estimation/sdf_pose_detector.py).  One Levenberg-Marquardt iteration is two launches: an evaluation
+ * of the observed points at the candidate pose, then one step.  Nothing accumulates with atomics: results are
+ * bit-identical from run to run.
+ *
+ * The evaluation's workspace: one row of CUROBO_HIP_POSE_WS_ROW 4-byte words per workgroup of 256 points -- words 0..20 the
+ * upper triangle of J^T J (row major), 21..26 J^T r, 27 sum r^2 (floats), 28 the valid count (int32), the rest 0.  Every row is
+ * written by every evaluation: nothing needs zeroing in between. */
+#define CUROBO_HIP_POSE_WS_ROW 32
+int curobo_hip_pose_sdf_ws_bytes(int n_points, int64_t *out_bytes);
+
+/* mesh_surface_distance_query_kernel (wp_mesh_sdf_alignment.py:84-146) and the per-thread part of jacobian_reduce_kernel
+ * (:176-222) for points [n_points, 3] in the world frame against ONE mesh at the pose position [3] / quaternion [4] wxyz
+ * (DEVICE pointers: the step kernel writes them): p_mesh = R^T (p - t) (:121), the closest surface point within
+ * max_distance (:124-128; unsigned, no inside test), valid iff one was found and 1e-8 < distance <= distance_threshold
+ * (:135), gradient = R (closest - p_mesh) / distance (:137-140), the Huber scale sqrt(huber_delta / r) for r > huber_delta
+ * (:207-211, use_huber != 0), the Jacobian row [g, (g_z p_y - g_y p_z, g_x p_z - g_z p_x, g_y p_x - g_x p_y)] times that
+ * scale (:213-220).  out_distance [n_points], out_gradient [n_points, 3], out_valid [n_points] int32: optional (NULL skips
+ * one), 0 at invalid points.  The sums the reference adds with tile_atomic_add (:238-377) leave as one row per workgroup
+ * in `workspace` (see above), in a fixed order.  mesh: HOST pointer (the struct is copied into the launch).  A pose that is
+ * not finite finds nothing. */
+int curobo_hip_pose_sdf_evaluate(float *out_distance, float *out_gradient, int32_t *out_valid, void *workspace,
+                                 int64_t workspace_bytes, const float *points, const float *position,
+                                 const float *quaternion, const curobo_hip_mesh *mesh, float max_distance,
+                                 float distance_threshold, int use_huber, float huber_delta, int n_points,
+                                 curobo_hip_stream_t stream);
+
+/* The refinement state (SDFRefinementState, sdf_pose_detector.py:56-75, plus the candidate the next evaluation reads), on
+ * the DEVICE; 4-byte fields only. */
+typedef struct curobo_hip_pose_lm_state {
+  float best_position[3], best_quaternion[4]; /* wxyz */
+  float best_error, best_sum_sq;
+  int32_t best_n_valid;
+  float lambda_damping;
+  float best_JtJ[36], best_Jtr[6];
+  float cand_position[3], cand_quaternion[4]; /* what curobo_hip_pose_sdf_evaluate is to be called with next */
+  float pred_reduction;
+  float delta[6];       /* translation_change = delta[0..2], rotation_change = delta[3..5] */
+  float cand_sum_sq;    /* of the evaluation this step consumed */
+  int32_t cand_n_valid;
+  float trust_ratio;    /* of this step (0 in the initial mode) */
+  int32_t accepted;     /* of this step (1 in the initial mode) */
+} curobo_hip_pose_lm_state;
+
+#define CUROBO_HIP_POSE_LM_INIT 0
+#define CUROBO_HIP_POSE_LM_UPDATE 1
+/* Everything _refine_iteration (sdf_pose_detector.py:305-399) does outside its two Warp launches, by one lane.  The rows
+ * of `workspace` (the evaluation at state->cand_*) are added in workgroup order.  Then
+ *   mode CUROBO_HIP_POSE_LM_INIT   (_setup_refinement :266-302): the sums become the best state, best_error =
+ *        sqrt(sum r^2 / (n + 1e-8)), lambda_damping = lambda_initial;
+ *   mode CUROBO_HIP_POSE_LM_UPDATE (trust_region_update, optim_pose_lm.py:53-175): has_enough_valid = n >
+ *        minimum_valid_count (the reference's 10); trust ratio = (best_sum_sq - sum r^2) / (pred_reduction + 1e-8); the
+ *        step is accepted iff ratio >= 0 and has_enough_valid -- rho_min is carried and, as in the reference (:142), not
+ *        consulted; lambda is divided (accepted) or multiplied by lambda_factor and clamped to [lambda_min, lambda_max];
+ *        the best position, quaternion, error, sum r^2, count, J^T J and J^T r are the candidate's or stay.
+ * Both modes then produce the next candidate from the best state: delta from the fp32 Cholesky factorisation of
+ * J^T J + lambda I (solve_lm_step :180-202), pred_reduction = -delta . J^T r - 0.5 delta . J^T J delta (:28-48), and the pose
+ * Pose.from_euler_xyz(delta[3..5], delta[0..2]).multiply(best) (sdf_pose_detector.py:327-334), not renormalised.  A pivot
+ * that is not positive makes delta, the prediction and the candidate NaN: that candidate finds no point, is rejected by the
+ * next step, and lambda grows. */
+int curobo_hip_pose_lm_step(curobo_hip_pose_lm_state *state, const void *workspace, int64_t workspace_bytes, int n_points,
+                            int mode, float lambda_initial, float lambda_factor, float lambda_min, float lambda_max,
+                            float rho_min, int minimum_valid_count, curobo_hip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
