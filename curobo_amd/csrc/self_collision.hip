@@ -29,6 +29,100 @@ struct SelfCollArgs {
   int store_pair_distance, write_grad;
 };
 
+// ------------------------------------------------------------------------------------------
+// The rules every kernel of this file shares, stated once.  `A` is SelfCollArgs or SelfDenseArgs (same leading fields).
+
+// Staging: a sphere gets its padding added, and a row that the previous call flagged in sparse_index is zeroed in
+// out_gradient and its flag cleared (reference load_spheres_and_zero_gradients, self_collision_helper.cuh:151-192).
+// NAN_RADIUS (the bitmap kernels): a negative (disabled) radius becomes NaN, so every pair of the sphere compares false --
+// the list kernels leave that to pair_penetration.  stage_sphere does both for sphere k of the run that starts at flat index
+// flat0 = point * S (src = robot_spheres + flat0, hoisted by the caller; s = the sphere's index in the robot); kernels that
+// issue a wavefront's loads before the first use call the two steps on the loaded values.
+template <bool NAN_RADIUS>
+__device__ __forceinline__ float4 pad_radius(float4 v, float offset) {
+  v.w += offset;
+  if (NAN_RADIUS && !(v.w >= 0.0f)) v.w = __builtin_nanf("");
+  return v;
+}
+template <class A>
+__device__ __forceinline__ void clear_stale_row(const A &a, size_t flat, uint8_t stale) {
+  if (stale) {
+    reinterpret_cast<float4 *>(a.out_gradient)[flat] = make_float4(0.f, 0.f, 0.f, 0.f);
+    a.sparse_index[flat] = 0;
+  }
+}
+template <bool NAN_RADIUS, class A>
+__device__ __forceinline__ float4 stage_sphere(const A &a, const float4 *src, size_t flat0, int k, int s) {
+  const float4 v = pad_radius<NAN_RADIUS>(src[k], a.offsets[s]);
+  clear_stale_row(a, flat0 + k, a.sparse_index[flat0 + k]);
+  return v;
+}
+
+// Arg-max over a wavefront: the largest penetration, then the lowest key among the lanes that attain it (key = index in
+// pair_locations or (i << 10) | j: both orders are the list's).  kNoKey when nothing penetrates.
+constexpr int kNoKey = 0x7fffffff;
+struct MaxKey { float m; int key; };
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
+  return v;
+}
+__device__ __forceinline__ int wave_min(int k) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) k = min(k, __shfl_xor(k, off, kWave));
+  return k;
+}
+__device__ __forceinline__ MaxKey wave_argmax(float v, int key) {
+  const float m = wave_max(v);
+  return {m, wave_min((m > 0.0f && v == m) ? key : kNoKey)};
+}
+// ... then over the NWAVES wavefronts of a workgroup through red[2 * NWAVES]: true on the one thread that holds the result
+template <int NWAVES>
+__device__ __forceinline__ bool block_argmax(MaxKey &r, float *red, int wave, int lane) {
+  if (lane == 0) {
+    red[wave * 2] = r.m;
+    reinterpret_cast<int *>(red)[wave * 2 + 1] = r.key;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return false;
+  r = {0.0f, kNoKey};
+  for (int w = 0; w < NWAVES; w++) {
+    const float mw = red[w * 2];
+    const int kw = reinterpret_cast<const int *>(red)[w * 2 + 1];
+    if (mw > r.m || (mw == r.m && kw < r.key)) r = {mw, kw};
+  }
+  return true;
+}
+
+// Finalize (one thread per point; reference finalize_collision_results, self_collision_helper.cuh:277-349): the cost of
+// the deepest pair of point n, its two gradient rows and their flags; m <= 0: nothing penetrates.  pair(i, j) names the
+// pair and is only asked when the rows are written.
+template <class A, class P>
+__device__ __forceinline__ void finalize_point(const A &a, int S, int n, const float4 *sph, float m, P pair) {
+  if (!(m > 0.0f)) {
+    a.out_distance[n] = 0.0f;
+    return;
+  }
+  const float w = a.weight[0];
+  a.out_distance[n] = 0.5f * w * m;
+  if (a.write_grad) {
+    int i, j;
+    pair(i, j);
+    const float4 s1 = sph[i], s2 = sph[j];
+    const float vx = w * (s2.x - s1.x), vy = w * (s2.y - s1.y), vz = w * (s2.z - s1.z);
+    float4 *g = reinterpret_cast<float4 *>(a.out_gradient) + (size_t)n * S;
+    g[i] = make_float4(vx, vy, vz, w * -1.0f);
+    g[j] = make_float4(-1.0f * vx, -1.0f * vy, -1.0f * vz, w * -1.0f);
+    a.sparse_index[(size_t)n * S + i] = 1;
+    a.sparse_index[(size_t)n * S + j] = 1;
+  }
+}
+// the bitmap kernels' key (i << 10) | j
+template <class A>
+__device__ __forceinline__ void finalize_point(const A &a, int S, int n, const float4 *sph, MaxKey r) {
+  finalize_point(a, S, n, sph, r.key == kNoKey ? 0.0f : r.m, [&](int &i, int &j) { i = r.key >> 10; j = r.key & 1023; });
+}
+
 // Scan pairs [k_begin, k_end) of the LDS-resident pair tile for the wave's point.  Four pairs per
 // lane are in flight per iteration (pair dwords first, then the 8 sphere reads) so the two
 // dependent LDS round trips overlap.  Consecutive lanes take consecutive pairs: the list is
@@ -86,15 +180,7 @@ __global__ void __launch_bounds__(NWAVES * 64) self_collision_kernel(const SelfC
     //      (reference load_spheres_and_zero_gradients, self_collision_helper.cuh:151-192)
     if (valid_pt) {
       const float4 *src = reinterpret_cast<const float4 *>(a.robot_spheres) + (size_t)n * S;
-      for (int s = lane; s < S; s += kWave) {
-        float4 v = src[s];
-        v.w += a.offsets[s];
-        sph[s] = v;
-        if (a.sparse_index[(size_t)n * S + s]) {
-          reinterpret_cast<float4 *>(a.out_gradient)[(size_t)n * S + s] = make_float4(0.f, 0.f, 0.f, 0.f);
-          a.sparse_index[(size_t)n * S + s] = 0;
-        }
-      }
+      for (int s = lane; s < S; s += kWave) sph[s] = stage_sphere<false>(a, src, (size_t)n * S, s, s);
     }
     float best = 0.0f;
     int best_k = -1;
@@ -112,31 +198,19 @@ __global__ void __launch_bounds__(NWAVES * 64) self_collision_kernel(const SelfC
         if (valid_pt) scan_pairs<STORE>(s_pairs, sph, t0, cnt, lane, pair_out, best, best_k);
       }
     }
-    // wave64 butterfly arg-max on (value, pair index); ties -> lowest pair index
+    // wave64 butterfly arg-max on (value, pair index); ties -> lowest pair index: value and index travel
+    // together through argmax_merge (self_device.hpp), one pass where wave_argmax takes two
 #pragma unroll
     for (int off = kWave / 2; off > 0; off >>= 1) {
       const float ov = __shfl_xor(best, off, kWave);
       const int ok = __shfl_xor(best_k, off, kWave);
       argmax_merge(best, best_k, ov, ok);
     }
-    // ---- finalize (reference finalize_collision_results, self_collision_helper.cuh:277-349)
     if (valid_pt && lane == 0) {
-      if (best_k < 0 || best <= 0.0f) {
-        a.out_distance[n] = 0.0f;
-      } else {
-        const float w = a.weight[0];
-        a.out_distance[n] = 0.5f * w * best;
-        if (a.write_grad) {
-          const int i = a.pair_locations[2 * best_k], j = a.pair_locations[2 * best_k + 1];
-          const float4 s1 = sph[i], s2 = sph[j];
-          const float vx = w * (s2.x - s1.x), vy = w * (s2.y - s1.y), vz = w * (s2.z - s1.z);
-          float4 *g = reinterpret_cast<float4 *>(a.out_gradient) + (size_t)n * S;
-          g[i] = make_float4(vx, vy, vz, w * -1.0f);
-          g[j] = make_float4(-1.0f * vx, -1.0f * vy, -1.0f * vz, w * -1.0f);
-          a.sparse_index[(size_t)n * S + i] = 1;
-          a.sparse_index[(size_t)n * S + j] = 1;
-        }
-      }
+      finalize_point(a, S, n, sph, best_k < 0 ? 0.0f : best, [&](int &i, int &j) {
+        i = a.pair_locations[2 * best_k];
+        j = a.pair_locations[2 * best_k + 1];
+      });
     }
     // the sphere slot is rewritten by the next point: all lanes must be done reading it
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -159,17 +233,9 @@ __global__ void __launch_bounds__(256) self_collision_row16_kernel(const SelfCol
   const int pt0 = blockIdx.x * kPts;
   const int npts = min(kPts, a.n_points - pt0);
   {  // spheres (+ padding) of the workgroup's points; zero rows flagged by the previous call
-    const float4 *src = reinterpret_cast<const float4 *>(a.robot_spheres) + (size_t)pt0 * S;
     const size_t flat0 = (size_t)pt0 * S;
-    for (int i = tid; i < npts * S; i += 256) {
-      float4 v = src[i];
-      v.w += a.offsets[i % S];
-      sph_all[i] = v;
-      if (a.sparse_index[flat0 + i]) {
-        reinterpret_cast<float4 *>(a.out_gradient)[flat0 + i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        a.sparse_index[flat0 + i] = 0;
-      }
-    }
+    const float4 *src = reinterpret_cast<const float4 *>(a.robot_spheres) + flat0;
+    for (int i = tid; i < npts * S; i += 256) sph_all[i] = stage_sphere<false>(a, src, flat0, i, i % S);
     for (int k = tid; k < P; k += 256) s_pairs[k] = g_pairs[k];
   }
   __syncthreads();
@@ -177,7 +243,7 @@ __global__ void __launch_bounds__(256) self_collision_row16_kernel(const SelfCol
   const bool valid_pt = grp < npts;
   const float4 *sph = sph_all + (size_t)grp * S;
   float best = 0.0f;
-  int best_k = 0x7fffffff;
+  int best_k = kNoKey;
   if (valid_pt) {
     for (int k0 = lane; k0 < P; k0 += kLanes * U) {
       uint32_t ij[U];
@@ -202,27 +268,15 @@ __global__ void __launch_bounds__(256) self_collision_row16_kernel(const SelfCol
       }
     }
   }
-  // arg-max inside the 16-lane row: max value, then the lowest pair index that attains it
+  // the same arg-max as wave_argmax, inside the point's 16-lane row (DPP only)
   const float m = row16_max(best);
-  const int kmin = row16_min((best == m && best > 0.0f) ? best_k : 0x7fffffff);
+  const int kmin = row16_min((best == m && best > 0.0f) ? best_k : kNoKey);
   if (!valid_pt || lane != 0) return;
-  if (kmin == 0x7fffffff || m <= 0.0f) {
-    a.out_distance[n] = 0.0f;
-    return;
-  }
-  const float w = a.weight[0];
-  a.out_distance[n] = 0.5f * w * m;
-  if (a.write_grad) {
+  finalize_point(a, S, n, sph, kmin == kNoKey ? 0.0f : m, [&](int &i, int &j) {
     const uint32_t ij = s_pairs[kmin];
-    const int i = (int)(int16_t)(ij & 0xffffu), j = (int)(int16_t)(ij >> 16);
-    const float4 s1 = sph[i], s2 = sph[j];
-    const float vx = w * (s2.x - s1.x), vy = w * (s2.y - s1.y), vz = w * (s2.z - s1.z);
-    float4 *g = reinterpret_cast<float4 *>(a.out_gradient) + (size_t)n * S;
-    g[i] = make_float4(vx, vy, vz, w * -1.0f);
-    g[j] = make_float4(-1.0f * vx, -1.0f * vy, -1.0f * vz, w * -1.0f);
-    a.sparse_index[(size_t)n * S + i] = 1;
-    a.sparse_index[(size_t)n * S + j] = 1;
-  }
+    i = (int)(int16_t)(ij & 0xffffu);
+    j = (int)(int16_t)(ij >> 16);
+  });
 }
 
 
@@ -273,19 +327,8 @@ __global__ void __launch_bounds__(256) self_collision_dense_kernel(const SelfDen
   const float qnan = __builtin_nanf("");
   {  // spheres (+ padding) -> this wave's LDS slot; disabled / padding spheres carry a NaN radius (lose every max)
     const float4 *src = reinterpret_cast<const float4 *>(a.robot_spheres) + (size_t)n * S;
-    for (int s = lane; s < SL; s += kWave) {
-      float4 v = make_float4(0.f, 0.f, 0.f, qnan);
-      if (s < S) {
-        v = src[s];
-        v.w += a.offsets[s];
-        if (!(v.w >= 0.0f)) v.w = qnan;  // pair_penetration: pairs with a negative (padded) radius contribute 0
-        if (a.sparse_index[(size_t)n * S + s]) {
-          reinterpret_cast<float4 *>(a.out_gradient)[(size_t)n * S + s] = make_float4(0.f, 0.f, 0.f, 0.f);
-          a.sparse_index[(size_t)n * S + s] = 0;
-        }
-      }
-      sph[s] = v;
-    }
+    for (int s = lane; s < SL; s += kWave)
+      sph[s] = s < S ? stage_sphere<true>(a, src, (size_t)n * S, s, s) : make_float4(0.f, 0.f, 0.f, qnan);
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -338,10 +381,8 @@ __global__ void __launch_bounds__(256) self_collision_dense_kernel(const SelfDen
       if (gbest[t] > best) { best = gbest[t]; best_code = (g0 + t) * NB + gjb[t]; }  // strict: the lowest slot wins ties
   }
   // ---- arg-max over the wave; lanes that attain it look up the first j of their winning block
-  float m = best;
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
-  int key = 0x7fffffff;
+  const float m = wave_max(best);
+  int key = kNoKey;
   if (m > 0.0f && best == m) {
     const int slot = best_code / NB, jb = best_code - slot * NB;
     const float4 o = sph[slot * 64 + lane];
@@ -355,25 +396,8 @@ __global__ void __launch_bounds__(256) self_collision_dense_kernel(const SelfDen
     }
     if (bj >= 0) key = ((slot * 64 + lane) << 10) | bj;
   }
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) key = min(key, __shfl_xor(key, off, kWave));
-  if (lane != 0) return;
-  if (!(m > 0.0f) || key == 0x7fffffff) {
-    a.out_distance[n] = 0.0f;
-    return;
-  }
-  const float wgt = a.weight[0];
-  a.out_distance[n] = 0.5f * wgt * m;
-  if (a.write_grad) {
-    const int i = key >> 10, j = key & 1023;
-    const float4 s1 = sph[i], s2 = sph[j];
-    const float vx = wgt * (s2.x - s1.x), vy = wgt * (s2.y - s1.y), vz = wgt * (s2.z - s1.z);
-    float4 *g = reinterpret_cast<float4 *>(a.out_gradient) + (size_t)n * S;
-    g[i] = make_float4(vx, vy, vz, wgt * -1.0f);
-    g[j] = make_float4(-1.0f * vx, -1.0f * vy, -1.0f * vz, wgt * -1.0f);
-    a.sparse_index[(size_t)n * S + i] = 1;
-    a.sparse_index[(size_t)n * S + j] = 1;
-  }
+  key = wave_min(key);
+  if (lane == 0) finalize_point(a, S, n, sph, MaxKey{m, key});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -383,8 +407,7 @@ __global__ void __launch_bounds__(256) self_collision_dense_kernel(const SelfDen
 // it can penetrate, and only positive penetrations count (result preserving).  For a humanoid in a typical pose one
 // in seven of the tiles that hold enabled pairs survives (Unitree G1: 107 of 763; 32 x 32 tiles: 63 of 224 = twice
 // the pair tests).  `tiles` = the (ib | jb << 8) list of tiles with at least one enabled pair (built once per robot
-// next to the bitmap).  A wavefront owns a point; the surviving tiles are compacted and taken four at a time, one per
-// 16-lane row: lane (row, li) keeps sphere i = 16 ib + li in registers and streams the 16 spheres of block jb from LDS.
+// next to the bitmap).  The two kernels below share the staging, the boxes and this test; they differ in the narrow phase.
 constexpr int kTile = 16;
 struct SelfTilesArgs {
   SelfDenseArgs d;
@@ -396,122 +419,6 @@ struct SelfTilesArgs {
 __device__ __forceinline__ float pair_pen(float4 o, float4 sj) {
   const float dx = o.x - sj.x, dy = o.y - sj.y, dz = o.z - sj.z, rr = o.w + sj.w;
   return rr * rr - (dx * dx + dy * dy + dz * dz);
-}
-
-__global__ void __launch_bounds__(256) self_collision_tiles_kernel(const SelfTilesArgs t) {
-  const SelfDenseArgs &a = t.d;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int S = a.nspheres, NS = a.nslots, SL = NS * 64, NB = SL / kTile;
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  const size_t wave_floats = (size_t)SL * 4 + (size_t)NB * 8 + (size_t)((t.n_tiles + 3) & ~3);
-  float4 *sph = reinterpret_cast<float4 *>(smem + wave * wave_floats);
-  float *box = reinterpret_cast<float *>(sph + SL);       // [NB][8]: lo xyz, -, hi xyz, -
-  int *kept = reinterpret_cast<int *>(box + NB * 8);      // surviving tiles
-  const int n = blockIdx.x * (blockDim.x / kWave) + wave;
-  if (n >= a.n_points) return;  // waves are independent: only wave-level fences below
-  const float qnan = __builtin_nanf("");
-  const int row = lane >> 4, li = lane & 15;
-  {  // spheres (+ padding) -> LDS, stale gradient rows cleared (as the other kernels), block boxes on the way
-    const float4 *src = reinterpret_cast<const float4 *>(a.robot_spheres) + (size_t)n * S;
-    for (int sl = 0; sl < NS; sl++) {
-      const int s = sl * 64 + lane;
-      float4 v = make_float4(0.f, 0.f, 0.f, qnan);
-      if (s < S) {
-        v = src[s];
-        v.w += a.offsets[s];
-        if (!(v.w >= 0.0f)) v.w = qnan;
-        if (a.sparse_index[(size_t)n * S + s]) {
-          reinterpret_cast<float4 *>(a.out_gradient)[(size_t)n * S + s] = make_float4(0.f, 0.f, 0.f, 0.f);
-          a.sparse_index[(size_t)n * S + s] = 0;
-        }
-      }
-      sph[s] = v;
-      const bool on = v.w == v.w;  // disabled / padding spheres: an empty box
-      const float big = 3.0e38f;
-      const float lx = -row16_max(on ? v.w - v.x : -big), ly = -row16_max(on ? v.w - v.y : -big), lz = -row16_max(on ? v.w - v.z : -big);
-      const float hx = row16_max(on ? v.x + v.w : -big), hy = row16_max(on ? v.y + v.w : -big), hz = row16_max(on ? v.z + v.w : -big);
-      if (li == 0) {
-        float *b = box + (sl * 4 + row) * 8;
-        b[0] = lx; b[1] = ly; b[2] = lz; b[4] = hx; b[5] = hy; b[6] = hz;
-      }
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  // ---- broad phase: tiles whose block boxes overlap, compacted in list order
-  int count = 0;
-  for (int c0 = 0; c0 < t.n_tiles; c0 += kWave) {
-    const int c = c0 + lane;
-    bool keep = false;
-    int tl = 0;
-    if (c < t.n_tiles) {
-      tl = t.tiles[c];
-      const float *bi = box + (tl & 0xff) * 8, *bj = box + (tl >> 8) * 8;
-      keep = bi[0] <= bj[4] && bj[0] <= bi[4] && bi[1] <= bj[5] && bj[1] <= bi[5] && bi[2] <= bj[6] && bj[2] <= bi[6];
-    }
-    const unsigned long long m = __ballot(keep);
-    if (keep) kept[count + __popcll(m & ((1ull << lane) - 1ull))] = tl;
-    count += __popcll(m);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  // ---- narrow phase: four tiles per round, one per 16-lane row
-  float bv = 0.0f;
-  int bkey = 0x7fffffff;
-  for (int t0 = 0; t0 < count; t0 += 4) {
-    const bool has = t0 + row < count;
-    const int tl = kept[has ? t0 + row : t0];
-    const int ib = tl & 0xff, jb = tl >> 8;
-    const int i = ib * kTile + li;
-    const float4 own = sph[i];
-    // bit jj of bitmap[j / 32][i] <-> pair (i, j): the 16 bits of this tile's j block
-    const uint32_t word = has ? (a.bitmap[(size_t)(jb >> 1) * SL + i] >> ((jb & 1) * 16)) & 0xffffu : 0u;
-    if (__ballot(word != 0u) == 0ull) continue;
-    const float4 *sj = sph + jb * kTile;
-    float tm = 0.0f;
-#pragma unroll
-    for (int jj = 0; jj < kTile; jj++) tm = fmaxf(tm, mask_f(pair_pen(own, sj[jj]), word, jj));
-    if (tm > 0.0f && tm >= bv) {  // the lane's best so far, or a tie with it: the first j of this tile that attains the
-      // maximum.  Value and index come from THIS loop (the unrolled loop above may contract the products differently,
-      // so an equality test against its maximum can fail by an ulp)
-      float tv = 0.0f;
-      int jf = 0;
-#pragma unroll 1
-      for (int jj = 0; jj < kTile; jj++) {
-        const float v = mask_f(pair_pen(own, sj[jj]), word, jj);
-        if (v > tv) { tv = v; jf = jj; }
-      }
-      if (tv > 0.0f && tv >= bv) {
-        const int key = (i << 10) | (jb * kTile + jf);
-        if (tv > bv || key < bkey) bkey = key;
-        bv = tv;
-      }
-    }
-  }
-  // ---- arg-max over the wave: largest penetration, then the lexicographically first (i, j)
-  float m = bv;
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
-  int key = (m > 0.0f && bv == m) ? bkey : 0x7fffffff;
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) key = min(key, __shfl_xor(key, off, kWave));
-  if (lane != 0) return;
-  if (!(m > 0.0f) || key == 0x7fffffff) {
-    a.out_distance[n] = 0.0f;
-    return;
-  }
-  const float wgt = a.weight[0];
-  a.out_distance[n] = 0.5f * wgt * m;
-  if (a.write_grad) {
-    const int i = key >> 10, j = key & 1023;
-    const float4 s1 = sph[i], s2 = sph[j];
-    const float vx = wgt * (s2.x - s1.x), vy = wgt * (s2.y - s1.y), vz = wgt * (s2.z - s1.z);
-    float4 *g = reinterpret_cast<float4 *>(a.out_gradient) + (size_t)n * S;
-    g[i] = make_float4(vx, vy, vz, wgt * -1.0f);
-    g[j] = make_float4(-1.0f * vx, -1.0f * vy, -1.0f * vz, wgt * -1.0f);
-    a.sparse_index[(size_t)n * S + i] = 1;
-    a.sparse_index[(size_t)n * S + j] = 1;
-  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -535,6 +442,101 @@ __host__ __device__ inline size_t tiles2_lds_floats(int nslots, int n_tiles) {
   return SL * 4 + (SL / kTile) * kT2Box + (SL / 4) * kT2Box + kT2Waves * (tiles2_kept_cap(n_tiles) + kT2Ring) + 2 * kT2Waves;
 }
 
+// ---- what the two-level and the matrix-core kernel share: one point per workgroup of NWAVES wavefronts
+constexpr int kMaxTileTrips = 8;  // <= 8 * 256 = 2048 listed tiles (64 x 64 blocks of 16 spheres hold 2080)
+constexpr int kMaxSlots = 4;      // nslots <= 16, four wavefronts
+
+// Boxes (lo xyz, hi xyz) of the 16 consecutive spheres of a DPP row, stored by the row's first lane; QUADS: also of every 4
+// consecutive spheres (the second step of the row maximum is the quad's).  Disabled / padding spheres: an empty box.
+template <bool QUADS>
+__device__ __forceinline__ void block_boxes(float4 v, int sl, int lane, float *box, float *box4) {
+  const bool on = v.w == v.w;
+  const float big = 3.0e38f;
+  float e[6] = {on ? v.w - v.x : -big, on ? v.w - v.y : -big, on ? v.w - v.z : -big,
+                on ? v.x + v.w : -big, on ? v.y + v.w : -big, on ? v.z + v.w : -big};
+  auto put = [&](float *b) { b[0] = -e[0]; b[1] = -e[1]; b[2] = -e[2]; b[3] = e[3]; b[4] = e[4]; b[5] = e[5]; };
+#pragma unroll
+  for (int c = 0; c < 6; c++) {  // quad maximum, then the row's
+    e[c] = fmaxf(e[c], dpp_f<0xB1>(e[c]));
+    e[c] = fmaxf(e[c], dpp_f<0x4E>(e[c]));
+  }
+  if (QUADS && (lane & 3) == 0) put(box4 + (size_t)((sl * 64 + lane) >> 2) * kT2Box);
+#pragma unroll
+  for (int c = 0; c < 6; c++) {
+    e[c] = fmaxf(e[c], dpp_f<0x141>(e[c]));
+    e[c] = fmaxf(e[c], dpp_f<0x140>(e[c]));
+  }
+  if ((lane & 15) == 0) put(box + (sl * 4 + (lane >> 4)) * kT2Box);
+}
+
+// Spheres (+ padding) of point n -> LDS, stale gradient rows cleared, boxes on the way.  Wavefront `wave` takes the slots
+// u * NWAVES + wave, and every load of the wavefront is in flight before the first use.  each(s, v): what a kernel adds per
+// staged sphere.
+template <int NWAVES, bool QUADS, class F>
+__device__ __forceinline__ void stage_point_prefetched(const SelfDenseArgs &a, int n, int wave, int lane, float4 *sph, float *box,
+                                                       float *box4, F each) {
+  const int S = a.nspheres, NS = a.nslots;
+  const float4 *src = reinterpret_cast<const float4 *>(a.robot_spheres) + (size_t)n * S;
+  float4 sv[kMaxSlots];
+  float off[kMaxSlots];
+  uint8_t dirty[kMaxSlots];
+#pragma unroll
+  for (int u = 0; u < kMaxSlots; u++) {
+    const int s = (u * NWAVES + wave) * 64 + lane;
+    const bool in = u * NWAVES + wave < NS && s < S;
+    sv[u] = in ? src[s] : make_float4(0.f, 0.f, 0.f, __builtin_nanf(""));
+    off[u] = in ? a.offsets[s] : 0.0f;
+    dirty[u] = in ? a.sparse_index[(size_t)n * S + s] : (uint8_t)0;
+  }
+#pragma unroll
+  for (int u = 0; u < kMaxSlots; u++) {
+    const int sl = u * NWAVES + wave;
+    if (sl >= NS) break;
+    const int s = sl * 64 + lane;
+    float4 v = sv[u];
+    if (s < S) {
+      v = pad_radius<true>(v, off[u]);
+      clear_stale_row(a, (size_t)n * S + s, dirty[u]);
+    }
+    sph[s] = v;
+    each(s, v);
+    block_boxes<QUADS>(v, sl, lane, box, box4);
+  }
+}
+
+// This wavefront's share of the level-1 tile list: requested before the staging, used after it (the list is 3 KB: L2)
+template <int NWAVES>
+__device__ __forceinline__ void load_my_tiles(const SelfTilesArgs &t, int wave, int lane, int (&my_tiles)[kMaxTileTrips]) {
+#pragma unroll
+  for (int u = 0; u < kMaxTileTrips; u++) {
+    const int c = (u * NWAVES + wave) * kWave + lane;
+    my_tiles[u] = c < t.n_tiles ? t.tiles[c] : -1;
+  }
+}
+
+// Level 1: the tiles of that share whose block boxes overlap, compacted into kept[] in list order; returns their number.
+// TAG: the tile's index in the list goes into the high half-word.
+template <int NWAVES, bool TAG>
+__device__ __forceinline__ int broad_phase_level1(const int (&my_tiles)[kMaxTileTrips], int n_tiles, const float *box, int *kept,
+                                                  int wave, int lane) {
+  int count = 0;
+#pragma unroll
+  for (int u = 0; u < kMaxTileTrips; u++) {
+    const int c0 = (u * NWAVES + wave) * kWave;
+    if (c0 >= n_tiles) break;
+    const int tl = my_tiles[u];
+    bool keep = false;
+    if (tl >= 0) {
+      const float *bi = box + (tl & 0xff) * kT2Box, *bj = box + (tl >> 8) * kT2Box;
+      keep = bi[0] <= bj[3] && bj[0] <= bi[3] && bi[1] <= bj[4] && bj[1] <= bi[4] && bi[2] <= bj[5] && bj[2] <= bi[5];
+    }
+    const unsigned long long m = __ballot(keep);
+    if (keep) kept[count + __popcll(m & ((1ull << lane) - 1ull))] = TAG ? tl | ((c0 + lane) << 16) : tl;
+    count += __popcll(m);
+  }
+  return count;
+}
+
 // One POINT per workgroup of four wavefronts.  A wavefront per point is latency bound (a dependent chain of LDS and
 // L2 round trips) and a CU only holds as many points as their spheres fit in its LDS (G1: 6-9): the SIMDs idle.  Four
 // wavefronts that share the point's staged spheres and boxes split the staging, the tile list and the narrow phase, so a CU
@@ -552,92 +554,19 @@ __global__ void __launch_bounds__(kT2Waves * 64) self_collision_tiles2_kernel(co
   int *ring = kept + kept_cap;                            // ... and its surviving 4 x 4 sub-tiles
   float *red = box4 + NB4 * kT2Box + kT2Waves * (kept_cap + kT2Ring);  // [kT2Waves] (penetration, key) per wavefront
   const int n = blockIdx.x;
-  const float qnan = __builtin_nanf("");
-  const int row = lane >> 4, li = lane & 15;
-  // this wavefront's tiles of the level-1 list: requested now, used after the staging (the list is 3 KB: L2)
-  constexpr int kMaxTileTrips = 8;  // <= 8 * 256 = 2048 listed tiles (64 x 64 blocks of 16 spheres hold 2080)
   int my_tiles[kMaxTileTrips];
-#pragma unroll
-  for (int u = 0; u < kMaxTileTrips; u++) {
-    const int c = (u * kT2Waves + wave) * kWave + lane;
-    my_tiles[u] = c < t.n_tiles ? t.tiles[c] : -1;
-  }
-  {  // spheres (+ padding) -> LDS, stale gradient rows cleared, boxes of 4 and of 16 consecutive spheres on the way
-    const float4 *src = reinterpret_cast<const float4 *>(a.robot_spheres) + (size_t)n * S;
-    constexpr int kMaxSlots = 4;  // nslots <= 16, four wavefronts
-    float4 sv[kMaxSlots];
-    float off[kMaxSlots];
-    uint8_t dirty[kMaxSlots];
-#pragma unroll
-    for (int u = 0; u < kMaxSlots; u++) {  // every load of the wavefront in flight before the first use
-      const int s = (u * kT2Waves + wave) * 64 + lane;
-      const bool in = u * kT2Waves + wave < NS && s < S;
-      sv[u] = in ? src[s] : make_float4(0.f, 0.f, 0.f, qnan);
-      off[u] = in ? a.offsets[s] : 0.0f;
-      dirty[u] = in ? a.sparse_index[(size_t)n * S + s] : (uint8_t)0;
-    }
-#pragma unroll
-    for (int u = 0; u < kMaxSlots; u++) {
-      const int sl = u * kT2Waves + wave;
-      if (sl >= NS) break;
-      const int s = sl * 64 + lane;
-      float4 v = sv[u];
-      if (s < S) {
-        v.w += off[u];
-        if (!(v.w >= 0.0f)) v.w = qnan;
-        if (dirty[u]) {
-          reinterpret_cast<float4 *>(a.out_gradient)[(size_t)n * S + s] = make_float4(0.f, 0.f, 0.f, 0.f);
-          a.sparse_index[(size_t)n * S + s] = 0;
-        }
-      }
-      sph[s] = v;
-      const bool on = v.w == v.w;  // disabled / padding spheres: an empty box
-      const float big = 3.0e38f;
-      float e[6] = {on ? v.w - v.x : -big, on ? v.w - v.y : -big, on ? v.w - v.z : -big,
-                    on ? v.x + v.w : -big, on ? v.y + v.w : -big, on ? v.z + v.w : -big};
-#pragma unroll
-      for (int c = 0; c < 6; c++) {  // quad maximum, then the row's
-        e[c] = fmaxf(e[c], dpp_f<0xB1>(e[c]));
-        e[c] = fmaxf(e[c], dpp_f<0x4E>(e[c]));
-      }
-      if ((lane & 3) == 0) {
-        float *b = box4 + (size_t)(s >> 2) * kT2Box;
-        b[0] = -e[0]; b[1] = -e[1]; b[2] = -e[2]; b[3] = e[3]; b[4] = e[4]; b[5] = e[5];
-      }
-#pragma unroll
-      for (int c = 0; c < 6; c++) {
-        e[c] = fmaxf(e[c], dpp_f<0x141>(e[c]));
-        e[c] = fmaxf(e[c], dpp_f<0x140>(e[c]));
-      }
-      if (li == 0) {
-        float *b = box + (sl * 4 + row) * kT2Box;
-        b[0] = -e[0]; b[1] = -e[1]; b[2] = -e[2]; b[3] = e[3]; b[4] = e[4]; b[5] = e[5];
-      }
-    }
-  }
+  load_my_tiles<kT2Waves>(t, wave, lane, my_tiles);
+  // boxes of 4 and of 16 consecutive spheres
+  stage_point_prefetched<kT2Waves, true>(a, n, wave, lane, sph, box, box4, [](int, float4) {});
   __syncthreads();
-  // ---- level 1: this wavefront's share of the tiles whose block boxes overlap, compacted in list order
-  int count = 0;
-#pragma unroll
-  for (int u = 0; u < kMaxTileTrips; u++) {
-    if ((u * kT2Waves + wave) * kWave >= t.n_tiles) break;
-    const int tl = my_tiles[u];
-    bool keep = false;
-    if (tl >= 0) {
-      const float *bi = box + (tl & 0xff) * kT2Box, *bj = box + (tl >> 8) * kT2Box;
-      keep = bi[0] <= bj[3] && bj[0] <= bi[3] && bi[1] <= bj[4] && bj[1] <= bi[4] && bi[2] <= bj[5] && bj[2] <= bi[5];
-    }
-    const unsigned long long m = __ballot(keep);
-    if (keep) kept[count + __popcll(m & ((1ull << lane) - 1ull))] = tl;
-    count += __popcll(m);
-  }
+  const int count = broad_phase_level1<kT2Waves, false>(my_tiles, t.n_tiles, box, kept, wave, lane);
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
   // ---- level 2: four tiles = 64 sub-tiles per round, one per lane.  A surviving sub-tile fetches its 16 bits of the pair
   // bitmap (one 16-byte load: the words of its four spheres i) -- sub-tiles without a listed pair drop out here and the
   // narrow phase needs no memory access besides LDS.  Ring entry: ib4 | jb4 << 8 | bits << 16.
   float bv = 0.0f;
-  int bkey = 0x7fffffff;
+  int bkey = kNoKey;
   int n4 = 0;  // sub-tiles in the ring (uniform)
   const int sub_t = lane >> 4, pi = (lane >> 2) & 3, pj = lane & 3;
   auto narrow = [&](int first) {  // ring entries first .. first + 3 (entries beyond n4 are skipped by `has`)
@@ -701,42 +630,9 @@ __global__ void __launch_bounds__(kT2Waves * 64) self_collision_tiles2_kernel(co
     if (n4 + 64 > kT2Ring) drain(false);
   }
   drain(true);
-  // ---- arg-max: largest penetration, then the lexicographically first (i, j); over the wavefront, then over the four
-  float m = bv;
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
-  int key = (m > 0.0f && bv == m) ? bkey : 0x7fffffff;
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) key = min(key, __shfl_xor(key, off, kWave));
-  if (lane == 0) {
-    red[wave * 2] = m;
-    reinterpret_cast<int *>(red)[wave * 2 + 1] = key;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  m = 0.0f;
-  key = 0x7fffffff;
-  for (int w = 0; w < kT2Waves; w++) {
-    const float mw = red[w * 2];
-    const int kw = reinterpret_cast<const int *>(red)[w * 2 + 1];
-    if (mw > m || (mw == m && kw < key)) { m = mw; key = kw; }
-  }
-  if (!(m > 0.0f) || key == 0x7fffffff) {
-    a.out_distance[n] = 0.0f;
-    return;
-  }
-  const float wgt = a.weight[0];
-  a.out_distance[n] = 0.5f * wgt * m;
-  if (a.write_grad) {
-    const int i = key >> 10, j = key & 1023;
-    const float4 s1 = sph[i], s2 = sph[j];
-    const float vx = wgt * (s2.x - s1.x), vy = wgt * (s2.y - s1.y), vz = wgt * (s2.z - s1.z);
-    float4 *g = reinterpret_cast<float4 *>(a.out_gradient) + (size_t)n * S;
-    g[i] = make_float4(vx, vy, vz, wgt * -1.0f);
-    g[j] = make_float4(-1.0f * vx, -1.0f * vy, -1.0f * vz, wgt * -1.0f);
-    a.sparse_index[(size_t)n * S + i] = 1;
-    a.sparse_index[(size_t)n * S + j] = 1;
-  }
+  // ---- arg-max over the wavefront, then over the four
+  MaxKey r = wave_argmax(bv, bkey);
+  if (block_argmax<kT2Waves>(r, red, wave, lane)) finalize_point(a, S, n, sph, r);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -771,78 +667,14 @@ __global__ void __launch_bounds__(kTmWaves * 64) self_collision_tiles_mfma_kerne
   int *kept = reinterpret_cast<int *>(box + NB * kT2Box) + wave * kept_cap;  // this wavefront's surviving tiles
   float *red = box + NB * kT2Box + kTmWaves * kept_cap;   // [kTmWaves] (penetration, key) per wavefront
   const int n = blockIdx.x;
-  const float qnan = __builtin_nanf("");
-  const int row = lane >> 4, li = lane & 15;
-  constexpr int kMaxTileTrips = 8;  // <= 8 * 256 = 2048 listed tiles
   int my_tiles[kMaxTileTrips];
-#pragma unroll
-  for (int u = 0; u < kMaxTileTrips; u++) {
-    const int c = (u * kTmWaves + wave) * kWave + lane;
-    my_tiles[u] = c < t.n_tiles ? t.tiles[c] : -1;
-  }
-  {  // spheres (+ padding) -> LDS with their row / column term, stale gradient rows cleared, boxes of 16 consecutive spheres
-    const float4 *src = reinterpret_cast<const float4 *>(a.robot_spheres) + (size_t)n * S;
-    constexpr int kMaxSlots = 4;  // nslots <= 16, four wavefronts
-    float4 sv[kMaxSlots];
-    float off[kMaxSlots];
-    uint8_t dirty[kMaxSlots];
-#pragma unroll
-    for (int u = 0; u < kMaxSlots; u++) {
-      const int s = (u * kTmWaves + wave) * 64 + lane;
-      const bool in = u * kTmWaves + wave < NS && s < S;
-      sv[u] = in ? src[s] : make_float4(0.f, 0.f, 0.f, qnan);
-      off[u] = in ? a.offsets[s] : 0.0f;
-      dirty[u] = in ? a.sparse_index[(size_t)n * S + s] : (uint8_t)0;
-    }
-#pragma unroll
-    for (int u = 0; u < kMaxSlots; u++) {
-      const int sl = u * kTmWaves + wave;
-      if (sl >= NS) break;
-      const int s = sl * 64 + lane;
-      float4 v = sv[u];
-      if (s < S) {
-        v.w += off[u];
-        if (!(v.w >= 0.0f)) v.w = qnan;
-        if (dirty[u]) {
-          reinterpret_cast<float4 *>(a.out_gradient)[(size_t)n * S + s] = make_float4(0.f, 0.f, 0.f, 0.f);
-          a.sparse_index[(size_t)n * S + s] = 0;
-        }
-      }
-      sph[s] = v;
-      aterm[s] = 0.5f * (v.w * v.w - (v.x * v.x + v.y * v.y + v.z * v.z));
-      const bool on = v.w == v.w;  // disabled / padding spheres: an empty box
-      const float big = 3.0e38f;
-      float e[6] = {on ? v.w - v.x : -big, on ? v.w - v.y : -big, on ? v.w - v.z : -big,
-                    on ? v.x + v.w : -big, on ? v.y + v.w : -big, on ? v.z + v.w : -big};
-#pragma unroll
-      for (int c = 0; c < 6; c++) {
-        e[c] = fmaxf(e[c], dpp_f<0xB1>(e[c]));
-        e[c] = fmaxf(e[c], dpp_f<0x4E>(e[c]));
-        e[c] = fmaxf(e[c], dpp_f<0x141>(e[c]));
-        e[c] = fmaxf(e[c], dpp_f<0x140>(e[c]));
-      }
-      if (li == 0) {
-        float *b = box + (sl * 4 + row) * kT2Box;
-        b[0] = -e[0]; b[1] = -e[1]; b[2] = -e[2]; b[3] = e[3]; b[4] = e[4]; b[5] = e[5];
-      }
-    }
-  }
+  load_my_tiles<kTmWaves>(t, wave, lane, my_tiles);
+  // boxes of 16 consecutive spheres; every sphere with its row / column term
+  stage_point_prefetched<kTmWaves, false>(a, n, wave, lane, sph, box, nullptr, [&](int s, float4 v) {
+    aterm[s] = 0.5f * (v.w * v.w - (v.x * v.x + v.y * v.y + v.z * v.z));
+  });
   __syncthreads();
-  // ---- level 1: this wavefront's share of the tiles whose block boxes overlap, compacted in list order
-  int count = 0;
-#pragma unroll
-  for (int u = 0; u < kMaxTileTrips; u++) {
-    if ((u * kTmWaves + wave) * kWave >= t.n_tiles) break;
-    const int tl = my_tiles[u];
-    bool keep = false;
-    if (tl >= 0) {
-      const float *bi = box + (tl & 0xff) * kT2Box, *bj = box + (tl >> 8) * kT2Box;
-      keep = bi[0] <= bj[3] && bj[0] <= bi[3] && bi[1] <= bj[4] && bj[1] <= bi[4] && bi[2] <= bj[5] && bj[2] <= bi[5];
-    }
-    const unsigned long long m = __ballot(keep);
-    if (keep) kept[count + __popcll(m & ((1ull << lane) - 1ull))] = tl | (((u * kTmWaves + wave) * kWave + lane) << 16);  // + its list index
-    count += __popcll(m);
-  }
+  const int count = broad_phase_level1<kTmWaves, true>(my_tiles, t.n_tiles, box, kept, wave, lane);
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
   // ---- narrow phase: one tile per pair of matrix-core instructions.  Lane (k = lane / 16, m = lane % 16) feeds component k of
@@ -852,7 +684,7 @@ __global__ void __launch_bounds__(kTmWaves * 64) self_collision_tiles_mfma_kerne
   // no accumulator initialisation, no doubling.  A disabled / padding sphere carries NaN: its whole row / column is NaN and
   // compares false.
   float bv = 0.0f;
-  int bkey = 0x7fffffff;
+  int bkey = kNoKey;
   const int kk = lane >> 4, mm = lane & 15;
   const char *sphb = reinterpret_cast<const char *>(sph) + (mm * 4 + kk) * 4;  // + 256 * block: component kk of its sphere mm
   const char *ahb = reinterpret_cast<const char *>(aterm) + mm * 4;             // + 64 * block: h of its sphere mm
@@ -911,42 +743,9 @@ __global__ void __launch_bounds__(kTmWaves * 64) self_collision_tiles_mfma_kerne
       }
     }
   }
-  // ---- arg-max: largest penetration, then the lexicographically first (i, j); over the wavefront, then over the four
-  float m = bv;
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
-  int key = (m > 0.0f && bv == m) ? bkey : 0x7fffffff;
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) key = min(key, __shfl_xor(key, off, kWave));
-  if (lane == 0) {
-    red[wave * 2] = m;
-    reinterpret_cast<int *>(red)[wave * 2 + 1] = key;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  m = 0.0f;
-  key = 0x7fffffff;
-  for (int w = 0; w < kTmWaves; w++) {
-    const float mw = red[w * 2];
-    const int kw = reinterpret_cast<const int *>(red)[w * 2 + 1];
-    if (mw > m || (mw == m && kw < key)) { m = mw; key = kw; }
-  }
-  if (!(m > 0.0f) || key == 0x7fffffff) {
-    a.out_distance[n] = 0.0f;
-    return;
-  }
-  const float wgt = a.weight[0];
-  a.out_distance[n] = 0.5f * wgt * m;
-  if (a.write_grad) {
-    const int i = key >> 10, j = key & 1023;
-    const float4 s1 = sph[i], s2 = sph[j];
-    const float vx = wgt * (s2.x - s1.x), vy = wgt * (s2.y - s1.y), vz = wgt * (s2.z - s1.z);
-    float4 *g = reinterpret_cast<float4 *>(a.out_gradient) + (size_t)n * S;
-    g[i] = make_float4(vx, vy, vz, wgt * -1.0f);
-    g[j] = make_float4(-1.0f * vx, -1.0f * vy, -1.0f * vz, wgt * -1.0f);
-    a.sparse_index[(size_t)n * S + i] = 1;
-    a.sparse_index[(size_t)n * S + j] = 1;
-  }
+  // ---- arg-max over the wavefront, then over the four
+  MaxKey r = wave_argmax(bv, bkey);
+  if (block_argmax<kTmWaves>(r, red, wave, lane)) finalize_point(a, S, n, sph, r);
 }
 
 template <int NWAVES>
@@ -1025,11 +824,9 @@ CUROBO_EXPORT int curobo_hip_self_collision_distance_dense(
   hipStream_t st = (hipStream_t)stream;
   static const bool no_tiles = getenv("CUROBO_HIP_SELF_NO_BROAD_PHASE") != nullptr;
   if (tile_list != nullptr && num_tiles > 0 && !no_tiles) {  // broad phase over 16 x 16 tiles
-    static const bool one_level = getenv("CUROBO_HIP_SELF_ONE_LEVEL") != nullptr;  // (A/B knob: the round-2 kernel)
     SelfTilesArgs ta{a, tile_list, num_tiles, tile_lane_masks};
     static bool attr2 = false;
     if (!attr2) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(self_collision_tiles_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(self_collision_tiles2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
       attr2 = true;
     }
@@ -1039,7 +836,7 @@ CUROBO_EXPORT int curobo_hip_self_collision_distance_dense(
     // wave-instructions, 4.1 SIMD-cycles each).  It runs on request (CUROBO_HIP_SELF_MFMA=1, the tests); the default stays the
     // two-level kernel.
     const bool use_mfma = getenv("CUROBO_HIP_SELF_MFMA") != nullptr;  // (read per call: the tests switch it)
-    if (!one_level && use_mfma) {  // level-1 block boxes, then one 16 x 16 tile per pair of matrix-core instructions
+    if (use_mfma) {  // level-1 block boxes, then one 16 x 16 tile per pair of matrix-core instructions
       static bool attr3 = false;
       if (!attr3) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(self_collision_tiles_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
@@ -1050,18 +847,10 @@ CUROBO_EXPORT int curobo_hip_self_collision_distance_dense(
       hipLaunchKernelGGL(self_collision_tiles_mfma_kernel, dim3((unsigned)n_points), dim3(kTmWaves * 64), lds, st, ta);
       return check_launch(what, st);
     }
-    if (!one_level) {  // two-level broad phase, four wavefronts per point
-      const size_t lds = tiles2_lds_floats(nslots, num_tiles) * sizeof(float);
-      CUROBO_REQUIRE(lds <= 64 * 1024 && num_tiles <= 2048 && nslots <= 16, "%s: too many tiles / spheres for the LDS tiling", what);
-      hipLaunchKernelGGL(self_collision_tiles2_kernel, dim3((unsigned)n_points), dim3(kT2Waves * 64), lds, st, ta);
-      return check_launch(what, st);
-    }
-    const size_t wave_bytes = ((size_t)nslots * 64 * 4 + (size_t)nslots * 4 * 8 + (size_t)((num_tiles + 3) & ~3)) * sizeof(float);
-    // one wavefront per workgroup for big robots: the CU then holds as many wavefronts as its LDS allows, not a
-    // multiple of a workgroup's
-    const int wv = wave_bytes >= 8 * 1024 ? 1 : 4;
-    CUROBO_REQUIRE(wave_bytes * wv <= 64 * 1024, "%s: too many tiles / spheres for the LDS tiling", what);
-    hipLaunchKernelGGL(self_collision_tiles_kernel, dim3((unsigned)ceil_div_l(n_points, wv)), dim3(wv * 64), wave_bytes * wv, st, ta);
+    // two-level broad phase, four wavefronts per point
+    const size_t lds = tiles2_lds_floats(nslots, num_tiles) * sizeof(float);
+    CUROBO_REQUIRE(lds <= 64 * 1024 && num_tiles <= 2048 && nslots <= 16, "%s: too many tiles / spheres for the LDS tiling", what);
+    hipLaunchKernelGGL(self_collision_tiles2_kernel, dim3((unsigned)n_points), dim3(kT2Waves * 64), lds, st, ta);
     return check_launch(what, st);
   }
   const size_t lds_wave = (size_t)nslots * 64 * 16;

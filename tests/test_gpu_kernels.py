@@ -176,7 +176,7 @@ def test_fk_sphere_sets_per_environment(robot, oracle, device):
     np.testing.assert_allclose(out.cpu().numpy(), want_g, atol=1e-5 * scale, rtol=1e-4)
 
 
-@pytest.mark.parametrize("robot,n", [("franka", 515), ("ur10e", 64), ("unitree_g1", 33)])
+@pytest.mark.parametrize("robot,n", [("franka", 515), ("franka", 17), ("ur10e", 64), ("unitree_g1", 33)])
 def test_self_collision(robot, n, oracle, device):
     from curobo_amd.backends import geometry as G
 
@@ -585,6 +585,163 @@ def test_self_collision_dense_bitmap_kernel_c4_size(oracle, device):
     np.testing.assert_allclose(g1, ref["gradient"], atol=ATOL, rtol=1e-5)
     np.testing.assert_allclose(d1, d0, atol=1e-6, rtol=1e-6)
     np.testing.assert_allclose(g1, g0, atol=1e-6, rtol=1e-6)
+
+
+def _self_collision_forms(kp, sph, padding, stale_grad, stale_flag, device, weight=2.5):
+    """(distance [n], gradient [n, S, 4], flags [n, S]) of n points from every kernel form that serves a dense pair set: the
+    two-level bitmap kernel (what the drop-in entry point picks), its matrix-core narrow phase, the register-tiled kernel
+    without a broad phase (no tile list) and the LDS pair-list kernel."""
+    import os
+
+    from curobo_amd._lib import check, current_stream, load, ptr
+    from curobo_amd.backends import geometry as G
+
+    sc = kp.self_collision
+    n, S = sph.shape[0], sph.shape[1]
+    P = int(sc.collision_pairs.shape[0])
+    t = lambda a: torch.as_tensor(a, device=device)  # noqa: E731
+    w, pad, sph_d = torch.tensor([weight], device=device), t(np.asarray(padding, np.float32)), t(sph)
+    bm = G.pair_bitmap(sc.collision_pairs, S)
+    assert bm is not None
+
+    def run(form):
+        out_d, out_g, flags = torch.full((n, 1), -1.0, device=device), t(stale_grad.copy()), t(stale_flag.copy())
+        if form in ("tiles2", "mfma"):
+            G.self_collision_distance(out_d, out_g, torch.zeros(1, device=device), flags, sph_d, pad, w, sc.collision_pairs,
+                                      torch.zeros(1, device=device), torch.zeros(2, dtype=torch.int16, device=device), 1, 256, n, 1, S, P,
+                                      False, True)
+        elif form == "dense":
+            check(load().curobo_hip_self_collision_distance_dense(
+                ptr(out_d), ptr(out_g), ptr(flags), ptr(sph_d), ptr(pad), ptr(w), ptr(bm[0]), None, 0, None, n, 1, S, bm[1], 1,
+                current_stream(out_d)))
+        else:
+            check(load().curobo_hip_self_collision_distance(
+                ptr(out_d), ptr(out_g), None, ptr(flags), ptr(sph_d), ptr(pad), ptr(w), ptr(sc.collision_pairs), None, None,
+                1, 256, n, 1, S, P, 0, 1, current_stream(out_d)))
+        torch.cuda.synchronize()
+        return out_d.cpu().numpy()[:, 0], out_g.cpu().numpy(), flags.cpu().numpy()
+
+    out = {form: run(form) for form in ("tiles2", "dense", "list")}
+    os.environ["CUROBO_HIP_SELF_MFMA"] = "1"
+    try:
+        out["mfma"] = run("mfma")
+    finally:
+        del os.environ["CUROBO_HIP_SELF_MFMA"]
+    return out
+
+
+def test_self_collision_every_dense_form_small(oracle, device):
+    """Unitree G1 (674 spheres: 12 slots of 64, the last two ragged / empty) at five points -- one point per workgroup for the
+    two-level and the matrix-core kernel, a second workgroup with three idle wavefronts for the register-tiled one -- through
+    all four forms vs the oracle: exact flags, stale rows cleared, a disabled sphere ignored."""
+    model = load_model("unitree_g1")
+    kp = _kp(model, device)
+    n, S = 5, model.num_spheres
+    q = sample_q(model, n, seed=1, scale=0.6)
+    sph = oracle.kinematics_forward(q, model.as_dict())["robot_spheres"].copy()
+    sph[2, 322, 3] = -0.5   # a disabled sphere (negative radius): its pairs must not count
+    stale_grad = np.zeros((n, S, 4), np.float32)
+    stale_flag = np.zeros((n, S), np.uint8)
+    stale_grad[[0, 3], 11] = 3.0
+    stale_flag[[0, 3], 11] = 1
+    ref = oracle.self_collision(sph, model.sphere_padding, model.collision_pairs, 2.5, out_gradient=stale_grad.copy(),
+                                sparse_index=stale_flag.copy())
+    assert (ref["distance"] > 0).any() and (ref["distance"] == 0).any(), "test inputs must hold a colliding and a free point"
+    out = _self_collision_forms(kp, sph, model.sphere_padding, stale_grad, stale_flag, device)
+    for form, (d, g, f) in out.items():
+        assert np.array_equal(f, ref["sparse_index"]), f"{form}: collision-pair indices must be exact"
+        np.testing.assert_allclose(d, ref["distance"], atol=ATOL, rtol=1e-5, err_msg=form)
+        np.testing.assert_allclose(g, ref["gradient"], atol=ATOL, rtol=1e-5, err_msg=form)
+    for form in ("tiles2", "dense"):
+        np.testing.assert_allclose(out[form][0], out["list"][0], atol=1e-6, rtol=1e-6, err_msg=form)
+        np.testing.assert_allclose(out[form][1], out["list"][1], atol=1e-6, rtol=1e-6, err_msg=form)
+    for a, b in zip(out["mfma"], out["tiles2"]):
+        assert np.array_equal(a, b), "the matrix-core narrow phase must give every bit of the two-level kernel"
+
+
+def _placed_tie(model, pair1, pair2):
+    """The robot's spheres on a 0.5 m grid inside +-2 m, radius 0.05: nothing touches, every coordinate is exact in fp32.
+    Then sphere j of each of the two pairs is put 0.0625 m beside its sphere i: both pairs penetrate by the same bits,
+    (0.05 + 0.05)^2 - 0.0625^2."""
+    S = model.num_spheres
+    g = np.arange(-2.0, 2.01, 0.5, dtype=np.float32)
+    s = np.arange(S)
+    sph = np.stack([g[s % 9], g[(s // 9) % 9], g[s // 81], np.full(S, 0.05, np.float32)], axis=1).astype(np.float32)
+    listed = {tuple(p) for p in np.asarray(model.collision_pairs).reshape(-1, 2).tolist()}
+    for i, j in (pair1, pair2):
+        assert (i, j) in listed
+        sph[j, :3] = sph[i, :3] + np.array([0.0625, 0.0, 0.0], np.float32)
+    return sph[None]
+
+
+def _assert_tie_answer(name, d, g, f, pair, weight=2.5):
+    """the literal answer of a placed tie won by `pair`: its two flags, the gradient rows +-w (0.0625, 0, 0) with -w in the
+    radius slot (all exact in fp32), and the cost w / 2 * ((0.05 + 0.05)^2 - 0.0625^2) in either fp32 rounding of the
+    penetration (fused or separate multiply and subtract)"""
+    i, j = pair
+    assert np.flatnonzero(f[0]).tolist() == [i, j], f"{name}: a tie goes to the lowest pair index"
+    want_g = np.zeros_like(g)
+    want_g[0, i] = [weight * 0.0625, 0.0, 0.0, -weight]
+    want_g[0, j] = [-weight * 0.0625, 0.0, 0.0, -weight]
+    assert np.array_equal(g, want_g), name
+    rr = np.float32(0.05) + np.float32(0.05)
+    fused = np.float32(float(rr) * float(rr) - 0.0625 * 0.0625)  # (exact in float64: 48 + 8 significant bits)
+    separate = np.float32(rr * rr) - np.float32(0.0625 * 0.0625)
+    half_w = np.float32(0.5) * np.float32(weight)
+    assert d[0] in (half_w * fused, half_w * separate), f"{name}: {float(d[0]).hex()}"
+
+
+# (pair 1, pair 2) of the G1's pair list with pair 1 < pair 2: in ONE 16 x 16 tile (0, 4) of the pair matrix; in the tiles
+# (0, 3) and (2, 5), entries 0 and 64 of the tile list, which two different wavefronts of a workgroup test
+G1_TIES = {"one_tile": ((0, 64), (1, 65)), "two_wavefronts": ((0, 63), (32, 80))}
+
+
+@pytest.mark.parametrize("case", sorted(G1_TIES))
+def test_self_collision_placed_tie_dense_forms(case, oracle, device):
+    """Two listed pairs with bit-identical penetration: every form flags the lower pair only and returns the same cost."""
+    from curobo_amd.backends import geometry as G
+
+    model = load_model("unitree_g1")
+    kp = _kp(model, device)
+    S = model.num_spheres
+    pair1, pair2 = G1_TIES[case]
+    assert pair1 < pair2
+    tiles = G.pair_bitmap(kp.self_collision.collision_pairs, S)[2].cpu().numpy().tolist()
+    c1, c2 = (tiles.index((i // 16) | ((j // 16) << 8)) for i, j in (pair1, pair2))
+    assert c2 - c1 == (0 if case == "one_tile" else 64)
+    sph = _placed_tie(model, pair1, pair2)
+    zero_pad, no_grad, no_flag = np.zeros(S, np.float32), np.zeros((1, S, 4), np.float32), np.zeros((1, S), np.uint8)
+    ref = oracle.self_collision(sph, zero_pad, model.collision_pairs, 2.5)
+    _assert_tie_answer("oracle", ref["distance"], ref["gradient"], ref["sparse_index"], pair1)
+    out = _self_collision_forms(kp, sph, zero_pad, no_grad, no_flag, device)
+    for form, (d, g, f) in out.items():
+        _assert_tie_answer(form, d, g, f, pair1)
+        assert d[0] == out["tiles2"][0][0], f"{form}: every form returns the same cost"
+
+
+def test_self_collision_placed_tie_row16(oracle, device):
+    """The same for franka through the 16-lanes-per-point kernel: entries 5 and 55 of its pair list, on lanes 5 and 7."""
+    from curobo_amd.backends import geometry as G
+
+    model = load_model("franka")
+    kp = _kp(model, device)
+    S, P = model.num_spheres, model.collision_pairs.shape[0]
+    pairs = np.asarray(model.collision_pairs).reshape(-1, 2).tolist()
+    pair1, pair2 = (0, 15), (1, 10)
+    k1, k2 = pairs.index(list(pair1)), pairs.index(list(pair2))
+    assert k1 < k2 and k1 % 16 != k2 % 16
+    sph = _placed_tie(model, pair1, pair2)
+    zero_pad = np.zeros(S, np.float32)
+    ref = oracle.self_collision(sph, zero_pad, model.collision_pairs, 2.5)
+    _assert_tie_answer("oracle", ref["distance"], ref["gradient"], ref["sparse_index"], pair1)
+    out_d, out_g = torch.full((1, 1), -1.0, device=device), torch.zeros(1, S, 4, device=device)
+    flags = torch.zeros(1, S, dtype=torch.uint8, device=device)
+    G.self_collision_distance(
+        out_d, out_g, torch.zeros(1, device=device), flags, torch.as_tensor(sph, device=device), torch.as_tensor(zero_pad, device=device),
+        torch.tensor([2.5], device=device), kp.self_collision.collision_pairs, torch.zeros(1, device=device),
+        torch.zeros(2, dtype=torch.int16, device=device), 1, 256, 1, 1, S, P, False, True)
+    torch.cuda.synchronize()
+    _assert_tie_answer("row16", out_d.cpu().numpy()[:, 0], out_g.cpu().numpy(), flags.cpu().numpy(), pair1)
 
 
 @pytest.mark.parametrize("sweep", [False, True])
