@@ -147,3 +147,94 @@ def pose_lm_step(state: torch.Tensor, workspace: torch.Tensor, n_points: int, mo
     check(load().curobo_hip_pose_lm_step(
         ptr(state), ptr(workspace), int(workspace.numel() * workspace.element_size()), int(n_points), int(mode), float(lambda_initial),
         float(lambda_factor), float(lambda_min), float(lambda_max), float(rho_min), int(minimum_valid_count), current_stream(state)))
+
+
+# ---------------------------------------------------------------------------------------------------- point-to-plane ICP
+POSE_ICP_COARSE, POSE_ICP_FINE, POSE_ICP_FINALIZE = 0, 1, 2  # ``mode`` of ``curobo_hip_pose_icp_step``
+
+
+class PoseICPState(_C.Structure):
+    """``curobo_hip_pose_icp_state``: used for its field offsets; the states are a device tensor [H, POSE_ICP_STATE_WORDS]"""
+
+    _fields_ = [("T", _C.c_float * 12), ("error", _C.c_float), ("iterations", _C.c_int32), ("stopped", _C.c_int32),
+                ("solver_failed", _C.c_int32), ("n_valid", _C.c_int32), ("x", _C.c_float * 6), ("reserved", _C.c_int32)]
+
+
+POSE_ICP_STATE_WORDS = _C.sizeof(PoseICPState) // 4
+#: int32 fields of the state (every other word is a float)
+POSE_ICP_STATE_INT_FIELDS = ("iterations", "stopped", "solver_failed", "n_valid", "reserved")
+
+
+def pose_icp_state_slice(name: str) -> slice:
+    """the words of field ``name`` in each row of a state tensor"""
+    f = getattr(PoseICPState, name)
+    return slice(f.offset // 4, (f.offset + f.size) // 4)
+
+
+def pose_icp_ws_bytes(n_hypotheses: int, n_mesh: int) -> int:
+    """``curobo_hip_pose_icp_ws_bytes``"""
+    nbytes = _C.c_int64(0)
+    check(load().curobo_hip_pose_icp_ws_bytes(int(n_hypotheses), int(n_mesh), _C.cast(_C.pointer(nbytes), _C.c_void_p)))
+    return int(nbytes.value)
+
+
+def _require_icp_state(state: torch.Tensor, what: str) -> int:
+    _require(state, "state", torch.float32)
+    if state.dim() != 2 or state.shape[1] != POSE_ICP_STATE_WORDS:
+        raise ValueError(f"{what}: state must be (H, {POSE_ICP_STATE_WORDS}), got {tuple(state.shape)}")
+    return int(state.shape[0])
+
+
+def _require_workspace(workspace: torch.Tensor, like: torch.Tensor, what: str) -> int:
+    if not workspace.is_contiguous() or workspace.device != like.device:
+        raise ValueError(f"{what}: workspace must be a contiguous tensor on the state's device")
+    return int(workspace.numel() * workspace.element_size())
+
+
+def pose_icp_correspond(workspace: torch.Tensor, mesh_points: torch.Tensor, mesh_normals: torch.Tensor, observed_points: torch.Tensor,
+                        state: torch.Tensor, distance_threshold: float, use_huber: bool, huber_delta: float, honour_stopped: bool = True,
+                        out_index: Optional[torch.Tensor] = None, out_distance: Optional[torch.Tensor] = None) -> None:
+    """``curobo_hip_pose_icp_correspond``: mesh_points / mesh_normals [M, 3] at the H poses of ``state`` [H, POSE_ICP_STATE_WORDS]
+    against observed_points [O, 3] -> per hypothesis one row of partial sums per 64 samples in ``workspace``, and optionally
+    the per-sample nearest index [H, M] int32 (-1 when invalid) and distance [H, M]."""
+    what = "pose_icp_correspond"
+    h = _require_icp_state(state, what)
+    for name, t in (("mesh_points", mesh_points), ("mesh_normals", mesh_normals), ("observed_points", observed_points)):
+        _require(t, name, torch.float32, state)
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{what}: {name} must be (N, 3), got {tuple(t.shape)}")
+    m, o = int(mesh_points.shape[0]), int(observed_points.shape[0])
+    if tuple(mesh_normals.shape) != (m, 3):
+        raise ValueError(f"{what}: mesh_normals must have shape {(m, 3)}, got {tuple(mesh_normals.shape)}")
+    for name, t, dt in (("out_index", out_index, torch.int32), ("out_distance", out_distance, torch.float32)):
+        _require(t, name, dt, state)
+        if t is not None and tuple(t.shape) != (h, m):
+            raise ValueError(f"{what}: {name} must have shape {(h, m)}, got {tuple(t.shape)}")
+    check(load().curobo_hip_pose_icp_correspond(
+        ptr(out_index), ptr(out_distance), ptr(workspace), _require_workspace(workspace, state, what), ptr(mesh_points), ptr(mesh_normals),
+        ptr(observed_points), ptr(state), float(distance_threshold), int(bool(use_huber)), float(huber_delta), int(bool(honour_stopped)),
+        h, m, o, current_stream(state)))
+
+
+def pose_icp_step(state: torch.Tensor, workspace: torch.Tensor, n_mesh: int, mode: int) -> None:
+    """``curobo_hip_pose_icp_step`` on ``state`` [H, POSE_ICP_STATE_WORDS] (rows in the layout of ``PoseICPState``)"""
+    what = "pose_icp_step"
+    h = _require_icp_state(state, what)
+    check(load().curobo_hip_pose_icp_step(ptr(state), ptr(workspace), _require_workspace(workspace, state, what), h, int(n_mesh), int(mode),
+                                          current_stream(state)))
+
+
+def pose_icp_select(out_index: torch.Tensor, state: torch.Tensor, out_error: Optional[torch.Tensor] = None,
+                    out_transform: Optional[torch.Tensor] = None) -> None:
+    """``curobo_hip_pose_icp_select``: out_index [1] int32 = the lowest-index minimum of the H errors; optionally its error [1]
+    and its T [12]"""
+    what = "pose_icp_select"
+    h = _require_icp_state(state, what)
+    for name, t, dt, n in (("out_index", out_index, torch.int32, 1), ("out_error", out_error, torch.float32, 1),
+                           ("out_transform", out_transform, torch.float32, 12)):
+        _require(t, name, dt, state)
+        if t is not None and t.numel() != n:
+            raise ValueError(f"{what}: {name} must hold {n} values, got {t.numel()}")
+    if out_index is None:
+        raise ValueError(f"{what}: out_index must not be None")
+    check(load().curobo_hip_pose_icp_select(ptr(out_index), ptr(out_error), ptr(out_transform), ptr(state), h, current_stream(state)))

@@ -37,6 +37,7 @@ SOURCES = [
     "graph_planner.hip",
     "perception.hip",
     "pose_detect.hip",
+    "pose_icp.hip",
 ]
 
 

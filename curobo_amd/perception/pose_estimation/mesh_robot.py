@@ -2,7 +2,7 @@
 
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -28,6 +28,7 @@ class RobotMesh:
         self.faces = torch.as_tensor(f).to(self.device)
         self._host = (v, f)
         self._mesh: Optional[DeviceMesh] = None  # built at its first use: the members above need no GPU
+        self._sample_cache: dict = {}  # n_points -> (face indices [n], barycentrics [n, 3])
 
     @classmethod
     def from_trimesh(cls, mesh, device="cuda:0") -> "RobotMesh":
@@ -46,6 +47,29 @@ class RobotMesh:
         if self._mesh is None:
             self._mesh = build_mesh_bvh(self._host[0], self._host[1], self.device, cells=False)
         return self._mesh
+
+    def sample_surface_points(self, n_points: int, resample: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(points [n_points, 3], unit normals [n_points, 3]) on the surface, uniform by area (reference mesh_robot.py:334-413):
+        the faces and barycentrics are drawn once per ``n_points`` and kept (a detector asks for its coarse and its fine count
+        in turn); ``resample=True`` draws them again"""
+        if n_points not in self._sample_cache or resample:
+            self._sample_cache[n_points] = self._generate_sample_cache(n_points)
+        face_idx, bary = self._sample_cache[n_points]
+        faces = self.faces.long()
+        v0, v1, v2 = self.vertices[faces[face_idx, 0]], self.vertices[faces[face_idx, 1]], self.vertices[faces[face_idx, 2]]
+        points = bary[:, 0:1] * v0 + bary[:, 1:2] * v1 + bary[:, 2:3] * v2
+        normals = torch.cross(v1 - v0, v2 - v0, dim=1)
+        normals = normals / (torch.norm(normals, dim=1, keepdim=True) + 1e-8)
+        return points, normals
+
+    def _generate_sample_cache(self, n_points: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        faces = self.faces.long()
+        v0, v1, v2 = self.vertices[faces[:, 0]], self.vertices[faces[:, 1]], self.vertices[faces[:, 2]]
+        areas = 0.5 * torch.norm(torch.cross(v1 - v0, v2 - v0, dim=1), dim=1)
+        face_indices = torch.multinomial(areas / (areas.sum() + 1e-8), n_points, replacement=True)
+        r1 = torch.sqrt(torch.rand(n_points, device=self.device))  # the root makes the density uniform over the triangle
+        r2 = torch.rand(n_points, device=self.device)
+        return face_indices, torch.stack([1 - r1, r1 * (1 - r2), r1 * r2], dim=1)
 
     @property
     def n_vertices(self) -> int:

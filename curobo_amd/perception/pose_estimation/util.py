@@ -1,4 +1,4 @@
-"""Helpers of the pose detectors (reference pose_estimation/util.py:16-46)."""
+"""Helpers of the pose detectors (reference pose_estimation/util.py:16-46, :116-145)."""
 
 import torch
 
@@ -16,3 +16,15 @@ def extract_observed_points(camera_obs: CameraObservation, min_depth: float = 0.
     valid_mask = torch.isfinite(observed_points).all(dim=1)
     valid_mask &= observed_points[:, 2].abs() > min_depth
     return observed_points[valid_mask]
+
+
+def resample_points(points: torch.Tensor, target_count: int, device: torch.device = None) -> torch.Tensor:
+    """exactly ``target_count`` of ``points`` [N, 3]: a random subset, or, when there are too few, a random subset of the
+    cloud repeated (so points come up more than once)"""
+    n_points = len(points)
+    if device is None:
+        device = points.device
+    if n_points < target_count:
+        points = points.repeat((target_count // n_points) + 1, 1)
+    indices = torch.randperm(len(points), device=device)[:target_count]
+    return points[indices]

@@ -996,6 +996,56 @@ int curobo_hip_pose_lm_step(curobo_hip_pose_lm_state *state, const void *workspa
                             int mode, float lambda_initial, float lambda_factor, float lambda_min, float lambda_max,
                             float rho_min, int minimum_valid_count, curobo_hip_stream_t stream);
 
+/* ---- point-to-plane ICP (curobo_amd/perception/pose_estimation/pose_detector.py; reference PoseDetector:
+ * perception/pose_estimation/pose_detector.py :172-375 and util.py :88-113, :245-330).  Every hypothesis of a stage advances
+ * together, one iteration in two launches; nothing accumulates with atomics, results are bit-identical from run to run.
+ *
+ * One state per hypothesis, on the DEVICE, 4-byte fields only.  T: rows 0..2 of the homogeneous transform, row major
+ * (R | t).  iterations: the reference's iter_idx + 1.  stopped: set by the step where the reference's loop breaks. */
+typedef struct curobo_hip_pose_icp_state {
+  float T[12];
+  float error;            /* written by the finalize step: mean nearest distance, +inf when nothing was found */
+  int32_t iterations, stopped, solver_failed;
+  int32_t n_valid;        /* of the last step that ran */
+  float x[6];             /* the last solve: rotation vector, translation */
+  int32_t reserved;
+} curobo_hip_pose_icp_state;
+#define CUROBO_HIP_POSE_ICP_STATE_WORDS 24
+
+/* The workspace: per hypothesis one row of CUROBO_HIP_POSE_WS_ROW words per workgroup of 64 mesh samples -- words 0..20 the
+ * upper triangle of sum w J J^T (row major), 21..26 sum w J b, 27 the sum of nearest distances over every sample (thresholded
+ * or not), 28 the valid count (int32), the rest 0. */
+int curobo_hip_pose_icp_ws_bytes(int n_hypotheses, int n_mesh, int64_t *out_bytes);
+
+/* For hypothesis h and mesh sample i: s = R_h p_i + t_h, n' = R_h n_i, the nearest of observed_points [n_observed, 3] by
+ * brute force (squared distances in fp32, ties to the lowest index), valid iff distance <= distance_threshold (infinity
+ * allowed: every sample valid); for a valid one b = (o - s) . n', w = 1 if |b| < huber_delta else huber_delta / (|b| + 1e-10)
+ * (1 when use_huber == 0), Jacobian row [s x n', n'].  One workspace row per workgroup (above).  Optional per-sample outputs
+ * [n_hypotheses, n_mesh]: out_index (-1 when invalid), out_distance.  honour_stopped != 0: the workgroups of a hypothesis
+ * whose state is marked stopped return at once and leave its rows as they are. */
+int curobo_hip_pose_icp_correspond(int32_t *out_index, float *out_distance, void *workspace, int64_t workspace_bytes,
+                                   const float *mesh_points, const float *mesh_normals, const float *observed_points,
+                                   const curobo_hip_pose_icp_state *state, float distance_threshold, int use_huber,
+                                   float huber_delta, int honour_stopped, int n_hypotheses, int n_mesh, int n_observed,
+                                   curobo_hip_stream_t stream);
+
+#define CUROBO_HIP_POSE_ICP_COARSE 0
+#define CUROBO_HIP_POSE_ICP_FINE 1
+#define CUROBO_HIP_POSE_ICP_FINALIZE 2
+/* One wavefront per hypothesis; its rows are added in workgroup order.  COARSE / FINE (a stopped hypothesis is left as it
+ * is): iterations += 1; fewer than 10 valid samples stop it with T unchanged; else (J^T W J + 1e-6 I) x = J^T W b by a 6 x 6
+ * Cholesky in fp32, q = (cos(theta/2), omega sin(theta/2) / max(theta, 1e-10)), T <- T_update T.  FINE stops BEFORE the
+ * update when |x[3..5]| < 1e-4.  Deviation from the reference, which falls back to lstsq when the factorisation fails: a
+ * pivot that is not positive or not finite stops the hypothesis with T unchanged and sets solver_failed.
+ * FINALIZE (stopped or not): error = sum of distances / n_mesh, +inf when no sample is valid; nothing else changes. */
+int curobo_hip_pose_icp_step(curobo_hip_pose_icp_state *state, const void *workspace, int64_t workspace_bytes,
+                             int n_hypotheses, int n_mesh, int mode, curobo_hip_stream_t stream);
+
+/* out_index[0] = arg-min of the states' errors: the lowest index wins a tie, a NaN never wins, nothing finite gives 0.
+ * Optional: out_error [1] the winning error, out_transform [12] the winner's T. */
+int curobo_hip_pose_icp_select(int32_t *out_index, float *out_error, float *out_transform,
+                               const curobo_hip_pose_icp_state *state, int n_hypotheses, curobo_hip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
