@@ -75,9 +75,34 @@ def robot_mask(mask_out: torch.Tensor, depth_out: torch.Tensor, depth: torch.Ten
 
 # ---------------------------------------------------------------------------------------------------- pose refinement
 import ctypes as _C  # noqa: E402
+from functools import partial  # noqa: E402
 
 POSE_LM_INIT, POSE_LM_UPDATE = 0, 1  # ``mode`` of ``curobo_hip_pose_lm_step``
 POSE_WS_ROW = 32                     # CUROBO_HIP_POSE_WS_ROW
+
+
+def _field_slice(struct, name: str) -> slice:
+    """the words of field ``name`` of a ctypes struct of 4-byte words"""
+    f = getattr(struct, name)
+    return slice(f.offset // 4, (f.offset + f.size) // 4)
+
+
+def pose_state_field(state: torch.Tensor, struct, name: str) -> torch.Tensor:
+    """field ``name`` of a state tensor whose last dimension holds the words of ``struct``: a view, int32 for a scalar c_int32 field"""
+    words = state[..., _field_slice(struct, name)]
+    return words.view(torch.int32) if dict(struct._fields_)[name] is _C.c_int32 else words
+
+
+def _ws_bytes(query, *counts: int) -> int:
+    nbytes = _C.c_int64(0)
+    check(query(*(int(c) for c in counts), _C.cast(_C.pointer(nbytes), _C.c_void_p)))
+    return int(nbytes.value)
+
+
+def _require_workspace(workspace: torch.Tensor, like: torch.Tensor, what: str, where: str = "state's device") -> int:
+    if not workspace.is_contiguous() or workspace.device != like.device:
+        raise ValueError(f"{what}: workspace must be a contiguous tensor on the {where}")
+    return int(workspace.numel() * workspace.element_size())
 
 
 class PoseLMState(_C.Structure):
@@ -91,21 +116,13 @@ class PoseLMState(_C.Structure):
 
 
 POSE_STATE_WORDS = _C.sizeof(PoseLMState) // 4
-#: int32 fields of the state (every other word is a float)
-POSE_STATE_INT_FIELDS = ("best_n_valid", "cand_n_valid", "accepted")
-
-
-def pose_state_slice(name: str) -> slice:
-    """the words of field ``name`` in a state tensor"""
-    f = getattr(PoseLMState, name)
-    return slice(f.offset // 4, (f.offset + f.size) // 4)
+POSE_STATE_INT_FIELDS = tuple(n for n, t in PoseLMState._fields_ if t is _C.c_int32)  #: the scalar c_int32 fields; every other word is a float
+pose_state_slice = partial(_field_slice, PoseLMState)  #: (name) -> the words of field ``name`` in a state tensor
 
 
 def pose_sdf_ws_bytes(n_points: int) -> int:
     """``curobo_hip_pose_sdf_ws_bytes``"""
-    nbytes = _C.c_int64(0)
-    check(load().curobo_hip_pose_sdf_ws_bytes(int(n_points), _C.cast(_C.pointer(nbytes), _C.c_void_p)))
-    return int(nbytes.value)
+    return _ws_bytes(load().curobo_hip_pose_sdf_ws_bytes, n_points)
 
 
 def pose_sdf_evaluate(workspace: torch.Tensor, points: torch.Tensor, position: torch.Tensor, quaternion: torch.Tensor, mesh_struct,
@@ -128,10 +145,8 @@ def pose_sdf_evaluate(workspace: torch.Tensor, points: torch.Tensor, position: t
         _require(t, name, dt, points)
         if t is not None and tuple(t.shape) != shape:
             raise ValueError(f"pose_sdf_evaluate: {name} must have shape {shape}, got {tuple(t.shape)}")
-    if not workspace.is_contiguous() or workspace.device != points.device:
-        raise ValueError("pose_sdf_evaluate: workspace must be a contiguous tensor on the points' device")
     check(load().curobo_hip_pose_sdf_evaluate(
-        ptr(out_distance), ptr(out_gradient), ptr(out_valid), ptr(workspace), int(workspace.numel() * workspace.element_size()),
+        ptr(out_distance), ptr(out_gradient), ptr(out_valid), ptr(workspace), _require_workspace(workspace, points, "pose_sdf_evaluate", "points' device"),
         ptr(points), ptr(position), ptr(quaternion), _C.addressof(mesh_struct), float(max_distance), float(distance_threshold),
         int(bool(use_huber)), float(huber_delta), n, current_stream(points)))
 
@@ -142,10 +157,8 @@ def pose_lm_step(state: torch.Tensor, workspace: torch.Tensor, n_points: int, mo
     _require(state, "state", torch.float32)
     if state.numel() != POSE_STATE_WORDS:
         raise ValueError(f"pose_lm_step: state must hold {POSE_STATE_WORDS} words, got {state.numel()}")
-    if not workspace.is_contiguous() or workspace.device != state.device:
-        raise ValueError("pose_lm_step: workspace must be a contiguous tensor on the state's device")
     check(load().curobo_hip_pose_lm_step(
-        ptr(state), ptr(workspace), int(workspace.numel() * workspace.element_size()), int(n_points), int(mode), float(lambda_initial),
+        ptr(state), ptr(workspace), _require_workspace(workspace, state, "pose_lm_step"), int(n_points), int(mode), float(lambda_initial),
         float(lambda_factor), float(lambda_min), float(lambda_max), float(rho_min), int(minimum_valid_count), current_stream(state)))
 
 
@@ -161,21 +174,13 @@ class PoseICPState(_C.Structure):
 
 
 POSE_ICP_STATE_WORDS = _C.sizeof(PoseICPState) // 4
-#: int32 fields of the state (every other word is a float)
-POSE_ICP_STATE_INT_FIELDS = ("iterations", "stopped", "solver_failed", "n_valid", "reserved")
-
-
-def pose_icp_state_slice(name: str) -> slice:
-    """the words of field ``name`` in each row of a state tensor"""
-    f = getattr(PoseICPState, name)
-    return slice(f.offset // 4, (f.offset + f.size) // 4)
+POSE_ICP_STATE_INT_FIELDS = tuple(n for n, t in PoseICPState._fields_ if t is _C.c_int32)  #: the scalar c_int32 fields; every other word is a float
+pose_icp_state_slice = partial(_field_slice, PoseICPState)  #: (name) -> the words of field ``name`` in each row of a state tensor
 
 
 def pose_icp_ws_bytes(n_hypotheses: int, n_mesh: int) -> int:
     """``curobo_hip_pose_icp_ws_bytes``"""
-    nbytes = _C.c_int64(0)
-    check(load().curobo_hip_pose_icp_ws_bytes(int(n_hypotheses), int(n_mesh), _C.cast(_C.pointer(nbytes), _C.c_void_p)))
-    return int(nbytes.value)
+    return _ws_bytes(load().curobo_hip_pose_icp_ws_bytes, n_hypotheses, n_mesh)
 
 
 def _require_icp_state(state: torch.Tensor, what: str) -> int:
@@ -183,12 +188,6 @@ def _require_icp_state(state: torch.Tensor, what: str) -> int:
     if state.dim() != 2 or state.shape[1] != POSE_ICP_STATE_WORDS:
         raise ValueError(f"{what}: state must be (H, {POSE_ICP_STATE_WORDS}), got {tuple(state.shape)}")
     return int(state.shape[0])
-
-
-def _require_workspace(workspace: torch.Tensor, like: torch.Tensor, what: str) -> int:
-    if not workspace.is_contiguous() or workspace.device != like.device:
-        raise ValueError(f"{what}: workspace must be a contiguous tensor on the state's device")
-    return int(workspace.numel() * workspace.element_size())
 
 
 def pose_icp_correspond(workspace: torch.Tensor, mesh_points: torch.Tensor, mesh_normals: torch.Tensor, observed_points: torch.Tensor,

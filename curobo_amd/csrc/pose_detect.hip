@@ -11,19 +11,14 @@
 // (compute_predicted_reduction :28-48, trust_region_update :53-175, solve_lm_step :180-202) and
 // sdf_pose_detector.py:_setup_refinement / _refine_iteration (:266-399), which sequences them with ~40 torch launches.
 //
-// Determinism.  Nothing here adds with atomics: a wavefront sums by the DPP ladder (common.hpp::wave_sum), the four
-// wavefronts of a workgroup meet in LDS and are added in wavefront order, every workgroup stores its own row, and the step
-// kernel adds the rows in workgroup order.  Every row is written by every evaluation, so nothing has to be zeroed between
-// evaluations: a captured block of iterations is a plain chain of kernel nodes.
-#include "common.hpp"
+// The row of partial sums, its sum in workgroup order, the Cholesky solve and the rules that make all of it deterministic:
+// pose_device.hpp.  Here a workgroup is four wavefronts: each forms its row, they meet in LDS and are added in wavefront order.
 #include "mesh_device.hpp"
+#include "pose_device.hpp"
 
 namespace curobo_hip {
 
 constexpr int kPoseThreads = 256, kPoseWaves = kPoseThreads / kWave;
-constexpr int kPoseRow = CUROBO_HIP_POSE_WS_ROW;  // words per workgroup row: 21 + 6 + 1 floats, the count (int32), padding
-constexpr int kPoseSums = 28, kPoseCount = 28;
-static_assert(kPoseRow >= kPoseCount + 1, "a row holds 28 sums and the count");
 
 struct PoseEvalArgs {
   const float *points, *position, *quaternion;
@@ -77,44 +72,24 @@ __global__ __launch_bounds__(kPoseThreads) void pose_sdf_evaluate_kernel(PoseEva
     if (a.out_gradient) { a.out_gradient[(size_t)i * 3] = gw.x; a.out_gradient[(size_t)i * 3 + 1] = gw.y; a.out_gradient[(size_t)i * 3 + 2] = gw.z; }
     if (a.out_valid) a.out_valid[i] = valid ? 1 : 0;
   }
-  // ---- the workgroup's row: upper triangle of J^T J (row major), J^T r, sum r^2, count
+  // ---- the workgroup's row: J^T J, J^T r, sum r^2, count
   const float j[6] = {j0, j1, j2, j3, j4, j5};
   const int wave = tid / kWave, lane = tid % kWave;
-  int k = 0;
-#pragma unroll
-  for (int u = 0; u < 6; u++) {
-#pragma unroll
-    for (int v = u; v < 6; v++) {
-      const float s = wave_sum(j[u] * j[v]);
-      if (lane == 0) part[wave][k] = s;
-      k++;
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < 6; u++) {
-    const float s = wave_sum(j[u] * r);
-    if (lane == 0) part[wave][21 + u] = s;
-  }
-  {
-    const float s = wave_sum(r * r);
-    const int c = __popcll(__ballot(valid));
-    if (lane == 0) { part[wave][27] = s; part[wave][kPoseCount] = __int_as_float(c); }
-  }
+  const float word = pose_row_word(j, j, r, r * r, valid, lane);
+  if (lane < kPoseRow) part[wave][lane] = word;
   __syncthreads();
   if (tid < kPoseRow) {
     float *row = a.ws + (size_t)blockIdx.x * kPoseRow;
-    if (tid < kPoseSums) {
+    if (tid == kPoseCount) {
+      int c = 0;
+#pragma unroll
+      for (int w = 0; w < kPoseWaves; w++) c += __float_as_int(part[w][tid]);
+      row[tid] = __int_as_float(c);
+    } else {  // (the words after the count are zeros, and stay zeros)
       float s = part[0][tid];
 #pragma unroll
       for (int w = 1; w < kPoseWaves; w++) s += part[w][tid];
       row[tid] = s;
-    } else if (tid == kPoseCount) {
-      int c = 0;
-#pragma unroll
-      for (int w = 0; w < kPoseWaves; w++) c += __float_as_int(part[w][kPoseCount]);
-      row[tid] = __int_as_float(c);
-    } else {
-      row[tid] = 0.0f;
     }
   }
 }
@@ -128,63 +103,15 @@ struct PoseStepArgs {
   int minimum_valid_count;
 };
 
-// quotient and root rounded once (the library is built with the 2.5 ulp hardware forms; the damping must follow the
-// reference's lambda / factor bit for bit, and a double quotient of two floats rounds to the correctly rounded float)
-__device__ __forceinline__ float div_rn(float x, float y) { return (float)((double)x / (double)y); }
-__device__ __forceinline__ float sqrt_rn(float x) { return (float)sqrt((double)x); }
-
-// (J^T J + lambda I) delta = -J^T r by Cholesky, fp32 (solve_lm_step).  False on a pivot that is not positive.
-__device__ __forceinline__ bool pose_solve_lm(const float *JtJ, const float *Jtr, float lambda, float *delta) {
-  float L[6][6];
-  for (int i = 0; i < 6; i++) {
-    for (int c = 0; c <= i; c++) {
-      float acc = JtJ[i * 6 + c] + (i == c ? lambda : 0.0f);
-      for (int k = 0; k < c; k++) acc -= L[i][k] * L[c][k];
-      if (i == c) {
-        if (!(acc > 0.0f)) return false;
-        L[i][i] = sqrt_rn(acc);
-      } else {
-        L[i][c] = div_rn(acc, L[c][c]);
-      }
-    }
-  }
-  float y[6];
-  for (int i = 0; i < 6; i++) {
-    float acc = -Jtr[i];
-    for (int k = 0; k < i; k++) acc -= L[i][k] * y[k];
-    y[i] = div_rn(acc, L[i][i]);
-  }
-  for (int i = 5; i >= 0; i--) {
-    float acc = y[i];
-    for (int k = i + 1; k < 6; k++) acc -= L[k][i] * delta[k];
-    delta[i] = div_rn(acc, L[i][i]);
-  }
-  return true;
-}
-
 __global__ __launch_bounds__(kWave) void pose_lm_step_kernel(PoseStepArgs a) {
   __shared__ float red[kPoseRow];
   const int lane = threadIdx.x;
-  // ---- the evaluation's rows, added in workgroup order: lane k owns word k
-  if (lane < kPoseSums) {
-    float s = 0.0f;
-    for (int b = 0; b < a.n_rows; b++) s += a.ws[(size_t)b * kPoseRow + lane];
-    red[lane] = s;
-  } else if (lane == kPoseCount) {
-    int c = 0;
-    for (int b = 0; b < a.n_rows; b++) c += __float_as_int(a.ws[(size_t)b * kPoseRow + lane]);
-    red[lane] = __int_as_float(c);
-  }
-  __syncthreads();
+  pose_sum_rows(red, a.ws, a.n_rows, lane);
   if (lane != 0) return;
   curobo_hip_pose_lm_state &s = *a.s;
   float cJ[36], cr[6];
-  {
-    int k = 0;
-    for (int u = 0; u < 6; u++)
-      for (int v = u; v < 6; v++) { cJ[u * 6 + v] = red[k]; cJ[v * 6 + u] = red[k]; k++; }
-    for (int u = 0; u < 6; u++) cr[u] = red[21 + u];
-  }
+  pose_unpack_symmetric(red, cJ);
+  for (int u = 0; u < 6; u++) cr[u] = red[21 + u];
   const float sum_sq = red[27];
   const int n_valid = __float_as_int(red[kPoseCount]);
   const float cand_rms = sqrt_rn(div_rn(sum_sq, (float)n_valid + 1e-8f));
@@ -222,7 +149,7 @@ __global__ __launch_bounds__(kWave) void pose_lm_step_kernel(PoseStepArgs a) {
   // ---- the next candidate, from the best state (cJ / cr hold it now)
   float d[6];
   const float nan = __builtin_nanf("");
-  if (!pose_solve_lm(cJ, cr, lambda, d))
+  if (!pose_solve6<kPoseSolveLM>(cJ, lambda, cr, d))  // (J^T J + lambda I) delta = -J^T r (solve_lm_step)
     for (int k = 0; k < 6; k++) d[k] = nan;  // the candidate finds no point, is rejected, and lambda grows
   float pred = 0.0f, quad = 0.0f;  // compute_predicted_reduction
   for (int u = 0; u < 6; u++) {
@@ -255,12 +182,17 @@ __global__ __launch_bounds__(kWave) void pose_lm_step_kernel(PoseStepArgs a) {
 using namespace curobo_hip;
 
 static int pose_rows(int n_points) { return ceil_div(n_points, kPoseThreads); }
+static int check_sdf_workspace(const void *workspace, int64_t workspace_bytes, int n_points, const char *what) {
+  char counted[32];
+  snprintf(counted, sizeof counted, "%d points", n_points);
+  return check_pose_workspace(workspace, workspace_bytes, pose_rows(n_points), what, counted, "curobo_hip_pose_sdf_ws_bytes");
+}
 
 CUROBO_EXPORT int curobo_hip_pose_sdf_ws_bytes(int n_points, int64_t *out_bytes) {
   const char *what = "pose_sdf_ws_bytes";
   CUROBO_REQUIRE(out_bytes, "%s: out_bytes must not be null", what);
   CUROBO_REQUIRE(n_points > 0, "%s: n_points must be positive, got %d", what, n_points);
-  *out_bytes = (int64_t)pose_rows(n_points) * kPoseRow * (int64_t)sizeof(float);
+  *out_bytes = pose_ws_bytes(pose_rows(n_points));
   return CUROBO_HIP_OK;
 }
 
@@ -286,10 +218,7 @@ CUROBO_EXPORT int curobo_hip_pose_sdf_evaluate(float *out_distance, float *out_g
   if (int rc = check_pose_mesh(mesh, what)) return rc;
   CUROBO_REQUIRE(max_distance > 0.0f && distance_threshold > 0.0f, "%s: max_distance and distance_threshold must be positive", what);
   CUROBO_REQUIRE(use_huber == 0 || huber_delta > 0.0f, "%s: huber_delta must be positive, got %g", what, (double)huber_delta);
-  const int64_t need = (int64_t)pose_rows(n_points) * kPoseRow * (int64_t)sizeof(float);
-  CUROBO_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes, %d points need %lld (curobo_hip_pose_sdf_ws_bytes)", what,
-                 (long long)workspace_bytes, n_points, (long long)need);
-  CUROBO_REQUIRE(((uintptr_t)workspace & 3) == 0, "%s: workspace must be 4-byte aligned", what);
+  if (int rc = check_sdf_workspace(workspace, workspace_bytes, n_points, what)) return rc;
   PoseEvalArgs a{};
   a.points = points, a.position = position, a.quaternion = quaternion, a.mesh = *mesh;
   a.max_distance = max_distance, a.distance_threshold = distance_threshold, a.huber_delta = huber_delta;
@@ -310,9 +239,7 @@ CUROBO_EXPORT int curobo_hip_pose_lm_step(curobo_hip_pose_lm_state *state, const
                  mode);
   CUROBO_REQUIRE(lambda_factor > 0.0f && lambda_min > 0.0f && lambda_max >= lambda_min && lambda_initial > 0.0f,
                  "%s: lambda_initial, lambda_factor and lambda_min must be positive and lambda_max >= lambda_min", what);
-  const int64_t need = (int64_t)pose_rows(n_points) * kPoseRow * (int64_t)sizeof(float);
-  CUROBO_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes, %d points need %lld (curobo_hip_pose_sdf_ws_bytes)", what,
-                 (long long)workspace_bytes, n_points, (long long)need);
+  if (int rc = check_sdf_workspace(workspace, workspace_bytes, n_points, what)) return rc;
   PoseStepArgs a{};
   a.s = state, a.ws = (const float *)workspace, a.n_rows = pose_rows(n_points), a.mode = mode;
   a.lambda_initial = lambda_initial, a.lambda_factor = lambda_factor, a.lambda_min = lambda_min, a.lambda_max = lambda_max;

@@ -12,12 +12,11 @@
 // hypotheses one after the other with about fifteen torch launches per iteration, and util.py (find_nearest_neighbors :88-113,
 // compute_pose_point_to_plane_cholesky :245-330, omega_to_quaternion :49-66).
 //
-// Determinism: the rules of pose_detect.hip.  No float atomics; a workgroup stores one row, the step adds rows in workgroup
-// order; every row of a running hypothesis is written by every launch, so nothing is zeroed between iterations and a stage
-// is a plain chain of kernel nodes.  The nearest point is the minimum of (squared distance, index) in that order, which does
+// The row of partial sums, its sum in workgroup order, the Cholesky solve and the rules that make all of it deterministic:
+// pose_device.hpp.  The nearest point is the minimum of (squared distance, index) in that order, which does
 // not depend on how the observed range is shared out: 64 samples per workgroup, each wavefront scanning a quarter of every
 // staged tile, the four candidates met in LDS.
-#include "common.hpp"
+#include "pose_device.hpp"
 
 namespace curobo_hip {
 
@@ -25,11 +24,8 @@ constexpr int kIcpThreads = 256, kIcpWaves = kIcpThreads / kWave;
 constexpr int kIcpSamples = kWave;                   // mesh samples per workgroup: lane l of every wavefront owns sample l
 constexpr int kIcpTile = 1024;                       // observed points staged per pass (16 KB of LDS)
 constexpr int kIcpSlice = kIcpTile / kIcpWaves;      // of which one wavefront scans this many
-constexpr int kIcpRow = CUROBO_HIP_POSE_WS_ROW;      // 21 + 6 + 1 floats, the count (int32), padding
-constexpr int kIcpSums = 28, kIcpCount = 28;
 constexpr int kIcpMinValid = 10;                     // pose_detector.py:237 / :331
 constexpr float kIcpDamping = 1e-6f;                 // util.py:252
-static_assert(kIcpRow >= kIcpCount + 1 && kIcpRow <= kWave, "a row holds 28 sums and the count, one word per lane");
 static_assert(sizeof(curobo_hip_pose_icp_state) == 4 * CUROBO_HIP_POSE_ICP_STATE_WORDS, "state layout");
 
 struct IcpCorrespondArgs {
@@ -41,9 +37,6 @@ struct IcpCorrespondArgs {
   float *out_distance;
   float *ws;
 };
-
-__device__ __forceinline__ float icp_sqrt_rn(float x) { return (float)sqrt((double)x); }
-__device__ __forceinline__ float icp_div_rn(float x, float y) { return (float)((double)x / (double)y); }
 
 __global__ __launch_bounds__(kIcpThreads) void pose_icp_correspond_kernel(IcpCorrespondArgs a) {
   __shared__ float4 tile[kIcpTile];
@@ -96,7 +89,7 @@ __global__ __launch_bounds__(kIcpThreads) void pose_icp_correspond_kernel(IcpCor
   const bool found = live && best_j >= 0;
   bool valid = false;
   if (found) {
-    dist = icp_sqrt_rn(best);
+    dist = sqrt_rn(best);
     valid = dist <= a.distance_threshold;
     if (valid) {
       const f3 n = make_f3(a.mesh_normals[(size_t)i * 3], a.mesh_normals[(size_t)i * 3 + 1], a.mesh_normals[(size_t)i * 3 + 2]);
@@ -115,30 +108,10 @@ __global__ __launch_bounds__(kIcpThreads) void pose_icp_correspond_kernel(IcpCor
     if (a.out_index) a.out_index[at] = valid ? best_j : -1;
     if (a.out_distance) a.out_distance[at] = dist;
   }
-  // ---- the workgroup's row: lane k keeps word k
-  float mine = 0.0f;
-  int k = 0;
-#pragma unroll
-  for (int u = 0; u < 6; u++) {
-#pragma unroll
-    for (int v = u; v < 6; v++) {
-      const float sum = wave_sum(wgt * j6[u] * j6[v]);
-      if (lane == k) mine = sum;
-      k++;
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < 6; u++) {
-    const float sum = wave_sum(wgt * j6[u] * b);
-    if (lane == 21 + u) mine = sum;
-  }
-  {
-    const float sum = wave_sum(dist);
-    if (lane == 27) mine = sum;
-    const int c = __popcll(__ballot(valid));
-    if (lane == kIcpCount) mine = __int_as_float(c);
-  }
-  if (lane < kIcpRow) a.ws[((size_t)h * a.rows_per_hypothesis + blockIdx.x) * kIcpRow + lane] = mine;
+  // ---- the workgroup's row: J^T W J, J^T W b, the sum of nearest distances, count
+  const float wj6[6] = {wgt * j6[0], wgt * j6[1], wgt * j6[2], wgt * j6[3], wgt * j6[4], wgt * j6[5]};
+  const float mine = pose_row_word(wj6, j6, b, dist, valid, lane);
+  if (lane < kPoseRow) a.ws[((size_t)h * a.rows_per_hypothesis + blockIdx.x) * kPoseRow + lane] = mine;
 }
 
 // ---------------------------------------------------------------------------------------------------- the step
@@ -148,75 +121,30 @@ struct IcpStepArgs {
   int rows_per_hypothesis, n_mesh, mode;
 };
 
-// (J^T W J + damping I) x = J^T W b by Cholesky in fp32, quotients and roots rounded once as in pose_detect.hip.  False
-// on a pivot that is not positive or not finite.
-__device__ __forceinline__ bool icp_solve(const float *A, const float *rhs, float *x) {
-  float L[6][6];
-  for (int i = 0; i < 6; i++) {
-    for (int c = 0; c <= i; c++) {
-      float acc = A[i * 6 + c] + (i == c ? kIcpDamping : 0.0f);
-      for (int k = 0; k < c; k++) acc -= L[i][k] * L[c][k];
-      if (i == c) {
-        if (!(acc > 0.0f) || !isfinite(acc)) return false;
-        L[i][i] = icp_sqrt_rn(acc);
-      } else {
-        L[i][c] = icp_div_rn(acc, L[c][c]);
-      }
-    }
-  }
-  float y[6];
-  for (int i = 0; i < 6; i++) {
-    float acc = rhs[i];
-    for (int k = 0; k < i; k++) acc -= L[i][k] * y[k];
-    y[i] = icp_div_rn(acc, L[i][i]);
-  }
-  for (int i = 5; i >= 0; i--) {
-    float acc = y[i];
-    for (int k = i + 1; k < 6; k++) acc -= L[k][i] * x[k];
-    x[i] = icp_div_rn(acc, L[i][i]);
-  }
-  for (int i = 0; i < 6; i++)
-    if (!isfinite(x[i])) return false;
-  return true;
-}
-
 __global__ __launch_bounds__(kWave) void pose_icp_step_kernel(IcpStepArgs a) {
-  __shared__ float red[kIcpRow];
+  __shared__ float red[kPoseRow];
   const int h = blockIdx.x, lane = threadIdx.x;
   curobo_hip_pose_icp_state &s = a.state[h];
   if (a.mode != CUROBO_HIP_POSE_ICP_FINALIZE && s.stopped != 0) return;
-  const float *rows = a.ws + (size_t)h * a.rows_per_hypothesis * kIcpRow;
-  if (lane < kIcpSums) {
-    float sum = 0.0f;
-    for (int r = 0; r < a.rows_per_hypothesis; r++) sum += rows[(size_t)r * kIcpRow + lane];
-    red[lane] = sum;
-  } else if (lane == kIcpCount) {
-    int c = 0;
-    for (int r = 0; r < a.rows_per_hypothesis; r++) c += __float_as_int(rows[(size_t)r * kIcpRow + lane]);
-    red[lane] = __int_as_float(c);
-  }
-  __syncthreads();
+  pose_sum_rows(red, a.ws + (size_t)h * a.rows_per_hypothesis * kPoseRow, a.rows_per_hypothesis, lane);
   if (lane != 0) return;
-  const int n_valid = __float_as_int(red[kIcpCount]);
+  const int n_valid = __float_as_int(red[kPoseCount]);
   if (a.mode == CUROBO_HIP_POSE_ICP_FINALIZE) {  // errors.mean() over every sample (pose_detector.py:265-274)
-    s.error = n_valid > 0 ? icp_div_rn(red[27], (float)a.n_mesh) : __builtin_inff();
+    s.error = n_valid > 0 ? div_rn(red[27], (float)a.n_mesh) : __builtin_inff();
     return;
   }
   s.iterations += 1;  // iter_idx + 1 of the iteration now running
   s.n_valid = n_valid;
   if (n_valid < kIcpMinValid) { s.stopped = 1; return; }
   float A[36], x[6];
-  {
-    int k = 0;
-    for (int u = 0; u < 6; u++)
-      for (int v = u; v < 6; v++) { A[u * 6 + v] = red[k]; A[v * 6 + u] = red[k]; k++; }
-  }
-  if (!icp_solve(A, red + 21, x)) { s.stopped = 1; s.solver_failed = 1; return; }
+  pose_unpack_symmetric(red, A);
+  // (J^T W J + damping I) x = J^T W b
+  if (!pose_solve6<kPoseSolveICP>(A, kIcpDamping, red + 21, x)) { s.stopped = 1; s.solver_failed = 1; return; }
   for (int k = 0; k < 6; k++) s.x[k] = x[k];
-  if (a.mode == CUROBO_HIP_POSE_ICP_FINE && icp_sqrt_rn(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]) < 1e-4f) { s.stopped = 1; return; }
+  if (a.mode == CUROBO_HIP_POSE_ICP_FINE && sqrt_rn(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]) < 1e-4f) { s.stopped = 1; return; }
   // omega_to_quaternion, then the quaternion's matrix
-  const float theta = icp_sqrt_rn(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-  const float coeff = icp_div_rn(sinf(0.5f * theta), fmaxf(theta, 1e-10f));
+  const float theta = sqrt_rn(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+  const float coeff = div_rn(sinf(0.5f * theta), fmaxf(theta, 1e-10f));
   const float qw = cosf(0.5f * theta), qx = x[0] * coeff, qy = x[1] * coeff, qz = x[2] * coeff;
   const float U[9] = {1.0f - 2.0f * (qy * qy + qz * qz), 2.0f * (qx * qy - qz * qw), 2.0f * (qx * qz + qy * qw),
                       2.0f * (qx * qy + qz * qw), 1.0f - 2.0f * (qx * qx + qz * qz), 2.0f * (qy * qz - qx * qw),
@@ -264,9 +192,7 @@ __global__ __launch_bounds__(kWave) void pose_icp_select_kernel(IcpSelectArgs a)
 using namespace curobo_hip;
 
 static int icp_rows(int n_mesh) { return ceil_div(n_mesh, kIcpSamples); }
-static int64_t icp_ws_need(int n_hypotheses, int n_mesh) {
-  return (int64_t)n_hypotheses * icp_rows(n_mesh) * kIcpRow * (int64_t)sizeof(float);
-}
+static int64_t icp_ws_rows(int n_hypotheses, int n_mesh) { return (int64_t)n_hypotheses * icp_rows(n_mesh); }
 
 static int check_icp_counts(int n_hypotheses, int n_mesh, const char *what) {
   CUROBO_REQUIRE(n_hypotheses > 0 && n_hypotheses <= 65535, "%s: n_hypotheses must be in 1..65535, got %d", what, n_hypotheses);
@@ -278,16 +204,14 @@ CUROBO_EXPORT int curobo_hip_pose_icp_ws_bytes(int n_hypotheses, int n_mesh, int
   const char *what = "pose_icp_ws_bytes";
   CUROBO_REQUIRE(out_bytes, "%s: out_bytes must not be null", what);
   if (int rc = check_icp_counts(n_hypotheses, n_mesh, what)) return rc;
-  *out_bytes = icp_ws_need(n_hypotheses, n_mesh);
+  *out_bytes = pose_ws_bytes(icp_ws_rows(n_hypotheses, n_mesh));
   return CUROBO_HIP_OK;
 }
 
 static int check_icp_workspace(const void *workspace, int64_t workspace_bytes, int n_hypotheses, int n_mesh, const char *what) {
-  const int64_t need = icp_ws_need(n_hypotheses, n_mesh);
-  CUROBO_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes, %d hypotheses of %d samples need %lld (curobo_hip_pose_icp_ws_bytes)",
-                 what, (long long)workspace_bytes, n_hypotheses, n_mesh, (long long)need);
-  CUROBO_REQUIRE(((uintptr_t)workspace & 3) == 0, "%s: workspace must be 4-byte aligned", what);
-  return CUROBO_HIP_OK;
+  char counted[64];
+  snprintf(counted, sizeof counted, "%d hypotheses of %d samples", n_hypotheses, n_mesh);
+  return check_pose_workspace(workspace, workspace_bytes, icp_ws_rows(n_hypotheses, n_mesh), what, counted, "curobo_hip_pose_icp_ws_bytes");
 }
 
 CUROBO_EXPORT int curobo_hip_pose_icp_correspond(int32_t *out_index, float *out_distance, void *workspace, int64_t workspace_bytes,

@@ -42,8 +42,7 @@ class _Run:
         self.graph: Optional[torch.cuda.CUDAGraph] = None
 
     def field(self, name: str) -> torch.Tensor:
-        words = self.state[B.pose_state_slice(name)]
-        return words.view(torch.int32) if name in B.POSE_STATE_INT_FIELDS else words
+        return B.pose_state_field(self.state, B.PoseLMState, name)
 
 
 class SDFPoseDetector:

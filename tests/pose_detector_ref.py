@@ -8,8 +8,8 @@ Shared by tests/test_oracle_pose_detector.py (the reference's recorded fp32 outp
 and tests/randomised/fuzz_pose_detector.py (the HIP kernels against this)."""
 
 import numpy as np
+from pose_rows import EPS  # noqa: F401  (shared with the ICP detector's oracle)
 
-EPS = 2.0 ** -24
 BAND = 1e-6
 #: C of the per-point bounds (docs/ORACLE_PINS.md): distance within C 2^-24 S, gradient within 2 C 2^-24 S / dist + 4 2^-24.
 #: The reference's own fp32 output on the golden cases needs 372.7 (case lsolid_n257: the gradient of a point 2.3 mm from an

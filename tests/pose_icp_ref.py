@@ -23,8 +23,8 @@ The bounds (docs/ORACLE_PINS.md).
 """
 
 import numpy as np
+from pose_rows import EPS, row_bound, unpack_row  # noqa: F401  (the row's rules, shared with the LM detector's oracle)
 
-EPS = 2.0 ** -24
 BAND = 1e-6
 DAMPING = 1e-6
 MINIMUM_VALID_COUNT = 10
@@ -101,19 +101,6 @@ def correspond(mesh_points, mesh_normals, observed, T, distance_threshold=np.inf
 
 def distance_bound(scale, dist):
     return EPS * (18.0 * scale + 8.0 * np.asarray(dist))
-
-
-def row_bound(n_terms, row_abs, roundings):
-    return (n_terms + roundings) * EPS * np.asarray(row_abs)
-
-
-def unpack_row(row):
-    """[>= 27] -> (J^T J [6, 6], J^T b [6]) in float64"""
-    row = np.asarray(row, np.float64)
-    A = np.zeros((6, 6))
-    A[np.triu_indices(6)] = row[:21]
-    A = A + np.triu(A, 1).T
-    return A, row[21:27]
 
 
 def solve(JtJ, Jtb):

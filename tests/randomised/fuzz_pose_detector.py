@@ -15,6 +15,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.dirname(HERE), os.path.dirname(os.path.dirname(HERE))]
 import pose_detector_ref as R  # noqa: E402
+import pose_rows  # noqa: E402
 
 
 def hip_evaluate(points, position, quaternion, vertices, faces, max_distance, threshold, use_huber, delta, device="cuda:0"):
@@ -35,16 +36,8 @@ def hip_evaluate(points, position, quaternion, vertices, faces, max_distance, th
 
 def reduce_rows(rows):
     """(JtJ [6, 6], Jtr, sum_sq, n) of the workspace rows, the rows added in fp32 in order as the step kernel adds them"""
-    acc = np.zeros(28, np.float32)
-    for r in rows:
-        acc = (acc + r[:28]).astype(np.float32)
-    JtJ = np.zeros((6, 6))
-    k = 0
-    for u in range(6):
-        for v in range(u, 6):
-            JtJ[u, v] = JtJ[v, u] = acc[k]
-            k += 1
-    return JtJ, acc[21:27].astype(np.float64), float(acc[27]), int(rows[:, 28].view(np.int32).sum())
+    acc, n = pose_rows.reduce_rows(rows)
+    return (*pose_rows.unpack_row(acc), float(acc[27]), n)
 
 
 def check_case(name, points, position, quaternion, vertices, faces, max_distance, threshold, use_huber, delta, say=print):
@@ -73,10 +66,10 @@ def check_case(name, points, position, quaternion, vertices, faces, max_distance
     J, r, v = R.jacobian_from_outputs(points, dist, grad, valid, use_huber, delta)
     s = R.sums_of(J, r, v)
     JtJ, Jtr, ssq, cnt = reduce_rows(rows)
-    k = (len(r) + 8) * R.EPS
     # (the kernel forms each Jacobian entry in fp32 before it multiplies: 4 roundings per entry on top of the summation)
-    worst = max(float((np.abs(JtJ - s["JtJ"]) / (k * s["abs_JtJ"] + 1e-45)).max()), float((np.abs(Jtr - s["Jtr"]) / (k * s["abs_Jtr"] + 1e-45)).max()),
-                abs(ssq - s["sum_sq"]) / (k * s["abs_sum_sq"] + 1e-45))
+    bound = lambda term: pose_rows.row_bound(len(r), s[term], 8) + 1e-45  # noqa: E731
+    worst = max(float((np.abs(JtJ - s["JtJ"]) / bound("abs_JtJ")).max()), float((np.abs(Jtr - s["Jtr"]) / bound("abs_Jtr")).max()),
+                abs(ssq - s["sum_sq"]) / bound("abs_sum_sq"))
     if worst > 1:
         bad.append(f"reduced sums at {worst:.3f} of the bound")
     if cnt != s["n"]:

@@ -17,6 +17,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.dirname(HERE), os.path.dirname(os.path.dirname(HERE))]
 import pose_icp_ref as R  # noqa: E402
+from pose_rows import reduce_rows  # noqa: E402
 
 DEV = "cuda:0"
 #: cond(J^T J + 1e-6 I) 2^-24 from which a random system counts as singular in fp32: the K bound is a first-order one
@@ -42,8 +43,7 @@ def make_state(T, stopped=None):
 def state_field(state, name):
     from curobo_amd.backends import perception as P
 
-    a = state.cpu().numpy()[:, P.pose_icp_state_slice(name)]
-    return a.view(np.int32) if name in P.POSE_ICP_STATE_INT_FIELDS else a
+    return P.pose_state_field(state, P.PoseICPState, name).cpu().numpy()
 
 
 def hip_correspond(mesh_points, mesh_normals, observed, T, threshold, use_huber, delta, stopped=None, honour_stopped=True, ws_fill=float("nan")):
@@ -59,14 +59,6 @@ def hip_correspond(mesh_points, mesh_normals, observed, T, threshold, use_huber,
                           honour_stopped=honour_stopped, out_index=idx, out_distance=dist)
     torch.cuda.synchronize()
     return idx.cpu().numpy(), dist.cpu().numpy(), ws.cpu().numpy().reshape(h, -1, P.POSE_WS_ROW), state, ws
-
-
-def reduce_rows(rows):
-    """([28] sums, count) of one hypothesis's rows, added in fp32 in workgroup order as the step kernel adds them"""
-    acc = np.zeros(28, np.float32)
-    for r in rows:
-        acc = (acc + r[:28]).astype(np.float32)
-    return acc, int(rows[:, 28].view(np.int32).sum())
 
 
 def check_case(name, mesh_points, mesh_normals, observed, T, threshold, use_huber, delta, say=print, step=True):
