@@ -1,0 +1,168 @@
+"""HIP backend of ``curobo_amd.perception.mapper`` (``csrc/mapper.hip``).  Same conventions as the other backends:
+pre-allocated tensors in, mutated in place, current stream."""
+
+from __future__ import annotations
+
+import ctypes as _C
+import math
+from typing import Sequence
+
+import torch
+
+from .._lib import check, current_stream, load, ptr
+from .perception import _require
+
+ESDF_MAX_AXIS = 1024  #: sites pack 10 bits per axis
+
+
+class MapperParams(_C.Structure):
+    """``curobo_hip_mapper_params`` (see include/curobo_hip.h): read on the host at every launch"""
+
+    _fields_ = [("grid_w", _C.c_int32), ("grid_h", _C.c_int32), ("grid_d", _C.c_int32), ("block_size", _C.c_int32),
+                ("nbx", _C.c_int32), ("nby", _C.c_int32), ("nbz", _C.c_int32), ("num_samples", _C.c_int32),
+                ("origin", _C.c_float * 3), ("voxel_size", _C.c_float), ("truncation_distance", _C.c_float),
+                ("depth_min", _C.c_float), ("depth_max", _C.c_float), ("minimum_tsdf_weight", _C.c_float), ("step_size", _C.c_float)]
+
+    @property
+    def n_blocks(self) -> int:
+        return int(self.nbx) * int(self.nby) * int(self.nbz)
+
+    @property
+    def block_voxels(self) -> int:
+        return int(self.block_size) ** 3
+
+
+def marking_step(block_size: int, voxel_size: float, truncation_distance: float):
+    """(step_size, num_samples) of the marking stage (builder_camera_integrate.py: STEP_SIZE, NUM_SAMPLES)"""
+    step = block_size * voxel_size / 1.42
+    return step, int(math.ceil(2.0 * truncation_distance / step)) + 1
+
+
+def make_params(grid_shape_zyx: Sequence[int], block_size: int, origin: Sequence[float], voxel_size: float, truncation_distance: float,
+                depth_min: float, depth_max: float, minimum_tsdf_weight: float) -> MapperParams:
+    """``grid_shape_zyx``: (nz, ny, nx) voxels, as ``MapperCfg.grid_shape``"""
+    nz, ny, nx = (int(v) for v in grid_shape_zyx)
+    bs = int(block_size)
+    step, num_samples = marking_step(bs, voxel_size, truncation_distance)
+    p = MapperParams(grid_w=nx, grid_h=ny, grid_d=nz, block_size=bs, nbx=-(-nx // bs), nby=-(-ny // bs), nbz=-(-nz // bs),
+                     num_samples=num_samples, voxel_size=voxel_size, truncation_distance=truncation_distance, depth_min=depth_min,
+                     depth_max=depth_max, minimum_tsdf_weight=minimum_tsdf_weight, step_size=step)
+    p.origin[:] = [float(v) for v in origin]
+    return p
+
+
+def mask_bytes(params: MapperParams) -> int:
+    """length of a block mask: one byte per block, rounded up to whole 4-byte words (``mapper_clear_mask`` writes words)"""
+    return -(-params.n_blocks // 4) * 4
+
+
+def _require_map(params: MapperParams, what: str, block_data=None, like=None, **masks) -> None:
+    if block_data is not None:
+        _require(block_data, "block_data", torch.float16, like)
+        if tuple(block_data.shape) != (params.n_blocks, params.block_voxels, 2):
+            raise ValueError(f"{what}: block_data must have shape {(params.n_blocks, params.block_voxels, 2)}, got {tuple(block_data.shape)}")
+    for name, m in masks.items():
+        _require(m, name, torch.uint8, like)
+        if m.dim() != 1 or m.numel() < params.n_blocks:
+            raise ValueError(f"{what}: {name} must be a vector of at least {params.n_blocks} bytes, got {tuple(m.shape)}")
+
+
+def _require_cameras(depth, intrinsics, cam_position, cam_quaternion, what: str):
+    if depth.dim() != 3:
+        raise ValueError(f"{what}: depth must be (num_cameras, H, W), got {tuple(depth.shape)}")
+    n, h, w = (int(v) for v in depth.shape)
+    for name, t, shape in (("depth", depth, (n, h, w)), ("intrinsics", intrinsics, (n, 3, 3)), ("cam_position", cam_position, (n, 3)),
+                           ("cam_quaternion", cam_quaternion, (n, 4))):
+        _require(t, name, torch.float32, depth)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{what}: {name} must have shape {shape}, got {tuple(t.shape)}")
+    return n, h, w
+
+
+def mapper_clear_mask(mask: torch.Tensor) -> None:
+    """``curobo_hip_mapper_clear_mask``"""
+    _require(mask, "mask", torch.uint8)
+    check(load().curobo_hip_mapper_clear_mask(ptr(mask), int(mask.numel()), current_stream(mask)))
+
+
+def mapper_mark_blocks(frame_mask: torch.Tensor, block_mask: torch.Tensor, depth: torch.Tensor, intrinsics: torch.Tensor,
+                       cam_position: torch.Tensor, cam_quaternion: torch.Tensor, params: MapperParams) -> None:
+    """``curobo_hip_mapper_mark_blocks``: 1 into both masks for every block a sample of this frame falls into"""
+    what = "mapper_mark_blocks"
+    n, h, w = _require_cameras(depth, intrinsics, cam_position, cam_quaternion, what)
+    _require_map(params, what, like=depth, frame_mask=frame_mask, block_mask=block_mask)
+    check(load().curobo_hip_mapper_mark_blocks(ptr(frame_mask), ptr(block_mask), ptr(depth), ptr(intrinsics), ptr(cam_position),
+                                               ptr(cam_quaternion), _C.addressof(params), n, h, w, current_stream(depth)))
+
+
+def mapper_integrate(block_data: torch.Tensor, frame_mask: torch.Tensor, depth: torch.Tensor, intrinsics: torch.Tensor,
+                     cam_position: torch.Tensor, cam_quaternion: torch.Tensor, params: MapperParams) -> None:
+    """``curobo_hip_mapper_integrate``: every voxel of every block of ``frame_mask``"""
+    what = "mapper_integrate"
+    n, h, w = _require_cameras(depth, intrinsics, cam_position, cam_quaternion, what)
+    _require_map(params, what, block_data, like=depth, frame_mask=frame_mask)
+    check(load().curobo_hip_mapper_integrate(ptr(block_data), ptr(frame_mask), ptr(depth), ptr(intrinsics), ptr(cam_position),
+                                             ptr(cam_quaternion), _C.addressof(params), n, h, w, current_stream(depth)))
+
+
+def _require_esdf(esdf_origin: torch.Tensor, esdf_voxel_size: torch.Tensor, shape: Sequence[int], what: str, like: torch.Tensor, **cells):
+    d, h, w = (int(v) for v in shape)
+    _require(esdf_origin, "esdf_origin", torch.float32, like)
+    _require(esdf_voxel_size, "esdf_voxel_size", torch.float32, like)
+    if esdf_origin.numel() != 3 or esdf_voxel_size.numel() != 1:
+        raise ValueError(f"{what}: esdf_origin must hold 3 values and esdf_voxel_size 1")
+    for name, (t, dt) in cells.items():
+        _require(t, name, dt, like)
+        if t.numel() != d * h * w:
+            raise ValueError(f"{what}: {name} must hold {d} x {h} x {w} = {d * h * w} cells, got {t.numel()}")
+    return d, h, w
+
+
+def mapper_esdf_seed(sites: torch.Tensor, block_data: torch.Tensor, block_mask: torch.Tensor, esdf_origin: torch.Tensor,
+                     esdf_voxel_size: torch.Tensor, params: MapperParams, shape: Sequence[int]) -> None:
+    """``curobo_hip_mapper_esdf_seed``: sites int32 [d h w] = the cell's packed coordinates where it is a seed, else -1"""
+    what = "mapper_esdf_seed"
+    _require_map(params, what, block_data, block_mask=block_mask)
+    d, h, w = _require_esdf(esdf_origin, esdf_voxel_size, shape, what, block_data, sites=(sites, torch.int32))
+    check(load().curobo_hip_mapper_esdf_seed(ptr(sites), ptr(block_data), ptr(block_mask), ptr(esdf_origin), ptr(esdf_voxel_size),
+                                             _C.addressof(params), d, h, w, current_stream(sites)))
+
+
+def mapper_edt_pass(sites_out: torch.Tensor, sites_in: torch.Tensor, shape: Sequence[int], axis: int) -> None:
+    """``curobo_hip_mapper_edt_pass``: one pass (axis 2, then 1, then 0) of the exact nearest-site transform"""
+    d, h, w = (int(v) for v in shape)
+    for name, t in (("sites_out", sites_out), ("sites_in", sites_in)):
+        _require(t, name, torch.int32, sites_in)
+        if t.numel() != d * h * w:
+            raise ValueError(f"mapper_edt_pass: {name} must hold {d} x {h} x {w} = {d * h * w} cells, got {t.numel()}")
+    check(load().curobo_hip_mapper_edt_pass(ptr(sites_out), ptr(sites_in), d, h, w, int(axis), current_stream(sites_in)))
+
+
+def mapper_edt(sites: torch.Tensor, scratch: torch.Tensor, shape: Sequence[int]) -> torch.Tensor:
+    """the three passes: ``sites`` -> ``scratch`` (z) -> ``sites`` (y) -> ``scratch`` (x).  Returns ``scratch``: the nearest sites."""
+    mapper_edt_pass(scratch, sites, shape, 2)
+    mapper_edt_pass(sites, scratch, shape, 1)
+    mapper_edt_pass(scratch, sites, shape, 0)
+    return scratch
+
+
+def mapper_esdf_distance(distance: torch.Tensor, sites: torch.Tensor, block_data: torch.Tensor, block_mask: torch.Tensor,
+                         esdf_origin: torch.Tensor, esdf_voxel_size: torch.Tensor, params: MapperParams, shape: Sequence[int]) -> None:
+    """``curobo_hip_mapper_esdf_distance``: distance fp16 [d h w], negative inside, 1e4 where there is no site"""
+    what = "mapper_esdf_distance"
+    _require_map(params, what, block_data, block_mask=block_mask)
+    d, h, w = _require_esdf(esdf_origin, esdf_voxel_size, shape, what, block_data, sites=(sites, torch.int32), distance=(distance, torch.float16))
+    check(load().curobo_hip_mapper_esdf_distance(ptr(distance), ptr(sites), ptr(block_data), ptr(block_mask), ptr(esdf_origin),
+                                                 ptr(esdf_voxel_size), _C.addressof(params), d, h, w, current_stream(distance)))
+
+
+def mapper_occupied_flags(flags: torch.Tensor, block_data: torch.Tensor, block_mask: torch.Tensor, params: MapperParams,
+                          surface_only: bool, sdf_threshold: float) -> None:
+    """``curobo_hip_mapper_occupied_flags``: flags uint8 [n_blocks, block_size^3]"""
+    what = "mapper_occupied_flags"
+    _require_map(params, what, block_data, block_mask=block_mask)
+    _require(flags, "flags", torch.uint8, block_data)
+    if flags.numel() != params.n_blocks * params.block_voxels:
+        raise ValueError(f"{what}: flags must hold {params.n_blocks * params.block_voxels} voxels, got {flags.numel()}")
+    check(load().curobo_hip_mapper_occupied_flags(ptr(flags), ptr(block_data), ptr(block_mask), _C.addressof(params), int(bool(surface_only)),
+                                                  float(sdf_threshold), current_stream(flags)))

@@ -38,6 +38,7 @@ SOURCES = [
     "perception.hip",
     "pose_detect.hip",
     "pose_icp.hip",
+    "mapper.hip",
 ]
 
 

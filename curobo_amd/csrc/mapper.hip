@@ -1,0 +1,444 @@
+// mapper.hip -- depth frames -> dense TSDF -> exact fp16 ESDF (curobo_amd/perception/mapper/mapper.py):
+//   curobo_hip_mapper_clear_mask      the frame's visible mask to 0 (a kernel, so that a captured chain holds kernel nodes only)
+//   curobo_hip_mapper_mark_blocks     one lane per (camera, pixel, sample along the ray): the blocks this frame sees
+//   curobo_hip_mapper_integrate       one workgroup per block, at once back where the frame does not see it: the weighted
+//                                     running mean of the projective signed distance, two fp16 words per voxel
+//   curobo_hip_mapper_esdf_seed       one lane per ESDF cell: 7 TSDF probes decide whether the cell is a site
+//   curobo_hip_mapper_edt_pass        one pass of the separable exact nearest-site transform, the lines of a tile in LDS
+//   curobo_hip_mapper_esdf_distance   site -> signed fp16 distance
+//   curobo_hip_mapper_occupied_flags  the rule of extract_occupied_voxels per voxel
+//
+// Reference: perception/mapper/kernel/builder/builder_camera_integrate.py (compute_block_keys_only_kernel :89-166,
+// integrate_voxels_kernel :400-487), builder_coord.py (world_to_continuous_voxel :45-54, voxel_to_world :57-66),
+// builder_esdf.py (_esdf_to_tsdf_voxel_coords :107-133, _check_seed_at_world_pos :267-306, seed_esdf_sites_gather_kernel
+// :308-406, compute_esdf_from_min_tsdf_kernel :412-491), wp_tsdf_sample.py (sample_dynamic_sdf :26-52), builder_raycast.py
+// (count_occupied_voxels_kernel :1015-1042).  The reference keeps the blocks in a hash table over a pool; here the grid is
+// dense, "block is allocated" is the byte block_mask, and nothing is allocated, hashed or counted with atomics: every store
+// of a launch goes to a word no other lane of that launch writes, except the mask bytes, which every writer sets to 1.
+//
+// The nearest-site transform: after the pass along z a cell knows the nearest seed of its z line, after y of its x plane,
+// after x of the grid (the squared distance separates by axis).  Within a pass the site of the line's cell j keeps j as its
+// coordinate along the line, so the pass is min_j (d2(j) + (i - j)^2) with d2(j) the squared distance of cell j to its own
+// site: d2 of a tile of lines is staged in LDS once and every cell scans its line by brute force, in integers.
+#include "common.hpp"
+
+namespace curobo_hip {
+
+constexpr int kMapThreads = 256;
+constexpr int kEdtThreads = 256;
+constexpr int kEdtLdsWords = 8192;        // 32 KB: columns per tile = min(64, kEdtLdsWords / line length)
+constexpr int kEdtNoSite = 1 << 30;       // above 3 * 1023^2 + 1023^2; kEdtNoSite + 1023^2 does not overflow
+constexpr int kEsdfMaxAxis = 1024;        // sites pack 10 bits per axis
+constexpr float kSdfInvalid = 1e10f;      // wp_tsdf_sample.py SDF_INFINITY as the lookups return it
+
+struct MapGrid {
+  int grid_w, grid_h, grid_d, bs, nbx, nby, nbz, num_samples;
+  float ox, oy, oz, vs, trunc, depth_min, depth_max, min_weight, step;
+};
+
+struct MapCameras {
+  const float *depth, *intrinsics, *position, *quaternion;
+  int n, height, width;
+};
+
+// wp.quat_rotate for q = (w, v): x (2 w^2 - 1) + 2 w (v x x) + 2 v (v . x)
+__device__ __forceinline__ f3 quat_rotate(float w, f3 v, f3 x) {
+  return (2.0f * w * w - 1.0f) * x + (2.0f * w) * cross(v, x) + (2.0f * dot(v, x)) * v;
+}
+
+__device__ __forceinline__ uint32_t pack_half2(float a, float b) {
+  const _Float16 ha = (_Float16)a, hb = (_Float16)b;  // round to nearest even
+  return (uint32_t)__builtin_bit_cast(uint16_t, ha) | ((uint32_t)__builtin_bit_cast(uint16_t, hb) << 16);
+}
+__device__ __forceinline__ float half_lo(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(v & 0xffffu)); }
+__device__ __forceinline__ float half_hi(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(v >> 16)); }
+
+// ---------------------------------------------------------------------------------------------------- frame mask
+__global__ __launch_bounds__(kMapThreads) void mapper_clear_mask_kernel(uint32_t *mask, int64_t n_words) {
+  const int64_t i = (int64_t)blockIdx.x * kMapThreads + threadIdx.x;
+  if (i < n_words) mask[i] = 0u;
+}
+
+// ---------------------------------------------------------------------------------------------------- stage 1: visible blocks
+__global__ __launch_bounds__(kMapThreads) void mapper_mark_kernel(uint8_t *frame_mask, uint8_t *block_mask, MapCameras c, MapGrid g) {
+  const int64_t tid = (int64_t)blockIdx.x * kMapThreads + threadIdx.x;
+  const int n_pixels = c.height * c.width;
+  const int64_t per_cam = (int64_t)n_pixels * g.num_samples;
+  if (tid >= per_cam * c.n) return;
+  const int cam = (int)(tid / per_cam);
+  const int rem = (int)(tid - (int64_t)cam * per_cam);
+  const int pixel = rem / g.num_samples, k = rem - pixel * g.num_samples;
+  const int px = pixel % c.width, py = pixel / c.width;
+  const float *K = c.intrinsics + cam * 9;
+  const float fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+  const float depth = c.depth[(size_t)cam * n_pixels + pixel];
+  if (depth < g.depth_min || depth > g.depth_max) return;
+  const float z_start = fmaxf(depth - g.trunc, g.depth_min);
+  const float z = z_start + (float)k * g.step;
+  if (z > depth + g.trunc + g.step) return;
+  const f3 p_cam = make_f3(((float)px + 0.5f - cx) / fx * z, ((float)py + 0.5f - cy) / fy * z, z);
+  const float *q = c.quaternion + cam * 4, *t = c.position + cam * 3;
+  const f3 p = make_f3(t[0], t[1], t[2]) + quat_rotate(q[0], make_f3(q[1], q[2], q[3]), p_cam);
+  const int vx = (int)floorf((p.x - g.ox) / g.vs + (float)g.grid_w * 0.5f);
+  const int vy = (int)floorf((p.y - g.oy) / g.vs + (float)g.grid_h * 0.5f);
+  const int vz = (int)floorf((p.z - g.oz) / g.vs + (float)g.grid_d * 0.5f);
+  if (vx < 0 || vx >= g.grid_w || vy < 0 || vy >= g.grid_h || vz < 0 || vz >= g.grid_d) return;
+  const int b = ((vz / g.bs) * g.nby + vy / g.bs) * g.nbx + vx / g.bs;  // < nbx nby nbz: the voxel is inside the grid
+  frame_mask[b] = 1;
+  block_mask[b] = 1;
+}
+
+// ---------------------------------------------------------------------------------------------------- stage 2: voxels
+__global__ __launch_bounds__(kMapThreads) void mapper_integrate_kernel(uint32_t *block_data, const uint8_t *frame_mask, MapCameras c, MapGrid g) {
+  const int b = blockIdx.x;
+  if (frame_mask[b] == 0) return;  // (uniform over the workgroup)
+  const int bx = b % g.nbx, by = (b / g.nbx) % g.nby, bz = b / (g.nbx * g.nby);
+  const int bs3 = g.bs * g.bs * g.bs;
+  for (int local = threadIdx.x; local < bs3; local += blockDim.x) {
+    const int lx = local % g.bs, ly = (local / g.bs) % g.bs, lz = local / (g.bs * g.bs);
+    const f3 centre = make_f3(((float)(bx * g.bs + lx) + 0.5f - (float)g.grid_w * 0.5f) * g.vs + g.ox,
+                              ((float)(by * g.bs + ly) + 0.5f - (float)g.grid_h * 0.5f) * g.vs + g.oy,
+                              ((float)(bz * g.bs + lz) + 0.5f - (float)g.grid_d * 0.5f) * g.vs + g.oz);
+    float total_sw = 0.0f, total_w = 0.0f;
+    for (int cam = 0; cam < c.n; cam++) {
+      const float *q = c.quaternion + cam * 4, *t = c.position + cam * 3;
+      // quat_inverse = the conjugate
+      const f3 v = quat_rotate(q[0], make_f3(-q[1], -q[2], -q[3]), centre - make_f3(t[0], t[1], t[2]));
+      // The depth along the camera's axis once more in double (the z row of the same rotation): sdf = depth - z cancels to
+      // nothing at the surface, where an fp32 z leaves an absolute error of a few 1e-7 m -- more than one step of the fp16
+      // word that stores sdf * weight there (steps of 6e-8 .. 5e-7 below 1e-3).  Pixel choice and weight stay fp32.
+      const double qw = q[0], qx = -(double)q[1], qy = -(double)q[2], qz = -(double)q[3];
+      const double ex = ((double)(bx * g.bs + lx) + 0.5 - (double)g.grid_w * 0.5) * (double)g.vs + (double)g.ox - (double)t[0];
+      const double ey = ((double)(by * g.bs + ly) + 0.5 - (double)g.grid_h * 0.5) * (double)g.vs + (double)g.oy - (double)t[1];
+      const double ez = ((double)(bz * g.bs + lz) + 0.5 - (double)g.grid_d * 0.5) * (double)g.vs + (double)g.oz - (double)t[2];
+      const double zd = ez * (2.0 * qw * qw - 1.0) + 2.0 * qw * (qx * ey - qy * ex) + 2.0 * qz * (qx * ex + qy * ey + qz * ez);
+      const float z = (float)zd;
+      if (!(zd > (double)g.depth_min)) continue;
+      const float *K = c.intrinsics + cam * 9;
+      const float fx = K[0], fy = K[4];
+      const float u = fx * v.x / z + K[2], w = fy * v.y / z + K[5];
+      const int px = (int)u, py = (int)w;  // toward zero: u in (-1, 0) is pixel 0, as in the reference
+      if (px < 0 || px >= c.width || py < 0 || py >= c.height) continue;
+      const float depth = c.depth[((size_t)cam * c.height + py) * c.width + px];
+      if (!(depth >= g.depth_min && depth <= g.depth_max)) continue;
+      const float sdf = (float)((double)depth - zd);
+      if (!(sdf >= -g.trunc)) continue;
+      const float weight = fmaxf((fx * g.vs / z) * (fy * g.vs / z), 1.0f);  // compute_tsdf_weight is 1
+      total_sw += fminf(sdf, g.trunc) * weight;
+      total_w += weight;
+    }
+    if (total_w > 0.0f) {
+      uint32_t *word = block_data + (size_t)b * bs3 + local;
+      const uint32_t old = *word;
+      *word = pack_half2(half_lo(old) + total_sw, half_hi(old) + total_w);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- TSDF sample
+// sdf at a world position, kSdfInvalid when the voxel is outside the grid, its block was never visible or it is unobserved
+__device__ __forceinline__ float tsdf_sample(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, float wx, float wy,
+                                             float wz) {
+  const int gx = (int)((wx - g.ox) / g.vs + (float)g.grid_w * 0.5f);
+  const int gy = (int)((wy - g.oy) / g.vs + (float)g.grid_h * 0.5f);
+  const int gz = (int)((wz - g.oz) / g.vs + (float)g.grid_d * 0.5f);
+  if (gx < 0 || gx >= g.grid_w || gy < 0 || gy >= g.grid_h || gz < 0 || gz >= g.grid_d) return kSdfInvalid;
+  const int b = ((gz / g.bs) * g.nby + gy / g.bs) * g.nbx + gx / g.bs;
+  if (block_mask[b] == 0) return kSdfInvalid;
+  const int local = ((gz % g.bs) * g.bs + gy % g.bs) * g.bs + gx % g.bs;
+  const uint32_t v = block_data[(size_t)b * (g.bs * g.bs * g.bs) + local];
+  const float w = half_hi(v);
+  return w > g.min_weight ? half_lo(v) / w : kSdfInvalid;
+}
+
+__device__ __forceinline__ bool is_seed(float sdf, const MapGrid &g) {
+  if (sdf > 1e9f) return false;
+  return fabsf(sdf) <= g.vs * 0.9f || sdf < -(g.trunc - g.vs * 1.1f);
+}
+
+struct EsdfArgs {
+  const uint32_t *block_data;
+  const uint8_t *block_mask;
+  const float *origin, *voxel_size;
+  int d, h, w;
+};
+
+// ---------------------------------------------------------------------------------------------------- ESDF stage 1: seed
+__global__ __launch_bounds__(kMapThreads) void mapper_esdf_seed_kernel(int32_t *sites, EsdfArgs a, MapGrid g) {
+  const int tid = blockIdx.x * kMapThreads + threadIdx.x;
+  if (tid >= a.d * a.h * a.w) return;
+  const int z = tid % a.w, y = (tid / a.w) % a.h, x = tid / (a.w * a.h);
+  const float vs = a.voxel_size[0], half = vs * 0.5f;
+  const float cx = a.origin[0] + ((float)x + 0.5f - (float)a.d * 0.5f) * vs;
+  const float cy = a.origin[1] + ((float)y + 0.5f - (float)a.h * 0.5f) * vs;
+  const float cz = a.origin[2] + ((float)z + 0.5f - (float)a.w * 0.5f) * vs;
+  const bool seed = is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx, cy, cz), g) ||
+                    is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx + half, cy, cz), g) ||
+                    is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx - half, cy, cz), g) ||
+                    is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx, cy + half, cz), g) ||
+                    is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx, cy - half, cz), g) ||
+                    is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx, cy, cz + half), g) ||
+                    is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx, cy, cz - half), g);
+  sites[tid] = seed ? (x | (y << 10) | (z << 20)) : -1;
+}
+
+// ---------------------------------------------------------------------------------------------------- ESDF stage 2: one pass
+// The grid seen from the pass: lines of `len` cells `stride_a` words apart; the lines are (p, q) with q the faster of the two
+// other axes.  A workgroup owns the `cols` lines q0 .. q0 + cols - 1 of one p.
+struct EdtArgs {
+  const int32_t *in;
+  int32_t *out;
+  int len, n_q, cols, axis;
+  int64_t stride_a, stride_p, stride_q;
+};
+
+__global__ __launch_bounds__(kEdtThreads) void mapper_edt_pass_kernel(EdtArgs a) {
+  __shared__ int d2[kEdtLdsWords];  // [j][col]
+  const int tid = threadIdx.x, p = blockIdx.y, q0 = blockIdx.x * a.cols;
+  const int32_t *in = a.in + (int64_t)p * a.stride_p;
+  const bool along_memory = a.stride_a == 1;
+  const int n = a.len * a.cols;  // <= kEdtLdsWords (the launcher's choice of cols)
+  for (int idx = tid; idx < n; idx += kEdtThreads) {
+    // consecutive lanes read consecutive words: along the line where the line is contiguous, else across the columns
+    const int col = along_memory ? idx / a.len : idx % a.cols;
+    const int j = along_memory ? idx % a.len : idx / a.cols;
+    const int q = q0 + col;
+    int v = kEdtNoSite;
+    if (q < a.n_q) {
+      const int32_t s = in[(int64_t)q * a.stride_q + (int64_t)j * a.stride_a];
+      if (s >= 0) {
+        // the cell's own coordinates: axis 2 = (p, q, j), axis 1 = (p, j, q), axis 0 = (j, p, q)
+        const int x = a.axis == 0 ? j : p, y = a.axis == 0 ? p : (a.axis == 1 ? j : q), z = a.axis == 2 ? j : q;
+        const int dx = x - (s & 0x3ff), dy = y - ((s >> 10) & 0x3ff), dz = z - ((s >> 20) & 0x3ff);
+        v = dx * dx + dy * dy + dz * dz;
+      }
+    }
+    d2[j * a.cols + col] = v;
+  }
+  __syncthreads();
+  // cells of a column kEdtThreads / cols apart per lane; where the line is contiguous consecutive lanes take consecutive cells
+  const int rows = kEdtThreads / a.cols;
+  const int col = along_memory ? tid / rows : tid % a.cols;
+  const int i0 = along_memory ? tid % rows : tid / a.cols;
+  const int q = q0 + col;
+  if (q >= a.n_q) return;
+  const int64_t line = (int64_t)q * a.stride_q;
+  for (int i = i0; i < a.len; i += rows) {
+    int best = kEdtNoSite, best_j = -1;
+    for (int j = 0; j < a.len; j++) {
+      const int v = d2[j * a.cols + col] + (i - j) * (i - j);
+      if (v < best) best = v, best_j = j;
+    }
+    a.out[(int64_t)p * a.stride_p + line + (int64_t)i * a.stride_a] = best_j >= 0 ? in[line + (int64_t)best_j * a.stride_a] : -1;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- ESDF stage 3: distance
+// (the reference's skip_steps branch reads the static channel only, which this mapper does not have: left out)
+__global__ __launch_bounds__(kMapThreads) void mapper_esdf_distance_kernel(uint16_t *distance, const int32_t *sites, EsdfArgs a, MapGrid g) {
+  const int tid = blockIdx.x * kMapThreads + threadIdx.x;
+  if (tid >= a.d * a.h * a.w) return;
+  const int32_t s = sites[tid];
+  float out = 1e4f;
+  if (s >= 0) {
+    const int z = tid % a.w, y = (tid / a.w) % a.h, x = tid / (a.w * a.h);
+    const float vs = a.voxel_size[0];
+    const float dx = (float)(x - (s & 0x3ff)), dy = (float)(y - ((s >> 10) & 0x3ff)), dz = (float)(z - ((s >> 20) & 0x3ff));
+    out = sqrtf(dx * dx + dy * dy + dz * dz) * vs;
+    const float sdf = tsdf_sample(a.block_data, a.block_mask, g, a.origin[0] + ((float)x + 0.5f - (float)a.d * 0.5f) * vs,
+                                  a.origin[1] + ((float)y + 0.5f - (float)a.h * 0.5f) * vs,
+                                  a.origin[2] + ((float)z + 0.5f - (float)a.w * 0.5f) * vs);
+    if (!(sdf > 1e9f) && sdf < 0.0f) out = -out;
+  }
+  distance[tid] = __builtin_bit_cast(uint16_t, (_Float16)out);
+}
+
+// ---------------------------------------------------------------------------------------------------- occupied voxels
+__global__ __launch_bounds__(kMapThreads) void mapper_occupied_kernel(uint8_t *flags, const uint32_t *block_data, const uint8_t *block_mask,
+                                                                      int64_t n_voxels, int bs3, float min_weight, int surface_only,
+                                                                      float sdf_threshold) {
+  const int64_t i = (int64_t)blockIdx.x * kMapThreads + threadIdx.x;
+  if (i >= n_voxels) return;
+  uint8_t flag = 0;
+  if (block_mask[i / bs3] != 0) {
+    const uint32_t v = block_data[i];
+    const float w = half_hi(v);
+    if (w > min_weight) {
+      const float sdf = half_lo(v) / w;
+      flag = surface_only ? (fabsf(sdf) < sdf_threshold) : (sdf <= 0.0f);
+    }
+  }
+  flags[i] = flag;
+}
+
+}  // namespace curobo_hip
+
+using namespace curobo_hip;
+
+// ---------------------------------------------------------------------------------------------------- host side
+static int64_t map_blocks(const MapGrid &g) { return (int64_t)g.nbx * g.nby * g.nbz; }
+
+static int read_params(const curobo_hip_mapper_params *p, MapGrid *g, const char *what) {
+  CUROBO_REQUIRE(p, "%s: params must not be null", what);
+  CUROBO_REQUIRE(p->grid_w > 0 && p->grid_h > 0 && p->grid_d > 0, "%s: the grid must have voxels along every axis, got %d x %d x %d", what,
+                 p->grid_w, p->grid_h, p->grid_d);
+  const int bs = p->block_size;
+  CUROBO_REQUIRE(bs >= 1 && bs <= 32 && (bs & (bs - 1)) == 0, "%s: block_size must be 1 or a power of two in 2..32, got %d", what, bs);
+  CUROBO_REQUIRE(p->nbx == ceil_div(p->grid_w, bs) && p->nby == ceil_div(p->grid_h, bs) && p->nbz == ceil_div(p->grid_d, bs),
+                 "%s: nbx, nby, nbz must be ceil(grid / block_size) = %d, %d, %d, got %d, %d, %d", what, ceil_div(p->grid_w, bs),
+                 ceil_div(p->grid_h, bs), ceil_div(p->grid_d, bs), p->nbx, p->nby, p->nbz);
+  const int64_t voxels = (int64_t)p->nbx * p->nby * p->nbz * bs * bs * bs;
+  CUROBO_REQUIRE(voxels < ((int64_t)1 << 31), "%s: the padded grid holds %lld voxels, the kernels index below 2^31", what, (long long)voxels);
+  CUROBO_REQUIRE(p->voxel_size > 0.0f && p->truncation_distance > 0.0f, "%s: voxel_size and truncation_distance must be positive", what);
+  CUROBO_REQUIRE(p->depth_min < p->depth_max, "%s: depth_min must be below depth_max", what);
+  g->grid_w = p->grid_w, g->grid_h = p->grid_h, g->grid_d = p->grid_d, g->bs = bs, g->nbx = p->nbx, g->nby = p->nby, g->nbz = p->nbz;
+  g->num_samples = p->num_samples, g->ox = p->origin[0], g->oy = p->origin[1], g->oz = p->origin[2], g->vs = p->voxel_size;
+  g->trunc = p->truncation_distance, g->depth_min = p->depth_min, g->depth_max = p->depth_max, g->min_weight = p->minimum_tsdf_weight;
+  g->step = p->step_size;
+  return CUROBO_HIP_OK;
+}
+
+static int read_cameras(MapCameras *c, const float *depth, const float *intrinsics, const float *cam_position, const float *cam_quaternion,
+                        int n_cameras, int height, int width, const char *what) {
+  CUROBO_REQUIRE(depth && intrinsics && cam_position && cam_quaternion,
+                 "%s: depth, intrinsics, cam_position and cam_quaternion must not be null", what);
+  CUROBO_REQUIRE(n_cameras > 0 && height > 0 && width > 0, "%s: depth must be (n_cameras, H, W), got (%d, %d, %d)", what, n_cameras, height,
+                 width);
+  CUROBO_REQUIRE((int64_t)n_cameras * height * width < ((int64_t)1 << 31), "%s: the depth images hold 2^31 pixels or more", what);
+  c->depth = depth, c->intrinsics = intrinsics, c->position = cam_position, c->quaternion = cam_quaternion;
+  c->n = n_cameras, c->height = height, c->width = width;
+  return CUROBO_HIP_OK;
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_clear_mask(uint8_t *mask, int64_t n_bytes, curobo_hip_stream_t stream) {
+  const char *what = "mapper_clear_mask";
+  CUROBO_REQUIRE(mask, "%s: mask must not be null", what);
+  CUROBO_REQUIRE(n_bytes > 0 && n_bytes % 4 == 0 && ((uintptr_t)mask & 3) == 0,
+                 "%s: the mask must be 4-byte aligned and a positive multiple of 4 bytes long, got %lld", what, (long long)n_bytes);
+  const int64_t words = n_bytes / 4;
+  hipLaunchKernelGGL(mapper_clear_mask_kernel, dim3((unsigned)ceil_div_l(words, kMapThreads)), dim3(kMapThreads), 0, (hipStream_t)stream,
+                     (uint32_t *)mask, words);
+  return check_launch(what, (hipStream_t)stream);
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_mark_blocks(uint8_t *frame_mask, uint8_t *block_mask, const float *depth, const float *intrinsics,
+                                                const float *cam_position, const float *cam_quaternion,
+                                                const curobo_hip_mapper_params *params, int n_cameras, int height, int width,
+                                                curobo_hip_stream_t stream) {
+  const char *what = "mapper_mark_blocks";
+  MapGrid g;
+  MapCameras c;
+  if (int rc = read_params(params, &g, what)) return rc;
+  if (int rc = read_cameras(&c, depth, intrinsics, cam_position, cam_quaternion, n_cameras, height, width, what)) return rc;
+  CUROBO_REQUIRE(frame_mask && block_mask, "%s: frame_mask and block_mask must not be null", what);
+  CUROBO_REQUIRE(g.num_samples > 0 && g.step > 0.0f, "%s: num_samples and step_size must be positive, got %d and %g", what, g.num_samples,
+                 (double)g.step);
+  const int64_t lanes = (int64_t)n_cameras * height * width * g.num_samples;
+  CUROBO_REQUIRE(lanes < ((int64_t)1 << 31) * kMapThreads, "%s: %lld samples are more than one launch holds", what, (long long)lanes);
+  hipLaunchKernelGGL(mapper_mark_kernel, dim3((unsigned)ceil_div_l(lanes, kMapThreads)), dim3(kMapThreads), 0, (hipStream_t)stream, frame_mask,
+                     block_mask, c, g);
+  return check_launch(what, (hipStream_t)stream);
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_integrate(void *block_data, const uint8_t *frame_mask, const float *depth, const float *intrinsics,
+                                              const float *cam_position, const float *cam_quaternion,
+                                              const curobo_hip_mapper_params *params, int n_cameras, int height, int width,
+                                              curobo_hip_stream_t stream) {
+  const char *what = "mapper_integrate";
+  MapGrid g;
+  MapCameras c;
+  if (int rc = read_params(params, &g, what)) return rc;
+  if (int rc = read_cameras(&c, depth, intrinsics, cam_position, cam_quaternion, n_cameras, height, width, what)) return rc;
+  CUROBO_REQUIRE(block_data && frame_mask, "%s: block_data and frame_mask must not be null", what);
+  CUROBO_REQUIRE(((uintptr_t)block_data & 3) == 0, "%s: block_data must be 4-byte aligned", what);
+  const int bs3 = g.bs * g.bs * g.bs;
+  hipLaunchKernelGGL(mapper_integrate_kernel, dim3((unsigned)map_blocks(g)), dim3(bs3 >= kMapThreads ? kMapThreads : kWave), 0,
+                     (hipStream_t)stream, (uint32_t *)block_data, frame_mask, c, g);
+  return check_launch(what, (hipStream_t)stream);
+}
+
+static int read_esdf(EsdfArgs *a, const void *block_data, const uint8_t *block_mask, const float *esdf_origin, const float *esdf_voxel_size,
+                     int esdf_d, int esdf_h, int esdf_w, const char *what) {
+  CUROBO_REQUIRE(block_data && block_mask && esdf_origin && esdf_voxel_size,
+                 "%s: block_data, block_mask, esdf_origin and esdf_voxel_size must not be null", what);
+  CUROBO_REQUIRE(((uintptr_t)block_data & 3) == 0, "%s: block_data must be 4-byte aligned", what);
+  CUROBO_REQUIRE(esdf_d > 0 && esdf_h > 0 && esdf_w > 0 && esdf_d <= kEsdfMaxAxis && esdf_h <= kEsdfMaxAxis && esdf_w <= kEsdfMaxAxis,
+                 "%s: every axis of the ESDF grid must hold 1..%d cells (sites pack 10 bits per axis), got %d x %d x %d", what, kEsdfMaxAxis,
+                 esdf_d, esdf_h, esdf_w);
+  a->block_data = (const uint32_t *)block_data, a->block_mask = block_mask, a->origin = esdf_origin, a->voxel_size = esdf_voxel_size;
+  a->d = esdf_d, a->h = esdf_h, a->w = esdf_w;
+  return CUROBO_HIP_OK;
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_esdf_seed(int32_t *sites, const void *block_data, const uint8_t *block_mask, const float *esdf_origin,
+                                              const float *esdf_voxel_size, const curobo_hip_mapper_params *params, int esdf_d, int esdf_h,
+                                              int esdf_w, curobo_hip_stream_t stream) {
+  const char *what = "mapper_esdf_seed";
+  MapGrid g;
+  EsdfArgs a;
+  if (int rc = read_params(params, &g, what)) return rc;
+  if (int rc = read_esdf(&a, block_data, block_mask, esdf_origin, esdf_voxel_size, esdf_d, esdf_h, esdf_w, what)) return rc;
+  CUROBO_REQUIRE(sites, "%s: sites must not be null", what);
+  const int cells = esdf_d * esdf_h * esdf_w;  // <= 2^30
+  hipLaunchKernelGGL(mapper_esdf_seed_kernel, dim3((unsigned)ceil_div(cells, kMapThreads)), dim3(kMapThreads), 0, (hipStream_t)stream, sites, a, g);
+  return check_launch(what, (hipStream_t)stream);
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_edt_pass(int32_t *sites_out, const int32_t *sites_in, int esdf_d, int esdf_h, int esdf_w, int axis,
+                                             curobo_hip_stream_t stream) {
+  const char *what = "mapper_edt_pass";
+  CUROBO_REQUIRE(sites_out && sites_in, "%s: sites_out and sites_in must not be null", what);
+  CUROBO_REQUIRE(esdf_d > 0 && esdf_h > 0 && esdf_w > 0 && esdf_d <= kEsdfMaxAxis && esdf_h <= kEsdfMaxAxis && esdf_w <= kEsdfMaxAxis,
+                 "%s: every axis of the ESDF grid must hold 1..%d cells (sites pack 10 bits per axis), got %d x %d x %d", what, kEsdfMaxAxis,
+                 esdf_d, esdf_h, esdf_w);
+  CUROBO_REQUIRE(axis >= 0 && axis <= 2, "%s: axis must be 0 (x), 1 (y) or 2 (z), got %d", what, axis);
+  const int64_t cells = (int64_t)esdf_d * esdf_h * esdf_w;
+  CUROBO_REQUIRE(sites_out + cells <= sites_in || sites_in + cells <= sites_out, "%s: sites_out and sites_in must not overlap", what);
+  EdtArgs a{};
+  a.in = sites_in, a.out = sites_out, a.axis = axis;
+  int n_p;
+  const int64_t hw = (int64_t)esdf_h * esdf_w;
+  if (axis == 2) a.len = esdf_w, n_p = esdf_d, a.n_q = esdf_h, a.stride_a = 1, a.stride_p = hw, a.stride_q = esdf_w;
+  else if (axis == 1) a.len = esdf_h, n_p = esdf_d, a.n_q = esdf_w, a.stride_a = esdf_w, a.stride_p = hw, a.stride_q = 1;
+  else a.len = esdf_d, n_p = esdf_h, a.n_q = esdf_w, a.stride_a = hw, a.stride_p = esdf_w, a.stride_q = 1;
+  // columns per workgroup: a power of two that divides the workgroup, fits the LDS tile (len <= 1024 leaves 8 or more) and does
+  // not run far past the lines there are; a pass along memory takes 4, so that a wavefront's 64 lanes write one line's run
+  int cols = a.stride_a == 1 ? 4 : 64;
+  while (cols * a.len > kEdtLdsWords) cols /= 2;
+  while (cols / 2 >= a.n_q) cols /= 2;
+  a.cols = cols;
+  hipLaunchKernelGGL(mapper_edt_pass_kernel, dim3((unsigned)ceil_div(a.n_q, cols), (unsigned)n_p), dim3(kEdtThreads), 0, (hipStream_t)stream, a);
+  return check_launch(what, (hipStream_t)stream);
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_esdf_distance(void *distance, const int32_t *sites, const void *block_data, const uint8_t *block_mask,
+                                                  const float *esdf_origin, const float *esdf_voxel_size,
+                                                  const curobo_hip_mapper_params *params, int esdf_d, int esdf_h, int esdf_w,
+                                                  curobo_hip_stream_t stream) {
+  const char *what = "mapper_esdf_distance";
+  MapGrid g;
+  EsdfArgs a;
+  if (int rc = read_params(params, &g, what)) return rc;
+  if (int rc = read_esdf(&a, block_data, block_mask, esdf_origin, esdf_voxel_size, esdf_d, esdf_h, esdf_w, what)) return rc;
+  CUROBO_REQUIRE(distance && sites, "%s: distance and sites must not be null", what);
+  CUROBO_REQUIRE(((uintptr_t)distance & 1) == 0, "%s: distance must be 2-byte aligned", what);
+  const int cells = esdf_d * esdf_h * esdf_w;
+  hipLaunchKernelGGL(mapper_esdf_distance_kernel, dim3((unsigned)ceil_div(cells, kMapThreads)), dim3(kMapThreads), 0, (hipStream_t)stream,
+                     (uint16_t *)distance, sites, a, g);
+  return check_launch(what, (hipStream_t)stream);
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_occupied_flags(uint8_t *flags, const void *block_data, const uint8_t *block_mask,
+                                                   const curobo_hip_mapper_params *params, int surface_only, float sdf_threshold,
+                                                   curobo_hip_stream_t stream) {
+  const char *what = "mapper_occupied_flags";
+  MapGrid g;
+  if (int rc = read_params(params, &g, what)) return rc;
+  CUROBO_REQUIRE(flags && block_data && block_mask, "%s: flags, block_data and block_mask must not be null", what);
+  CUROBO_REQUIRE(((uintptr_t)block_data & 3) == 0, "%s: block_data must be 4-byte aligned", what);
+  const int bs3 = g.bs * g.bs * g.bs;
+  const int64_t voxels = map_blocks(g) * bs3;
+  hipLaunchKernelGGL(mapper_occupied_kernel, dim3((unsigned)ceil_div_l(voxels, kMapThreads)), dim3(kMapThreads), 0, (hipStream_t)stream, flags,
+                     (const uint32_t *)block_data, block_mask, voxels, bs3, g.min_weight, surface_only != 0, sdf_threshold);
+  return check_launch(what, (hipStream_t)stream);
+}

@@ -1046,6 +1046,77 @@ int curobo_hip_pose_icp_step(curobo_hip_pose_icp_state *state, const void *works
 int curobo_hip_pose_icp_select(int32_t *out_index, float *out_error, float *out_transform,
                                const curobo_hip_pose_icp_state *state, int n_hypotheses, curobo_hip_stream_t stream);
 
+/* ---- depth mapper (curobo_amd/perception/mapper; reference perception/mapper: kernel/builder/builder_camera_integrate.py
+ * :89-166 and :400-487, builder_esdf.py :107-133, :267-491, builder_raycast.py :1015-1042).  The TSDF is stored DENSE:
+ * the grid of grid_w x grid_h x grid_d voxels (x, y, z) padded to whole blocks of block_size^3, block (bx, by, bz) at index
+ * (bz nby + by) nbx + bx, block_data fp16 [n_blocks][block_size^3][2] = (sum sdf w, sum w) at local index
+ * lz BS^2 + ly BS + lx, and one byte per block: block_mask "ever visible" (the reference's "allocated"), frame_mask
+ * "visible in this frame".  Voxel centre = origin + (g + 0.5 - N / 2) voxel_size.  No launch uses an atomic; every launch
+ * has dimensions fixed by the shapes alone.  The struct is read on the HOST at launch. */
+typedef struct curobo_hip_mapper_params {
+  int32_t grid_w, grid_h, grid_d;   /* voxels along x, y, z */
+  int32_t block_size;               /* 1 or a power of two in 2..32 */
+  int32_t nbx, nby, nbz;            /* blocks along x, y, z = ceil(grid / block_size) */
+  int32_t num_samples;              /* samples per pixel of the marking stage: ceil(2 truncation / step_size) + 1 */
+  float origin[3];                  /* world position of the grid's centre */
+  float voxel_size, truncation_distance, depth_min, depth_max, minimum_tsdf_weight;
+  float step_size;                  /* block_size voxel_size / 1.42 */
+} curobo_hip_mapper_params;
+
+/* n_bytes (a multiple of 4) bytes of a mask to 0: a kernel node, where a memset node would do on other stacks */
+int curobo_hip_mapper_clear_mask(uint8_t *mask, int64_t n_bytes, curobo_hip_stream_t stream);
+
+/* One lane per (camera, pixel, sample): depth [n_cameras, height, width] metres, intrinsics [n_cameras, 3, 3],
+ * cam_position [n_cameras, 3], cam_quaternion [n_cameras, 4] wxyz.  A pixel with depth in [depth_min, depth_max] is walked
+ * along its ray ((px + 0.5 - cx) / fx, (py + 0.5 - cy) / fy, 1) z from z_start = max(depth - truncation, depth_min) in
+ * steps of step_size while z <= depth + truncation + step_size; the block of every sample that falls into the grid gets 1
+ * in frame_mask and block_mask (plain byte stores of the same value). */
+int curobo_hip_mapper_mark_blocks(uint8_t *frame_mask, uint8_t *block_mask, const float *depth, const float *intrinsics,
+                                  const float *cam_position, const float *cam_quaternion,
+                                  const curobo_hip_mapper_params *params, int n_cameras, int height, int width,
+                                  curobo_hip_stream_t stream);
+
+/* One workgroup per block, returning at once where frame_mask is 0.  Per voxel and camera: the centre in the camera frame,
+ * z > depth_min, u = fx x / z + cx, v = fy y / z + cy, pixel ((int)u, (int)v) inside the image, its depth d in [depth_min,
+ * depth_max], sdf = d - z >= -truncation, clamped to truncation, weight = max((fx vs / z)(fy vs / z), 1).  z for the sdf is
+ * evaluated in double (d - z cancels at the surface, where an fp32 z is off by more than a step of the fp16 word); the pixel
+ * and the weight are fp32.  The sums over the cameras are fp32; where the summed weight is > 0 they are added to the stored
+ * pair in fp32 and rounded once to fp16. */
+int curobo_hip_mapper_integrate(void *block_data, const uint8_t *frame_mask, const float *depth, const float *intrinsics,
+                                const float *cam_position, const float *cam_quaternion,
+                                const curobo_hip_mapper_params *params, int n_cameras, int height, int width,
+                                curobo_hip_stream_t stream);
+
+/* The ESDF grid: esdf_d x esdf_h x esdf_w cells along x, y, z (x slowest, each <= 1024), cell centre = esdf_origin +
+ * (i + 0.5 - n / 2) esdf_voxel_size, both read from the DEVICE ([3] and [1] floats).  A TSDF sample at a world position:
+ * voxel (int)((p - origin) / voxel_size + N / 2) per axis, valid iff inside the grid, its block ever visible and its
+ * weight > minimum_tsdf_weight; then sdf = sum / weight.
+ * seed: one lane per cell; the cell is a seed iff at its centre or at +-half a cell along one axis a valid sample has
+ * |sdf| <= 0.9 voxel_size or sdf < -(truncation - 1.1 voxel_size).  A seed stores x | y << 10 | z << 20, every other cell -1. */
+int curobo_hip_mapper_esdf_seed(int32_t *sites, const void *block_data, const uint8_t *block_mask, const float *esdf_origin,
+                                const float *esdf_voxel_size, const curobo_hip_mapper_params *params, int esdf_d, int esdf_h,
+                                int esdf_w, curobo_hip_stream_t stream);
+
+/* One of the three passes of the exact Euclidean nearest-site transform: along axis (2 = z, then 1 = y, then 0 = x) every
+ * cell of a line receives the site of the line's cell j that minimises |cell - site(j)|^2 in integers (lowest j on a tie),
+ * or -1 when the line holds no site.  sites_in and sites_out [esdf_d esdf_h esdf_w] must not overlap.  After the three
+ * passes in that order every cell holds a nearest seed. */
+int curobo_hip_mapper_edt_pass(int32_t *sites_out, const int32_t *sites_in, int esdf_d, int esdf_h, int esdf_w, int axis,
+                               curobo_hip_stream_t stream);
+
+/* distance fp16 [esdf_d esdf_h esdf_w]: 1e4 where the cell has no site, else |cell - site| esdf_voxel_size in fp32, negated
+ * when the TSDF sample at the cell's own centre is valid and < 0. */
+int curobo_hip_mapper_esdf_distance(void *distance, const int32_t *sites, const void *block_data, const uint8_t *block_mask,
+                                    const float *esdf_origin, const float *esdf_voxel_size,
+                                    const curobo_hip_mapper_params *params, int esdf_d, int esdf_h, int esdf_w,
+                                    curobo_hip_stream_t stream);
+
+/* flags uint8 [n_blocks][block_size^3]: 1 where the block was ever visible, the voxel's weight > minimum_tsdf_weight and
+ * sdf <= 0 (surface_only == 0) or |sdf| < sdf_threshold (surface_only != 0), else 0. */
+int curobo_hip_mapper_occupied_flags(uint8_t *flags, const void *block_data, const uint8_t *block_mask,
+                                     const curobo_hip_mapper_params *params, int surface_only, float sdf_threshold,
+                                     curobo_hip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,112 @@
+"""Times of the depth mapper (csrc/mapper.hip) at the sizes a user runs -> <out>/mapper_timing.jsonl (one line per run).
+
+    python tools/mapper_timing.py [--out profiles]
+
+integrate: one 480 x 640 frame into the default map of the reference, 2 m at 5 mm = 400^3 voxels in blocks of 4 (256 MB dense),
+split into the frame-mask clear, the marking stage and the voxel stage.  compute_esdf: the captured chain at 128^3 and 256^3
+cells over the same map, and its five launches one by one.  Device events around repeated launches after a warm-up, the median
+of the rounds.  Beside each time the bytes the stage has to move (computed from the shapes and the visible-block count; the
+definitions are in the code) and what share of the 6.29 TB/s a float4 copy reaches on this part that is."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import mapper_ref as R  # noqa: E402  (the analytic depth image of a sphere over a ground plane)
+from curobo_amd.backends import mapper as B  # noqa: E402
+from curobo_amd.perception.mapper import Mapper, MapperCfg  # noqa: E402
+from curobo_amd.types import CameraObservation, Pose  # noqa: E402
+
+DEV = "cuda:0"
+HBM_BYTES_PER_S = 6.29e12  # measured float4 copy rate (8.0 TB/s on paper)
+
+
+def timed(fn, reps=20, rounds=5, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(rounds):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) / reps)
+    return float(np.median(out))
+
+
+def stage(ms: float, nbytes: float) -> dict:
+    return {"ms": round(ms, 4), "MB": round(nbytes / 1e6, 2), "share_of_hbm": round(nbytes / (ms * 1e-3) / HBM_BYTES_PER_S, 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "mapper_timing needs a GPU"
+    H, W = 480, 640
+    K = np.array([[520.0, 0, 320.3], [0, 520.0, 239.6], [0, 0, 1]], np.float32)
+    eye = np.array([1.0, -0.6, 0.5], np.float32)
+    quat = R.look_at(eye, (0.0, 0.0, -0.05), 0.3).astype(np.float32)
+    depth = R.render_depth(K, eye, quat, H, W)
+    t = lambda a: torch.as_tensor(a, device=DEV)  # noqa: E731
+    obs = CameraObservation(depth_image=t(depth[None]), intrinsics=t(K[None]), pose=Pose(t(eye[None]), t(quat[None])))
+    result = {"when": time.strftime("%Y-%m-%d"), "device": torch.cuda.get_device_name(0), "image": [H, W]}
+    for n_esdf in (128, 256):
+        cfg = MapperCfg(extent_meters_xyz=(2.0, 2.0, 2.0), voxel_size=0.005, image_height=H, image_width=W, esdf_voxel_size=2.0 / n_esdf,
+                        extent_esdf_meters_xyz=(2.0, 2.0, 2.0))
+        m = Mapper(cfg)
+        p, ts = m.tsdf.params, m.tsdf
+        d, k, pos, q = m._camera_tensors(obs)
+        m.integrate(obs)
+        torch.cuda.synchronize()
+        stats = m.get_stats()
+        visible, blocks, bs3 = stats["last_frame_blocks"], p.n_blocks, p.block_voxels
+        if n_esdf == 128:
+            lanes = H * W * p.num_samples
+            result["integrate"] = {
+                "map_voxels": [int(v) for v in cfg.grid_shape], "blocks": blocks, "visible_blocks": visible,
+                "workgroups_that_return_at_once": round(1.0 - visible / blocks, 4), "samples_per_pixel": int(p.num_samples),
+                # the mask's bytes written
+                "clear_mask": stage(timed(lambda: B.mapper_clear_mask(ts.frame_visible)), blocks),
+                # the depth image read once per sample lane group (cached after the first), one byte stored per live lane at most
+                "mark": stage(timed(lambda: B.mapper_mark_blocks(ts.frame_visible, ts.block_visible, d, k, pos, q, p)), H * W * 4 + lanes * 2),
+                # every mask byte read, the visible blocks' words read and written
+                "voxels": stage(timed(lambda: B.mapper_integrate(ts.block_data, ts.frame_visible, d, k, pos, q, p)), blocks + visible * bs3 * 8),
+                "whole_call": {"ms": round(timed(lambda: m.integrate(obs)), 4)}}
+        shape = m.esdf_grid_shape
+        cells = int(np.prod(shape))
+        m.compute_esdf()
+        torch.cuda.synchronize()
+        o, v = m._esdf_origin, m._esdf_voxel_size
+        entry = {"cells": list(shape), "captured_chain": {"ms": round(timed(lambda: m._graph.replay()), 4)},
+                 "whole_call": {"ms": round(timed(lambda: m.compute_esdf()), 4)},
+                 # a site word written per cell; the 7 probes of a cell read TSDF words, at most the whole dense map
+                 "seed": stage(timed(lambda: B.mapper_esdf_seed(m._sites, ts.block_data, ts.block_visible, o, v, p, shape)),
+                               cells * 4 + min(cells * 7 * 4, cfg.dense_bytes)),
+                 # a pass reads every site word, writes every site word and gathers one
+                 **{f"pass_{name}": stage(timed(lambda a=axis: B.mapper_edt_pass(m._sites_scratch, m._sites, shape, a)), cells * 12)
+                    for name, axis in (("z", 2), ("y", 1), ("x", 0))},
+                 # a site word and one TSDF word read, an fp16 written
+                 "distance": stage(timed(lambda: B.mapper_esdf_distance(m._dist_field, m._sites_scratch, ts.block_data, ts.block_visible, o, v, p, shape)),
+                                   cells * 10)}
+        result[f"esdf_{n_esdf}"] = entry
+        del m
+        torch.cuda.empty_cache()
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, "mapper_timing.jsonl"), "a") as fh:
+        fh.write(json.dumps(result) + "\n")
+    print(json.dumps(result, indent=1))
+
+
+if __name__ == "__main__":
+    main()
