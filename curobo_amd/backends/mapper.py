@@ -166,3 +166,86 @@ def mapper_occupied_flags(flags: torch.Tensor, block_data: torch.Tensor, block_m
         raise ValueError(f"{what}: flags must hold {params.n_blocks * params.block_voxels} voxels, got {flags.numel()}")
     check(load().curobo_hip_mapper_occupied_flags(ptr(flags), ptr(block_data), ptr(block_mask), _C.addressof(params), int(bool(surface_only)),
                                                   float(sdf_threshold), current_stream(flags)))
+
+
+def _require_mesh(params: MapperParams, what: str, block_list: torch.Tensor, **per_voxel) -> int:
+    """``block_list`` int32 [n_slots] and the per-voxel arrays [n_slots * block_size^3] (``(tensor, dtype, width)``); returns n_slots"""
+    _require(block_list, "block_list", torch.int32)
+    n_slots = int(block_list.numel())
+    if block_list.dim() != 1 or not 0 < n_slots <= params.n_blocks:
+        raise ValueError(f"{what}: block_list must be a vector of 1..{params.n_blocks} blocks, got {tuple(block_list.shape)}")
+    if n_slots * params.block_voxels * 5 >= 2 ** 31:
+        raise ValueError(f"{what}: {n_slots} visible blocks of {params.block_voxels} voxels may hold 2^31 triangles or more; indices are int32")
+    for name, (t, dt, width) in per_voxel.items():
+        _require(t, name, dt, block_list)
+        if t.numel() != n_slots * params.block_voxels * width:
+            raise ValueError(f"{what}: {name} must hold {n_slots} x {params.block_voxels} x {width} values, got {t.numel()}")
+    return n_slots
+
+
+def _require_rows(what: str, like: torch.Tensor, **rows) -> None:
+    """``(tensor, dtype, rows, width)``: contiguous, on ``like``'s device, of exactly that many values"""
+    for name, (t, dt, n, width) in rows.items():
+        _require(t, name, dt, like)
+        if t.numel() != n * width:
+            raise ValueError(f"{what}: {name} must hold {n} x {width} values, got {t.numel()}")
+
+
+def mapper_mesh_classify(cube_case: torch.Tensor, vert_count: torch.Tensor, tri_count: torch.Tensor, block_data: torch.Tensor,
+                         block_mask: torch.Tensor, block_list: torch.Tensor, table: torch.Tensor, params: MapperParams, level: float,
+                         surface_only: bool) -> None:
+    """``curobo_hip_mapper_mesh_classify``: per voxel of the listed blocks the case byte (0: no surface cube), the vertices it
+    owns (0..3) and the triangles of its table row (0..5); ``table`` int8 [256, 16]"""
+    what = "mapper_mesh_classify"
+    _require_map(params, what, block_data, block_mask=block_mask)
+    _require_mesh(params, what, block_list, cube_case=(cube_case, torch.uint8, 1), vert_count=(vert_count, torch.uint8, 1),
+                  tri_count=(tri_count, torch.uint8, 1))
+    _require_rows(what, block_list, table=(table, torch.int8, 256, 16))
+    check(load().curobo_hip_mapper_mesh_classify(ptr(cube_case), ptr(vert_count), ptr(tri_count), ptr(block_data), ptr(block_mask), ptr(block_list),
+                                                 int(block_list.numel()), ptr(table), _C.addressof(params), float(level),
+                                                 int(bool(surface_only)), current_stream(cube_case)))
+
+
+def mapper_mesh_vertices(vertices: torch.Tensor, normals: torch.Tensor, vert_ids: torch.Tensor, vert_count: torch.Tensor,
+                         vert_offset: torch.Tensor, block_data: torch.Tensor, block_mask: torch.Tensor, block_list: torch.Tensor,
+                         params: MapperParams, level: float, refine_iterations: int) -> None:
+    """``curobo_hip_mapper_mesh_vertices``: vertices, normals float32 [V, 3] at the offsets ``vert_offset`` (the exclusive prefix
+    sum of ``vert_count``, V its total), and the voxels' vertex ids int32 [n_slots * block_size^3, 3]"""
+    what = "mapper_mesh_vertices"
+    _require_map(params, what, block_data, block_mask=block_mask)
+    _require_mesh(params, what, block_list, vert_ids=(vert_ids, torch.int32, 3), vert_count=(vert_count, torch.uint8, 1),
+                  vert_offset=(vert_offset, torch.int32, 1))
+    n = int(vertices.shape[0])
+    _require_rows(what, block_list, vertices=(vertices, torch.float32, n, 3), normals=(normals, torch.float32, n, 3))
+    check(load().curobo_hip_mapper_mesh_vertices(ptr(vertices), ptr(normals), ptr(vert_ids), n, ptr(vert_count), ptr(vert_offset), ptr(block_data),
+                                                 ptr(block_mask), ptr(block_list), int(block_list.numel()), _C.addressof(params), float(level),
+                                                 int(refine_iterations), current_stream(vertices)))
+
+
+def mapper_mesh_triangles(raw_triangles: torch.Tensor, keep: torch.Tensor, cube_case: torch.Tensor, tri_count: torch.Tensor,
+                          tri_offset: torch.Tensor, vert_ids: torch.Tensor, vertices: torch.Tensor, block_list: torch.Tensor,
+                          block_slot: torch.Tensor, table: torch.Tensor, edge_owner: torch.Tensor, params: MapperParams) -> None:
+    """``curobo_hip_mapper_mesh_triangles``: every table triangle of every surface cube, int32 [n_raw, 3] with -1 for a missing
+    vertex, and ``keep`` uint8 [n_raw]; ``block_slot`` int32 [n_blocks], ``edge_owner`` int8 [12, 4]"""
+    what = "mapper_mesh_triangles"
+    _require_mesh(params, what, block_list, cube_case=(cube_case, torch.uint8, 1), tri_count=(tri_count, torch.uint8, 1),
+                  tri_offset=(tri_offset, torch.int32, 1), vert_ids=(vert_ids, torch.int32, 3))
+    n_raw, n_vertices = int(raw_triangles.shape[0]), int(vertices.shape[0])
+    _require_rows(what, block_list, raw_triangles=(raw_triangles, torch.int32, n_raw, 3), keep=(keep, torch.uint8, n_raw, 1),
+                  vertices=(vertices, torch.float32, n_vertices, 3), block_slot=(block_slot, torch.int32, params.n_blocks, 1),
+                  table=(table, torch.int8, 256, 16), edge_owner=(edge_owner, torch.int8, 12, 4))
+    check(load().curobo_hip_mapper_mesh_triangles(ptr(raw_triangles), ptr(keep), n_raw, ptr(cube_case), ptr(tri_count), ptr(tri_offset),
+                                                  ptr(vert_ids), ptr(vertices), n_vertices, ptr(block_list), ptr(block_slot),
+                                                  int(block_list.numel()), ptr(table), ptr(edge_owner), _C.addressof(params),
+                                                  current_stream(raw_triangles)))
+
+
+def mapper_mesh_compact(triangles: torch.Tensor, raw_triangles: torch.Tensor, keep: torch.Tensor, keep_offset: torch.Tensor) -> None:
+    """``curobo_hip_mapper_mesh_compact``: the raw triangles with ``keep`` set, in their order, to int32 [n, 3]; ``keep_offset`` int32:
+    the exclusive prefix sum of ``keep``, n its total"""
+    what = "mapper_mesh_compact"
+    n_raw, n = int(raw_triangles.shape[0]), int(triangles.shape[0])
+    _require_rows(what, raw_triangles, triangles=(triangles, torch.int32, n, 3), raw_triangles=(raw_triangles, torch.int32, n_raw, 3),
+                  keep=(keep, torch.uint8, n_raw, 1), keep_offset=(keep_offset, torch.int32, n_raw, 1))
+    check(load().curobo_hip_mapper_mesh_compact(ptr(triangles), n, ptr(raw_triangles), ptr(keep), ptr(keep_offset), n_raw,
+                                                current_stream(triangles)))

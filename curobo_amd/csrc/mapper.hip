@@ -7,12 +7,18 @@
 //   curobo_hip_mapper_edt_pass        one pass of the separable exact nearest-site transform, the lines of a tile in LDS
 //   curobo_hip_mapper_esdf_distance   site -> signed fp16 distance
 //   curobo_hip_mapper_occupied_flags  the rule of extract_occupied_voxels per voxel
+//   curobo_hip_mapper_mesh_classify   extract_mesh, per (visible block, tile): corner values in LDS, the cubes' cases and counts
+//   curobo_hip_mapper_mesh_vertices   ... per voxel: the vertices of its own cut edges, refined, with normals
+//   curobo_hip_mapper_mesh_triangles  ... per voxel: the table's triangles through the edges' owner cubes, and which of them stay
+//   curobo_hip_mapper_mesh_compact    ... per triangle: those that stay, in order
 //
 // Reference: perception/mapper/kernel/builder/builder_camera_integrate.py (compute_block_keys_only_kernel :89-166,
 // integrate_voxels_kernel :400-487), builder_coord.py (world_to_continuous_voxel :45-54, voxel_to_world :57-66),
 // builder_esdf.py (_esdf_to_tsdf_voxel_coords :107-133, _check_seed_at_world_pos :267-306, seed_esdf_sites_gather_kernel
 // :308-406, compute_esdf_from_min_tsdf_kernel :412-491), wp_tsdf_sample.py (sample_dynamic_sdf :26-52), builder_raycast.py
-// (count_occupied_voxels_kernel :1015-1042).  The reference keeps the blocks in a hash table over a pool; here the grid is
+// (count_occupied_voxels_kernel :1015-1042; sample_voxel :63-90, sample_tsdf_trilinear :168-258, compute_gradient :277-375),
+// builder_mesh.py (refine_vertex_mesh :52-80, is_surface_cube_combined :147-229, the vertex and triangle kernels :376-675),
+// marching_cubes/kernel/wp_mc_common.py (interpolate_edge_vertex :464-489), wp_mc_filter.py.  The reference keeps the blocks in a hash table over a pool; here the grid is
 // dense, "block is allocated" is the byte block_mask, and nothing is allocated, hashed or counted with atomics: every store
 // of a launch goes to a word no other lane of that launch writes, except the mask bytes, which every writer sets to 1.
 //
@@ -271,6 +277,244 @@ __global__ __launch_bounds__(kMapThreads) void mapper_occupied_kernel(uint8_t *f
   flags[i] = flag;
 }
 
+// ---------------------------------------------------------------------------------------------------- mesh extraction
+// Marching cubes over the ever-visible blocks.  Slot k of the compacted list is block block_list[k]; block_slot maps a block
+// back to its slot (-1: never visible).  Per-voxel scratch is [n_slots][bs^3] in the order (slot, voxel local index), which is
+// the order of the output; the offsets into the vertex and triangle lists are prefix sums the caller forms between launches.
+constexpr int kMeshTile = 8;                                                         // cubes per edge of a classify workgroup's tile
+constexpr int kMeshTileCorners = (kMeshTile + 1) * (kMeshTile + 1) * (kMeshTile + 1);  // 729 corner values in LDS
+
+struct MeshArgs {
+  const uint32_t *block_data;
+  const uint8_t *block_mask;
+  const int32_t *block_list, *block_slot;
+  int n_slots;
+  float level;
+};
+
+// the stored sdf of voxel (gx, gy, gz) of the PADDED grid, kSdfInvalid where there is no such voxel, its block was never
+// visible or its weight is below the minimum (>=: builder_raycast.py:78, the lookups of the mesh and the renderer)
+__device__ __forceinline__ float mesh_voxel(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, int gx, int gy, int gz) {
+  if (gx < 0 || gx >= g.nbx * g.bs || gy < 0 || gy >= g.nby * g.bs || gz < 0 || gz >= g.nbz * g.bs) return kSdfInvalid;
+  const int b = ((gz / g.bs) * g.nby + gy / g.bs) * g.nbx + gx / g.bs;
+  if (block_mask[b] == 0) return kSdfInvalid;
+  const int local = ((gz % g.bs) * g.bs + gy % g.bs) * g.bs + gx % g.bs;
+  const uint32_t v = block_data[(size_t)b * (g.bs * g.bs * g.bs) + local];
+  const float w = half_hi(v);
+  return w >= g.min_weight ? half_lo(v) / w : kSdfInvalid;
+}
+
+// continuous voxel coordinate of a world position (builder_coord.py:45-54)
+__device__ __forceinline__ f3 mesh_continuous(const MapGrid &g, f3 p) {
+  return make_f3((p.x - g.ox) / g.vs + (float)g.grid_w * 0.5f, (p.y - g.oy) / g.vs + (float)g.grid_h * 0.5f,
+                 (p.z - g.oz) / g.vs + (float)g.grid_d * 0.5f);
+}
+
+// nearest-voxel sample: voxel floor(v)  (builder_raycast.py:92-109)
+__device__ __forceinline__ float mesh_nearest(const MeshArgs &a, const MapGrid &g, f3 p) {
+  const f3 v = mesh_continuous(g, p);
+  return mesh_voxel(a.block_data, a.block_mask, g, (int)floorf(v.x), (int)floorf(v.y), (int)floorf(v.z));
+}
+
+// trilinear sample, lower corner floor(v - 0.5); an invalid corner contributes the truncation distance, no valid corner at
+// all makes the sample invalid  (builder_raycast.py:168-258)
+__device__ __forceinline__ float mesh_trilinear(const MeshArgs &a, const MapGrid &g, f3 p) {
+  const f3 v = mesh_continuous(g, p);
+  const float fx = v.x - 0.5f, fy = v.y - 0.5f, fz = v.z - 0.5f;
+  const float x0 = floorf(fx), y0 = floorf(fy), z0 = floorf(fz);
+  const float tx = fx - x0, ty = fy - y0, tz = fz - z0;
+  const int ix = (int)x0, iy = (int)y0, iz = (int)z0;
+  float total = 0.0f;
+  bool any_valid = false;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
+    const float s = mesh_voxel(a.block_data, a.block_mask, g, ix + dx, iy + dy, iz + dz);
+    const bool ok = !(s > 1e9f);
+    any_valid |= ok;
+    total += (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty) * (dz ? tz : 1.0f - tz) * (ok ? s : g.trunc);
+  }
+  return any_valid ? total : kSdfInvalid;
+}
+
+// normalised central difference of six samples at +-voxel_size; (0, 0, 1) where one of them is invalid or the magnitude is
+// below 1e-6  (builder_raycast.py:277-325 with trilinear samples, :327-375 with nearest-voxel samples)
+template <bool TRILINEAR>
+__device__ __forceinline__ f3 mesh_gradient(const MeshArgs &a, const MapGrid &g, f3 p) {
+  float s[6];
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    const float e = (k & 1) ? -g.vs : g.vs;
+    const f3 q = make_f3(p.x + (k / 2 == 0 ? e : 0.0f), p.y + (k / 2 == 1 ? e : 0.0f), p.z + (k / 2 == 2 ? e : 0.0f));
+    s[k] = TRILINEAR ? mesh_trilinear(a, g, q) : mesh_nearest(a, g, q);
+  }
+  const f3 up = make_f3(0.0f, 0.0f, 1.0f);
+  if (s[0] > 1e9f || s[1] > 1e9f || s[2] > 1e9f || s[3] > 1e9f || s[4] > 1e9f || s[5] > 1e9f) return up;
+  const f3 grad = make_f3((s[0] - s[1]) / (2.0f * g.vs), (s[2] - s[3]) / (2.0f * g.vs), (s[4] - s[5]) / (2.0f * g.vs));
+  const float mag = sqrtf(grad.x * grad.x + grad.y * grad.y + grad.z * grad.z);
+  if (mag < 1e-6f) return up;
+  return make_f3(grad.x / mag, grad.y / mag, grad.z / mag);
+}
+
+// Stage 1, one workgroup per (slot, tile of min(bs, 8)^3 cubes): the (tile + 1)^3 corner values sw / w - level once into LDS,
+// then per cube: is it a surface cube (builder_mesh.py:147-229), its case (:610-626), how many of its own edges 0, 3, 8 are
+// cut (exactly one end negative) and how many triangles its table row holds.  A cube that is no surface cube gets case 0.
+__global__ __launch_bounds__(kMapThreads) void mapper_mesh_classify_kernel(uint8_t *cube_case, uint8_t *vert_count, uint8_t *tri_count, MeshArgs a,
+                                                                           const int8_t *table, int surface_only, MapGrid g) {
+  __shared__ float corner[kMeshTileCorners];
+  const int tb = g.bs < kMeshTile ? g.bs : kMeshTile, tiles = g.bs / tb, tiles3 = tiles * tiles * tiles;
+  const int slot = blockIdx.x / tiles3, tile = blockIdx.x - slot * tiles3;
+  const int b = a.block_list[slot];
+  if (b < 0 || b >= g.nbx * g.nby * g.nbz) return;  // (uniform over the workgroup; the caller's list holds block rows only)
+  const int tx = tile % tiles, ty = (tile / tiles) % tiles, tz = tile / (tiles * tiles);
+  const int x0 = (b % g.nbx) * g.bs + tx * tb, y0 = ((b / g.nbx) % g.nby) * g.bs + ty * tb, z0 = (b / (g.nbx * g.nby)) * g.bs + tz * tb;
+  const int tc = tb + 1;
+  for (int idx = threadIdx.x; idx < tc * tc * tc; idx += blockDim.x) {
+    const float s = mesh_voxel(a.block_data, a.block_mask, g, x0 + idx % tc, y0 + (idx / tc) % tc, z0 + idx / (tc * tc));
+    corner[idx] = s > 1e9f ? kSdfInvalid : s - a.level;
+  }
+  __syncthreads();
+  const int bs3 = g.bs * g.bs * g.bs;
+  for (int v = threadIdx.x; v < tb * tb * tb; v += blockDim.x) {
+    const int lx = v % tb, ly = (v / tb) % tb, lz = v / (tb * tb);
+    const int at = (lz * tc + ly) * tc + lx;
+    // corners 0..7 at (0,0,0) (1,0,0) (1,1,0) (0,1,0) (0,0,1) (1,0,1) (1,1,1) (0,1,1)
+    const float s[8] = {corner[at],           corner[at + 1],           corner[at + tc + 1],           corner[at + tc],
+                        corner[at + tc * tc], corner[at + tc * tc + 1], corner[at + tc * tc + tc + 1], corner[at + tc * tc + tc]};
+    bool valid = true, positive = false, negative = false, in_band = false;
+    int config = 0;
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+      valid &= !(s[c] > 1e9f);
+      positive |= s[c] > 0.0f;
+      negative |= s[c] < 0.0f;
+      in_band |= fabsf(s[c]) < g.trunc;
+      config |= (s[c] < 0.0f) << c;
+    }
+    const bool surface = valid && positive && negative && (!surface_only || in_band);
+    int n_vert = 0, n_tri = 0;
+    if (surface) {
+      n_vert = (int)((s[0] < 0.0f) != (s[1] < 0.0f)) + (int)((s[0] < 0.0f) != (s[3] < 0.0f)) + (int)((s[0] < 0.0f) != (s[4] < 0.0f));
+      while (n_tri < 5 && table[config * 16 + n_tri * 3] >= 0) n_tri++;
+    }
+    const size_t out = (size_t)slot * bs3 + ((tz * tb + lz) * g.bs + ty * tb + ly) * g.bs + tx * tb + lx;
+    cube_case[out] = surface ? (uint8_t)config : (uint8_t)0;
+    vert_count[out] = (uint8_t)n_vert;
+    tri_count[out] = (uint8_t)n_tri;
+  }
+}
+
+// Stage 2, one lane per voxel of the visible blocks: the vertices of its own cut edges at vert_offset[i] .. in the order x, y,
+// z, refined (builder_mesh.py:52-80) and with their normals, and the voxel's three vertex ids (-1 where it emits none)
+__global__ __launch_bounds__(kMapThreads) void mapper_mesh_vertices_kernel(float *vertices, float *normals, int32_t *vert_ids, int n_vertices,
+                                                                           const uint8_t *vert_count, const int32_t *vert_offset, MeshArgs a,
+                                                                           int refine_iterations, MapGrid g) {
+  const int bs3 = g.bs * g.bs * g.bs;
+  const int64_t i = (int64_t)blockIdx.x * kMapThreads + threadIdx.x;
+  if (i >= (int64_t)a.n_slots * bs3) return;
+  int32_t *ids = vert_ids + (size_t)i * 3;
+  ids[0] = ids[1] = ids[2] = -1;
+  if (vert_count[i] == 0) return;
+  const int slot = (int)(i / bs3), local = (int)(i - (int64_t)slot * bs3);
+  const int b = a.block_list[slot];
+  if (b < 0 || b >= g.nbx * g.nby * g.nbz) return;
+  const int gx = (b % g.nbx) * g.bs + local % g.bs, gy = ((b / g.nbx) % g.nby) * g.bs + (local / g.bs) % g.bs;
+  const int gz = (b / (g.nbx * g.nby)) * g.bs + local / (g.bs * g.bs);
+  // (a surface cube: all four are valid)
+  const float s0 = mesh_voxel(a.block_data, a.block_mask, g, gx, gy, gz) - a.level;
+  const float sb[3] = {mesh_voxel(a.block_data, a.block_mask, g, gx + 1, gy, gz) - a.level,
+                       mesh_voxel(a.block_data, a.block_mask, g, gx, gy + 1, gz) - a.level,
+                       mesh_voxel(a.block_data, a.block_mask, g, gx, gy, gz + 1) - a.level};
+  // the voxel centres origin + (g + 0.5 - N / 2) voxel_size: where the TSDF was sampled
+  const float pa[3] = {((float)gx + 0.5f - (float)g.grid_w * 0.5f) * g.vs + g.ox, ((float)gy + 0.5f - (float)g.grid_h * 0.5f) * g.vs + g.oy,
+                       ((float)gz + 0.5f - (float)g.grid_d * 0.5f) * g.vs + g.oz};
+  const float pb[3] = {((float)(gx + 1) + 0.5f - (float)g.grid_w * 0.5f) * g.vs + g.ox,
+                       ((float)(gy + 1) + 0.5f - (float)g.grid_h * 0.5f) * g.vs + g.oy,
+                       ((float)(gz + 1) + 0.5f - (float)g.grid_d * 0.5f) * g.vs + g.oz};
+  int vid = vert_offset[i];
+#pragma unroll
+  for (int axis = 0; axis < 3; axis++) {
+    if ((s0 < 0.0f) == (sb[axis] < 0.0f)) continue;
+    if (vid < 0 || vid >= n_vertices) return;  // (offsets that do not belong to these counts)
+    const float t = fminf(fmaxf(-s0 / (sb[axis] - s0), 0.0f), 1.0f);  // wp_mc_common.py:487-488
+    float p[3] = {pa[0], pa[1], pa[2]};
+    p[axis] = pa[axis] + t * (pb[axis] - pa[axis]);
+    f3 pos = make_f3(p[0], p[1], p[2]);
+    for (int it = 0; it < refine_iterations; it++) {
+      const float sdf = mesh_trilinear(a, g, pos);
+      if (sdf > 1e9f) break;
+      const float value = sdf - a.level;
+      if (fabsf(value) < 1e-6f || value > 100.0f) break;
+      const f3 dir = mesh_gradient<true>(a, g, pos);
+      const float step = fminf(fmaxf(value, -0.5f * g.vs), 0.5f * g.vs);
+      pos = pos - step * dir;
+    }
+    const f3 n = mesh_gradient<false>(a, g, pos);
+    float *vo = vertices + (size_t)vid * 3, *no = normals + (size_t)vid * 3;
+    vo[0] = pos.x, vo[1] = pos.y, vo[2] = pos.z;
+    no[0] = n.x, no[1] = n.y, no[2] = n.z;
+    ids[axis] = vid++;
+  }
+}
+
+// Stage 3, one lane per voxel of the visible blocks: the triangles of the cube's table row at tri_offset[i] .., every corner the
+// vertex of the edge's owner cube (edge_owner[e] = dx, dy, dz, axis), -1 where that cube emits none or is not there; and per
+// triangle whether it stays: three vertices, all different, |cross|^2 above (voxel_size 1e-6)^2  (wp_mc_filter.py:91-108, :156)
+__global__ __launch_bounds__(kMapThreads) void mapper_mesh_triangles_kernel(int32_t *raw, uint8_t *keep, int n_raw, const uint8_t *cube_case,
+                                                                            const uint8_t *tri_count, const int32_t *tri_offset,
+                                                                            const int32_t *vert_ids, const float *vertices, int n_vertices, MeshArgs a,
+                                                                            const int8_t *table, const int8_t *edge_owner, MapGrid g) {
+  const int bs3 = g.bs * g.bs * g.bs;
+  const int64_t i = (int64_t)blockIdx.x * kMapThreads + threadIdx.x;
+  if (i >= (int64_t)a.n_slots * bs3) return;
+  const int count = tri_count[i];
+  if (count == 0) return;
+  const int slot = (int)(i / bs3), local = (int)(i - (int64_t)slot * bs3);
+  const int b = a.block_list[slot];
+  if (b < 0 || b >= g.nbx * g.nby * g.nbz) return;
+  const int gx = (b % g.nbx) * g.bs + local % g.bs, gy = ((b / g.nbx) % g.nby) * g.bs + (local / g.bs) % g.bs;
+  const int gz = (b / (g.nbx * g.nby)) * g.bs + local / (g.bs * g.bs);
+  const int8_t *row = table + (int)cube_case[i] * 16;
+  const int base = tri_offset[i];
+  const float min_cross2 = (g.vs * 1e-6f) * (g.vs * 1e-6f);
+  for (int t = 0; t < count && t < 5; t++) {
+    if (base < 0 || base + t >= n_raw) return;  // (offsets that do not belong to these counts)
+    int id[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const int e = row[t * 3 + k];
+      id[k] = -1;
+      if (e < 0 || e >= 12) continue;
+      const int ox = gx + edge_owner[e * 4], oy = gy + edge_owner[e * 4 + 1], oz = gz + edge_owner[e * 4 + 2], axis = edge_owner[e * 4 + 3];
+      if (ox >= g.nbx * g.bs || oy >= g.nby * g.bs || oz >= g.nbz * g.bs || axis < 0 || axis > 2) continue;
+      const int os = a.block_slot[((oz / g.bs) * g.nby + oy / g.bs) * g.nbx + ox / g.bs];
+      if (os < 0 || os >= a.n_slots) continue;
+      id[k] = vert_ids[((size_t)os * bs3 + ((oz % g.bs) * g.bs + oy % g.bs) * g.bs + ox % g.bs) * 3 + axis];
+      if (id[k] >= n_vertices) id[k] = -1;
+    }
+    bool stays = id[0] >= 0 && id[1] >= 0 && id[2] >= 0 && id[0] != id[1] && id[1] != id[2] && id[0] != id[2];
+    if (stays) {
+      const float *v0 = vertices + (size_t)id[0] * 3, *v1 = vertices + (size_t)id[1] * 3, *v2 = vertices + (size_t)id[2] * 3;
+      const f3 p0 = make_f3(v0[0], v0[1], v0[2]);
+      const f3 c = cross(make_f3(v1[0], v1[1], v1[2]) - p0, make_f3(v2[0], v2[1], v2[2]) - p0);
+      stays = !(dot(c, c) <= min_cross2);
+    }
+    int32_t *out = raw + (size_t)(base + t) * 3;
+    out[0] = id[0], out[1] = id[1], out[2] = id[2];
+    keep[base + t] = stays ? 1 : 0;
+  }
+}
+
+// Stage 4, one lane per triangle of stage 3: those that stay to keep_offset[j], in their order
+__global__ __launch_bounds__(kMapThreads) void mapper_mesh_compact_kernel(int32_t *triangles, int n_triangles, const int32_t *raw, const uint8_t *keep,
+                                                                          const int32_t *keep_offset, int n_raw) {
+  const int64_t j = (int64_t)blockIdx.x * kMapThreads + threadIdx.x;
+  if (j >= n_raw || keep[j] == 0) return;
+  const int o = keep_offset[j];
+  if (o < 0 || o >= n_triangles) return;
+  triangles[(size_t)o * 3] = raw[(size_t)j * 3], triangles[(size_t)o * 3 + 1] = raw[(size_t)j * 3 + 1], triangles[(size_t)o * 3 + 2] = raw[(size_t)j * 3 + 2];
+}
+
 }  // namespace curobo_hip
 
 using namespace curobo_hip;
@@ -440,5 +684,85 @@ CUROBO_EXPORT int curobo_hip_mapper_occupied_flags(uint8_t *flags, const void *b
   const int64_t voxels = map_blocks(g) * bs3;
   hipLaunchKernelGGL(mapper_occupied_kernel, dim3((unsigned)ceil_div_l(voxels, kMapThreads)), dim3(kMapThreads), 0, (hipStream_t)stream, flags,
                      (const uint32_t *)block_data, block_mask, voxels, bs3, g.min_weight, surface_only != 0, sdf_threshold);
+  return check_launch(what, (hipStream_t)stream);
+}
+
+static int read_mesh(MeshArgs *a, const void *block_data, const uint8_t *block_mask, const int32_t *block_list, const int32_t *block_slot,
+                     int n_slots, float level, const MapGrid &g, const char *what) {
+  CUROBO_REQUIRE(block_data && block_mask && block_list, "%s: block_data, block_mask and block_list must not be null", what);
+  CUROBO_REQUIRE(((uintptr_t)block_data & 3) == 0, "%s: block_data must be 4-byte aligned", what);
+  CUROBO_REQUIRE(n_slots > 0 && n_slots <= map_blocks(g), "%s: block_list must hold 1..%lld blocks, got %d", what, (long long)map_blocks(g),
+                 n_slots);
+  a->block_data = (const uint32_t *)block_data, a->block_mask = block_mask, a->block_list = block_list, a->block_slot = block_slot;
+  a->n_slots = n_slots, a->level = level;
+  return CUROBO_HIP_OK;
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_mesh_classify(uint8_t *cube_case, uint8_t *vert_count, uint8_t *tri_count, const void *block_data,
+                                                  const uint8_t *block_mask, const int32_t *block_list, int n_slots, const int8_t *table,
+                                                  const curobo_hip_mapper_params *params, float level, int surface_only,
+                                                  curobo_hip_stream_t stream) {
+  const char *what = "mapper_mesh_classify";
+  MapGrid g;
+  MeshArgs a;
+  if (int rc = read_params(params, &g, what)) return rc;
+  if (int rc = read_mesh(&a, block_data, block_mask, block_list, nullptr, n_slots, level, g, what)) return rc;
+  CUROBO_REQUIRE(cube_case && vert_count && tri_count && table, "%s: cube_case, vert_count, tri_count and table must not be null", what);
+  const int tb = g.bs < kMeshTile ? g.bs : kMeshTile, tiles = g.bs / tb;
+  const int64_t groups = (int64_t)n_slots * tiles * tiles * tiles;  // <= the voxels of the padded grid < 2^31
+  hipLaunchKernelGGL(mapper_mesh_classify_kernel, dim3((unsigned)groups), dim3(tb * tb * tb >= kMapThreads ? kMapThreads : kWave), 0,
+                     (hipStream_t)stream, cube_case, vert_count, tri_count, a, table, surface_only != 0, g);
+  return check_launch(what, (hipStream_t)stream);
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_mesh_vertices(float *vertices, float *normals, int32_t *vert_ids, int n_vertices, const uint8_t *vert_count,
+                                                  const int32_t *vert_offset, const void *block_data, const uint8_t *block_mask,
+                                                  const int32_t *block_list, int n_slots, const curobo_hip_mapper_params *params, float level,
+                                                  int refine_iterations, curobo_hip_stream_t stream) {
+  const char *what = "mapper_mesh_vertices";
+  MapGrid g;
+  MeshArgs a;
+  if (int rc = read_params(params, &g, what)) return rc;
+  if (int rc = read_mesh(&a, block_data, block_mask, block_list, nullptr, n_slots, level, g, what)) return rc;
+  CUROBO_REQUIRE(vertices && normals && vert_ids && vert_count && vert_offset,
+                 "%s: vertices, normals, vert_ids, vert_count and vert_offset must not be null", what);
+  CUROBO_REQUIRE(n_vertices > 0 && refine_iterations >= 0, "%s: n_vertices must be positive and refine_iterations >= 0, got %d and %d", what,
+                 n_vertices, refine_iterations);
+  const int64_t voxels = (int64_t)n_slots * g.bs * g.bs * g.bs;
+  hipLaunchKernelGGL(mapper_mesh_vertices_kernel, dim3((unsigned)ceil_div_l(voxels, kMapThreads)), dim3(kMapThreads), 0, (hipStream_t)stream,
+                     vertices, normals, vert_ids, n_vertices, vert_count, vert_offset, a, refine_iterations, g);
+  return check_launch(what, (hipStream_t)stream);
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_mesh_triangles(int32_t *raw_triangles, uint8_t *keep, int n_raw, const uint8_t *cube_case,
+                                                   const uint8_t *tri_count, const int32_t *tri_offset, const int32_t *vert_ids,
+                                                   const float *vertices, int n_vertices, const int32_t *block_list,
+                                                   const int32_t *block_slot, int n_slots, const int8_t *table, const int8_t *edge_owner,
+                                                   const curobo_hip_mapper_params *params, curobo_hip_stream_t stream) {
+  const char *what = "mapper_mesh_triangles";
+  MapGrid g;
+  if (int rc = read_params(params, &g, what)) return rc;
+  CUROBO_REQUIRE(raw_triangles && keep && cube_case && tri_count && tri_offset && vert_ids && vertices && block_list && block_slot && table &&
+                     edge_owner,
+                 "%s: no pointer may be null", what);
+  CUROBO_REQUIRE(n_slots > 0 && n_slots <= map_blocks(g), "%s: block_list must hold 1..%lld blocks, got %d", what, (long long)map_blocks(g),
+                 n_slots);
+  MeshArgs a{};  // (this launch reads no TSDF)
+  a.block_list = block_list, a.block_slot = block_slot, a.n_slots = n_slots;
+  CUROBO_REQUIRE(n_raw > 0 && n_vertices > 0, "%s: n_raw and n_vertices must be positive, got %d and %d", what, n_raw, n_vertices);
+  const int64_t voxels = (int64_t)n_slots * g.bs * g.bs * g.bs;
+  hipLaunchKernelGGL(mapper_mesh_triangles_kernel, dim3((unsigned)ceil_div_l(voxels, kMapThreads)), dim3(kMapThreads), 0, (hipStream_t)stream,
+                     raw_triangles, keep, n_raw, cube_case, tri_count, tri_offset, vert_ids, vertices, n_vertices, a, table, edge_owner, g);
+  return check_launch(what, (hipStream_t)stream);
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_mesh_compact(int32_t *triangles, int n_triangles, const int32_t *raw_triangles, const uint8_t *keep,
+                                                 const int32_t *keep_offset, int n_raw, curobo_hip_stream_t stream) {
+  const char *what = "mapper_mesh_compact";
+  CUROBO_REQUIRE(triangles && raw_triangles && keep && keep_offset, "%s: no pointer may be null", what);
+  CUROBO_REQUIRE(n_raw > 0 && n_triangles > 0 && n_triangles <= n_raw, "%s: need 0 < n_triangles <= n_raw, got %d and %d", what, n_triangles,
+                 n_raw);
+  hipLaunchKernelGGL(mapper_mesh_compact_kernel, dim3((unsigned)ceil_div(n_raw, kMapThreads)), dim3(kMapThreads), 0, (hipStream_t)stream, triangles,
+                     n_triangles, raw_triangles, keep, keep_offset, n_raw);
   return check_launch(what, (hipStream_t)stream);
 }

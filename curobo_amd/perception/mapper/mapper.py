@@ -3,9 +3,10 @@
 The reference's ``Mapper`` (``perception/mapper/mapper.py``) with the same calls: ``integrate(observation)`` fuses a
 batch of depth images, ``compute_esdf()`` returns the ``VoxelGrid`` that ``SceneData.update_voxel_data`` puts in front of
 the planners.  Where the reference keeps the blocks the camera has seen in a hash table over a pool, this mapper stores the
-whole grid, padded to whole blocks, and keeps one byte per block, "ever visible", for "allocated".  Not built: decay and
-block recycling, static obstacles, lidar, colour and feature channels, ``extract_mesh``, rendering, checkpoints,
-``clear_blocks``, jump flooding, scatter seeding."""
+whole grid, padded to whole blocks, and keeps one byte per block, "ever visible", for "allocated".  ``extract_mesh()`` is the
+reference's third read-out: marching cubes over the ever-visible blocks, as a ``Mesh``.  Not built: decay and block recycling,
+static obstacles, lidar, colour and feature channels, rendering, checkpoints, ``clear_blocks``, jump flooding, scatter
+seeding."""
 
 from __future__ import annotations
 
@@ -16,9 +17,10 @@ import numpy as np
 import torch
 
 from ...backends import mapper as B
-from ...scene.types import VoxelGrid
+from ...scene.types import Mesh, VoxelGrid
 from ...types import CameraObservation
 from ...util.graph_capture import capture_graph
+from . import mc_table
 from .mapper_cfg import MapperCfg
 
 
@@ -74,6 +76,7 @@ class Mapper:
         self._graph = None
         self._frame_count = 0
         self._last_voxel_grid: Optional[VoxelGrid] = None
+        self._mc_tables = None  # (case table, edge owners) on the device, from the first extract_mesh on
 
     # ------------------------------------------------------------------------------------------------ storage
     @property
@@ -224,6 +227,64 @@ class Mapper:
         half = torch.tensor([p.grid_w, p.grid_h, p.grid_d], dtype=torch.float32, device=self._device) * 0.5
         origin = torch.tensor(list(p.origin), dtype=torch.float32, device=self._device)
         return origin + (g + 0.5 - half) * float(p.voxel_size)
+
+    def extract_mesh(self, refine_iterations: int = 2, surface_only: bool = True, level: float = 0.0) -> Mesh:
+        """the iso-surface ``sdf = level`` of the TSDF as a ``Mesh`` named ``"block_sparse_tsdf_mesh"`` in the world frame, its
+        ``vertices``, ``faces``, ``vertex_normals`` and ``vertex_colors`` the device tensors of ``extract_mesh_tensors``"""
+        vertices, triangles, normals, colors = self.extract_mesh_tensors(level=level, surface_only=surface_only, refine_iterations=refine_iterations)
+        return Mesh(name="block_sparse_tsdf_mesh", pose=[0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0], vertices=vertices, faces=triangles,
+                    vertex_normals=normals, vertex_colors=colors)
+
+    def extract_mesh_tensors(self, level: float = 0.0, surface_only: bool = False, refine_iterations: int = 0):
+        """marching cubes over the ever-visible blocks (``csrc/mapper.hip``, the ``mapper_mesh_*`` launches): ``(vertices`` float32
+        [V, 3], ``triangles`` int32 [T, 3], ``normals`` float32 [V, 3], ``colors`` uint8 [V, 3]) on the mapper's device; four
+        ``(0, 3)`` tensors for an empty map or one without a surface.  ``colors`` is all zero: this mapper has no colour channel.
+
+        A cube's corners are eight voxel centres; it is meshed when all eight are observed (weight >= ``minimum_tsdf_weight``, in
+        ever-visible blocks) and their values ``sdf - level`` change sign -- with ``surface_only`` also some ``|sdf - level|`` is below
+        the truncation distance, which leaves out the sign change between free space and the clamped far side of a surface.
+        ``refine_iterations`` Newton steps along the trilinear gradient follow the linear interpolation; the normals are central
+        differences of the nearest voxels.  ``(v1 - v0) x (v2 - v0)`` of a triangle points to the positive (free) side.  Triangles
+        at the rim of the observed region whose neighbour cube is not meshed are dropped, and so are triangles without area, as in
+        the reference.  The order of both lists is (block, voxel, axis or table order) and the same from run to run.
+
+        The sizes depend on the data, so nothing here is captured into a graph: four launches on the current stream, and THREE
+        reads of totals back to the host (the visible blocks; vertices and table triangles; triangles kept)."""
+        p, t, dev = self._params, self._tsdf, self._device
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        empty = (torch.zeros((0, 3), **f32), torch.zeros((0, 3), **i32), torch.zeros((0, 3), **f32), torch.zeros((0, 3), dtype=torch.uint8, device=dev))
+        with torch.cuda.device(dev):
+            visible = t.block_visible[: p.n_blocks] != 0
+            block_list = torch.nonzero(visible).reshape(-1).to(torch.int32)  # read 1: how many blocks (ascending rows)
+            n_slots = int(block_list.numel())
+            if n_slots == 0:
+                return empty
+            if self._mc_tables is None:
+                self._mc_tables = (torch.as_tensor(mc_table.triangle_table(), device=dev).contiguous(),
+                                   torch.as_tensor(mc_table.EDGE_OWNER.astype(np.int8), device=dev).contiguous())
+            table, edge_owner = self._mc_tables
+            n_voxels = n_slots * p.block_voxels
+            cube_case, vert_count, tri_count = (torch.empty(n_voxels, dtype=torch.uint8, device=dev) for _ in range(3))
+            B.mapper_mesh_classify(cube_case, vert_count, tri_count, t.block_data, t.block_visible, block_list, table, p, level, surface_only)
+            vert_end, tri_end = torch.cumsum(vert_count, 0, dtype=torch.int32), torch.cumsum(tri_count, 0, dtype=torch.int32)
+            n_vertices, n_raw = (int(v) for v in torch.stack([vert_end[-1], tri_end[-1]]).tolist())  # read 2
+            if n_vertices == 0 or n_raw == 0:
+                return empty
+            vertices, normals = torch.empty((n_vertices, 3), **f32), torch.empty((n_vertices, 3), **f32)
+            vert_ids = torch.empty((n_voxels, 3), **i32)
+            B.mapper_mesh_vertices(vertices, normals, vert_ids, vert_count, vert_end - vert_count, t.block_data, t.block_visible, block_list, p,
+                                   level, refine_iterations)
+            block_slot = torch.where(visible, torch.cumsum(visible, 0, dtype=torch.int32) - 1, -1).to(torch.int32).contiguous()
+            raw, keep = torch.empty((n_raw, 3), **i32), torch.empty(n_raw, dtype=torch.uint8, device=dev)
+            B.mapper_mesh_triangles(raw, keep, cube_case, tri_count, tri_end - tri_count, vert_ids, vertices, block_list, block_slot, table,
+                                    edge_owner, p)
+            keep_end = torch.cumsum(keep, 0, dtype=torch.int32)
+            n_triangles = int(keep_end[-1].item())  # read 3
+            if n_triangles == 0:
+                return empty
+            triangles = torch.empty((n_triangles, 3), **i32)
+            B.mapper_mesh_compact(triangles, raw, keep, keep_end - keep)
+        return vertices, triangles, normals, torch.zeros((n_vertices, 3), dtype=torch.uint8, device=dev)
 
     def memory_usage_mb(self) -> float:
         t = self._tsdf

@@ -103,21 +103,31 @@ class Sphere(Obstacle):
         return Cuboid(name=self.name, pose=self._need_pose(), dims=[d, d, d], color=self.color, enable=self.enable)
 
 
+def _host_array(a, dtype) -> np.ndarray:
+    """lists, arrays and tensors on any device as a NumPy array"""
+    if hasattr(a, "detach") and hasattr(a, "cpu"):
+        a = a.detach().cpu().numpy()
+    return np.asarray(a, dtype)
+
+
 @dataclass
 class Mesh(Obstacle):
     #: Wavefront OBJ or STL file (``scene.mesh.load_mesh_file``), or ``vertices`` [V, 3] + ``faces`` [F, 3]
     file_path: Optional[str] = None
     vertices: Optional[Any] = None
     faces: Optional[Any] = None
+    #: per-vertex unit normals [V, 3] and colours [V, 3], where the producer has them (``Mapper.extract_mesh``); not read here
+    vertex_normals: Optional[Any] = None
+    vertex_colors: Optional[Any] = None
 
     def __post_init__(self):
         if self.scale is not None and self.vertices is not None:  # as the reference: scaled once, here
-            self.vertices = np.asarray(self.vertices, np.float32) * np.ravel(np.asarray(self.scale, np.float32))
+            self.vertices = _host_array(self.vertices, np.float32) * np.ravel(np.asarray(self.scale, np.float32))
             self.scale = None
 
     def get_mesh_data(self) -> Tuple[np.ndarray, np.ndarray]:
         if self.vertices is not None:
-            return np.asarray(self.vertices, np.float32), np.asarray(self.faces, np.int32).reshape(-1, 3)
+            return _host_array(self.vertices, np.float32), _host_array(self.faces, np.int32).reshape(-1, 3)
         from .mesh import load_mesh_file
 
         v, f = load_mesh_file(self.file_path)

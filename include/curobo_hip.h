@@ -1052,7 +1052,8 @@ int curobo_hip_pose_icp_select(int32_t *out_index, float *out_error, float *out_
  * (bz nby + by) nbx + bx, block_data fp16 [n_blocks][block_size^3][2] = (sum sdf w, sum w) at local index
  * lz BS^2 + ly BS + lx, and one byte per block: block_mask "ever visible" (the reference's "allocated"), frame_mask
  * "visible in this frame".  Voxel centre = origin + (g + 0.5 - N / 2) voxel_size.  No launch uses an atomic; every launch
- * has dimensions fixed by the shapes alone.  The struct is read on the HOST at launch. */
+ * has dimensions fixed by the shapes alone (the mesh launches further down: by the number of visible blocks as well).  The
+ * struct is read on the HOST at launch. */
 typedef struct curobo_hip_mapper_params {
   int32_t grid_w, grid_h, grid_d;   /* voxels along x, y, z */
   int32_t block_size;               /* 1 or a power of two in 2..32 */
@@ -1116,6 +1117,54 @@ int curobo_hip_mapper_esdf_distance(void *distance, const int32_t *sites, const 
 int curobo_hip_mapper_occupied_flags(uint8_t *flags, const void *block_data, const uint8_t *block_mask,
                                      const curobo_hip_mapper_params *params, int surface_only, float sdf_threshold,
                                      curobo_hip_stream_t stream);
+
+/* ---- mesh extraction: marching cubes over the ever-visible blocks (reference kernel/builder/builder_mesh.py,
+ * builder_raycast.py :63-375, marching_cubes/kernel/wp_mc_common.py :464-489, wp_mc_filter.py).  block_list int32 [n_slots]
+ * holds the rows of the ever-visible blocks in ascending order, block_slot int32 [n_blocks] the slot of a block or -1.
+ * Per-voxel arrays are [n_slots][block_size^3] in the order (slot, voxel local index): scratch grows with the visible
+ * blocks, never with the grid.  A voxel is valid iff it lies in the PADDED grid, its block is ever visible and its weight
+ * >= minimum_tsdf_weight; its value is s = sum / weight - level.  Cube g has corners 0..7 at the voxels g + (0,0,0) (1,0,0)
+ * (1,1,0) (0,1,0) (0,0,1) (1,0,1) (1,1,1) (0,1,1) and edges 0..11 = 0-1 1-2 2-3 3-0 4-5 5-6 6-7 7-4 0-4 1-5 2-6 3-7.  The
+ * four launches run in this order; between them the caller turns counts into exclusive prefix sums and reads the totals.
+ * No launch uses an atomic: the output order is (block row, voxel local index, then axis x y z / table order).
+ *
+ * classify: one workgroup per (slot, tile of min(block_size, 8)^3 cubes), the tile's corner values once in LDS.  A cube is
+ * a surface cube iff all eight corners are valid, some s > 0, some s < 0 and, with surface_only, some |s| < truncation.
+ * cube_case = sum of (s_c < 0) << c for a surface cube, else 0; vert_count = how many of its own edges 0, 3, 8 are cut
+ * (exactly one end negative); tri_count = the triangles of row cube_case of table int8 [256][16] (edge triples, then -1). */
+int curobo_hip_mapper_mesh_classify(uint8_t *cube_case, uint8_t *vert_count, uint8_t *tri_count, const void *block_data,
+                                    const uint8_t *block_mask, const int32_t *block_list, int n_slots, const int8_t *table,
+                                    const curobo_hip_mapper_params *params, float level, int surface_only,
+                                    curobo_hip_stream_t stream);
+
+/* One lane per voxel.  vert_offset int32: the exclusive prefix sum of vert_count, n_vertices its total.  The vertex of a cut
+ * edge a-b is p_a + clamp(-s_a / (s_b - s_a), 0, 1) (p_b - p_a), p the voxel CENTRES; then refine_iterations times: a
+ * trilinear sample at the vertex (lower corner floor(v - 0.5) of the continuous coordinate v, an invalid corner counts as the
+ * truncation distance, no valid corner = invalid); stop when it is invalid, |sdf - level| < 1e-6 or sdf - level > 100; else
+ * step clamp(sdf - level, +-voxel_size / 2) against the normalised central difference of six trilinear samples at
+ * +-voxel_size ((0, 0, 1) where one is invalid or the magnitude is below 1e-6).  normals: the same difference of six
+ * nearest-voxel samples (voxel floor(v)) at the final position.  vertices, normals float [n_vertices][3]; vert_ids int32
+ * [n_slots][block_size^3][3]: the voxel's vertices along x, y, z, -1 where it emits none. */
+int curobo_hip_mapper_mesh_vertices(float *vertices, float *normals, int32_t *vert_ids, int n_vertices, const uint8_t *vert_count,
+                                    const int32_t *vert_offset, const void *block_data, const uint8_t *block_mask,
+                                    const int32_t *block_list, int n_slots, const curobo_hip_mapper_params *params, float level,
+                                    int refine_iterations, curobo_hip_stream_t stream);
+
+/* One lane per voxel.  tri_offset int32: the exclusive prefix sum of tri_count, n_raw its total.  Every triangle of the
+ * cube's table row goes to raw_triangles int32 [n_raw][3]: a corner on edge e is vertex axis of the cube g + (dx, dy, dz),
+ * (dx, dy, dz, axis) = edge_owner int8 [12][4], or -1 where that cube is outside the padded grid, in a block never visible,
+ * or emits no such vertex.  keep uint8 [n_raw] = 1 iff the three are there, all different, and |(v1 - v0) x (v2 - v0)|^2 >
+ * (voxel_size 1e-6)^2.  (v1 - v0) x (v2 - v0) points to the positive side when the table's rows do. */
+int curobo_hip_mapper_mesh_triangles(int32_t *raw_triangles, uint8_t *keep, int n_raw, const uint8_t *cube_case,
+                                     const uint8_t *tri_count, const int32_t *tri_offset, const int32_t *vert_ids,
+                                     const float *vertices, int n_vertices, const int32_t *block_list, const int32_t *block_slot,
+                                     int n_slots, const int8_t *table, const int8_t *edge_owner,
+                                     const curobo_hip_mapper_params *params, curobo_hip_stream_t stream);
+
+/* One lane per raw triangle: triangles int32 [n_triangles][3] = the raw triangles with keep != 0, in their order;
+ * keep_offset int32 [n_raw]: the exclusive prefix sum of keep, n_triangles its total. */
+int curobo_hip_mapper_mesh_compact(int32_t *triangles, int n_triangles, const int32_t *raw_triangles, const uint8_t *keep,
+                                   const int32_t *keep_offset, int n_raw, curobo_hip_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,8 @@
 integrate: one 480 x 640 frame into the default map of the reference, 2 m at 5 mm = 400^3 voxels in blocks of 4 (256 MB dense),
 split into the frame-mask clear, the marking stage and the voxel stage.  compute_esdf: the captured chain at 128^3 and 256^3
 cells over the same map, and its five launches one by one.  Device events around repeated launches after a warm-up, the median
-of the rounds.  Beside each time the bytes the stage has to move (computed from the shapes and the visible-block count; the
+of the rounds.  extract_mesh: the whole call on that map after its one frame, by the host's clock (it reads three totals back, so
+the call ends synchronised), without and with two refinement steps.  Beside each time the bytes the stage has to move (computed from the shapes and the visible-block count; the
 definitions are in the code) and what share of the 6.29 TB/s a float4 copy reaches on this part that is."""
 import argparse
 import json
@@ -41,6 +42,19 @@ def timed(fn, reps=20, rounds=5, warmup=3):
         b.record()
         b.synchronize()
         out.append(a.elapsed_time(b) / reps)
+    return float(np.median(out))
+
+
+def wall_ms(fn, reps=5):
+    """a call that synchronises by itself: the host's clock, the median of ``reps`` calls after one"""
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
     return float(np.median(out))
 
 
@@ -83,6 +97,11 @@ def main():
                 # every mask byte read, the visible blocks' words read and written
                 "voxels": stage(timed(lambda: B.mapper_integrate(ts.block_data, ts.frame_visible, d, k, pos, q, p)), blocks + visible * bs3 * 8),
                 "whole_call": {"ms": round(timed(lambda: m.integrate(obs)), 4)}}
+            vertices, triangles, _, _ = m.extract_mesh_tensors()
+            result["extract_mesh"] = {"visible_blocks": stats["visible_blocks"], "vertices": int(vertices.shape[0]), "triangles": int(triangles.shape[0]),
+                                      "ms": round(wall_ms(lambda: m.extract_mesh_tensors()), 3),
+                                      "ms_two_refinement_steps": round(wall_ms(lambda: m.extract_mesh_tensors(refine_iterations=2)), 3),
+                                      "ms_surface_only": round(wall_ms(lambda: m.extract_mesh_tensors(surface_only=True)), 3)}
         shape = m.esdf_grid_shape
         cells = int(np.prod(shape))
         m.compute_esdf()
