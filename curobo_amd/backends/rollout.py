@@ -63,11 +63,17 @@ def _rollout_trajectory(fn, terms, with_terms,
     sweep_steps: int = 0,
     enable_speed_metric: bool = False,
     dispatch: Optional["DispatchOrder"] = None,
+    memo: Optional[tuple] = None,
 ):
     num_pairs = 0 if pair_locations is None else int(pair_locations.shape[0])
     lanes = getattr(pair_locations, "_self_lane_lists", None)
     ws, phase = (None, 0) if dispatch is None else dispatch.next(batch_size)
     extra = ((None if terms is None else C.addressof(terms)),) if with_terms else ()
+    if memo is not None:  # the *_reuse entry point of ``fn``: (x, cost, grad, stride[, slot]) behind the shared arguments
+        lib = load()
+        fn = lib.curobo_hip_rollout_trajopt_fused_reuse if with_terms else lib.curobo_hip_rollout_trajectory_fused_reuse
+        memo_x, memo_cost, memo_grad, memo_stride = memo[:4]
+        extra += (ptr(memo_x), ptr(memo_cost), ptr(memo_grad), int(memo_stride), int(memo[4]) if len(memo) > 4 else 0)
     check(fn(
         ptr(out_cost), ptr(out_grad_knots), ptr(out_position), ptr(out_robot_spheres), ptr(u_position),
         ptr(start_position), ptr(start_velocity), ptr(start_acceleration), ptr(start_jerk),
@@ -150,9 +156,16 @@ def rollout_trajectory_fused(
     sweep_steps: int = 0,
     enable_speed_metric: bool = False,
     dispatch: Optional["DispatchOrder"] = None,
+    memo: Optional[tuple] = None,
 ):
-    """cost[b], grad_knots[b, n_knots, dof] of ``batch_size`` B-spline trajectories in one launch."""
-    return _rollout_trajectory(load().curobo_hip_rollout_trajectory_fused, None, False, out_cost, out_grad_knots, out_position, out_robot_spheres, u_position, start_position, start_velocity, start_acceleration, start_jerk, goal_position, goal_velocity, goal_acceleration, goal_jerk, start_idx, goal_idx, traj_dt, use_implicit_goal_state, fixed_transform, robot_spheres, joint_map_type, joint_map, link_map, link_sphere_map, link_chain_data, link_chain_offsets, joint_offset_map, sphere_padding, self_collision_weight, pair_locations, scene, scene_collision_weight, activation_distance, speed_dt, env_query_idx, num_envs, use_multi_env, batch_size, padded_horizon, dof, n_knots, bspline_degree, sweep_steps, enable_speed_metric, dispatch)
+    """cost[b], grad_knots[b, n_knots, dof] of ``batch_size`` B-spline trajectories in one launch.
+
+    ``memo = (x, cost, grad, stride[, slot])``: evaluations the caller already holds
+    (``curobo_hip_rollout_trajectory_fused_reuse``).  Trajectory ``b`` with ``b % stride == slot`` (slot 0 when omitted)
+    whose knots equal ``x[b // stride]`` bit for bit gets ``cost[b // stride]`` / ``grad[b // stride]`` copied instead of
+    a rollout; any difference means a full evaluation.  The caller guarantees that the memo rows were computed with the
+    start / goal state, dt, environment, scene and weights their trajectories have now."""
+    return _rollout_trajectory(load().curobo_hip_rollout_trajectory_fused, None, False, out_cost, out_grad_knots, out_position, out_robot_spheres, u_position, start_position, start_velocity, start_acceleration, start_jerk, goal_position, goal_velocity, goal_acceleration, goal_jerk, start_idx, goal_idx, traj_dt, use_implicit_goal_state, fixed_transform, robot_spheres, joint_map_type, joint_map, link_map, link_sphere_map, link_chain_data, link_chain_offsets, joint_offset_map, sphere_padding, self_collision_weight, pair_locations, scene, scene_collision_weight, activation_distance, speed_dt, env_query_idx, num_envs, use_multi_env, batch_size, padded_horizon, dof, n_knots, bspline_degree, sweep_steps, enable_speed_metric, dispatch, memo)
 
 
 FUSED_LDS_LIMIT = 160 * 1024
@@ -234,7 +247,8 @@ def make_trajopt_terms(**tensors) -> TrajOptTerms:
 def rollout_trajopt_fused(terms: Optional[TrajOptTerms], *args, **kwargs):
     """``rollout_trajectory_fused`` plus the optional tool-pose and c-space STATE terms of the
     reference trajopt task in the same launch (``curobo_hip_rollout_trajopt_fused``).  Positional
-    arguments after ``terms`` are those of :func:`rollout_trajectory_fused`."""
+    arguments after ``terms`` are those of :func:`rollout_trajectory_fused` (``memo=`` included:
+    ``curobo_hip_rollout_trajopt_fused_reuse``)."""
     return _rollout_trajectory(load().curobo_hip_rollout_trajopt_fused, terms, True, *args, **kwargs)
 
 

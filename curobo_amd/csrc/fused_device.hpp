@@ -81,6 +81,12 @@ struct FusedTrajArgs {
   int dispatch_phase;
   int scene_rows;  // development knob: one sphere per lane in the scene pass (CUROBO_HIP_SCENE_ROWS)
   long long *prof;  // optional [B][16] wall-clock ticks (100 MHz) at the phase boundaries, see set_profile_buffer
+  // optional reuse of evaluations the caller already holds (see fused_reuse_known_row): trajectory b with
+  // b % memo_stride == memo_slot whose knots have the bits of memo_x[b / memo_stride] gets memo_cost / memo_grad of that row
+  const float *memo_x;     // [B / memo_stride][n_knots * D]
+  const float *memo_cost;  // [B / memo_stride]
+  const float *memo_grad;  // [B / memo_stride][n_knots * D]
+  int memo_stride, memo_slot;
 };
 
 // LDS carve (floats unless noted), per workgroup:
@@ -1024,8 +1030,47 @@ __device__ __forceinline__ void rebuild_dispatch_order(int32_t *ws, int B, int p
   }
 }
 
+// What a trajectory workgroup owes the longest-first dispatch when it ends: its duration and, in one workgroup of the
+// launch, the order the next launch uses.  (The barrier: the LDS the sort takes over is the finished rollout's.)
+__device__ __forceinline__ void fused_dispatch_epilogue(long long t_begin, int b, float *smem, int tid, int nt) {
+  int32_t *const ws = kernarg_block<int32_t *>(offsetof(FusedTrajArgs, dispatch_ws));
+  const int phase = kernarg_block<int>(offsetof(FusedTrajArgs, dispatch_phase)), n_traj = kernarg_block<int>(offsetof(FusedTrajArgs, batch));
+  if (tid == 0) ws[(size_t)(2 + phase) * n_traj + b] = (int)(wall_clock64() - t_begin);
+  if (blockIdx.x == (gridDim.x - 1) / 2) {
+    __syncthreads();
+    rebuild_dispatch_order(ws, n_traj, phase, reinterpret_cast<int *>(smem), tid, nt);
+  }
+}
+
+// Reuse of an evaluation the caller already holds.  A line search with a zero step among its candidates submits the point it
+// kept once more (candidate 0 = x + 0 * d, whose cost and gradient the previous launch computed), and the launch is a pure
+// function of its inputs: a trajectory whose knots have the BITS of the row the caller names gets that row's cost and gradient
+// copied, and its workgroup ends after two global round trips instead of a rollout.  The knots are compared as 32-bit
+// integers -- equal NaN payloads are equal, -0.0 is not +0.0, no special case -- and any difference means "evaluate": a scale
+// list without a zero, a non-finite direction or a caller's mistake cost time, never a result.  What the comparison cannot
+// see (start and goal state, dt, scene of trajectory b = those of the memo row) is the caller's contract.  Every wavefront
+// compares the whole row for itself (a few hundred bytes): the decision is uniform over the workgroup without a barrier.
+// The fields are read from the argument segment here (kernarg_block), so they occupy no register past this point.
+// Returns true when out_cost[b] / out_grad_knots[b] are written.
+__device__ __forceinline__ bool fused_reuse_known_row(int b, const float *knots, int n, int tid, int nt) {
+  const uint32_t *const memo_x = kernarg_block<const uint32_t *>(offsetof(FusedTrajArgs, memo_x));
+  if (memo_x == nullptr) return false;
+  const int stride = kernarg_block<int>(offsetof(FusedTrajArgs, memo_stride)), slot = kernarg_block<int>(offsetof(FusedTrajArgs, memo_slot));
+  const int row = b / stride;
+  if (b - row * stride != slot) return false;
+  const uint32_t *const x = reinterpret_cast<const uint32_t *>(knots) + (size_t)b * n, *const m = memo_x + (size_t)row * n;
+  uint32_t diff = 0u;
+  for (int e = tid & 63; e < n; e += 64) diff |= x[e] ^ m[e];
+  if (__ballot(diff != 0u) != 0ull) return false;
+  const uint32_t *const memo_grad = kernarg_block<const uint32_t *>(offsetof(FusedTrajArgs, memo_grad));
+  uint32_t *const out_grad = kernarg_block<uint32_t *>(offsetof(FusedTrajArgs, out_grad_knots));
+  for (int e = tid; e < n; e += nt) out_grad[(size_t)b * n + e] = memo_grad[(size_t)row * n + e];
+  if (tid == 0) kernarg_block<uint32_t *>(offsetof(FusedTrajArgs, out_cost))[b] = kernarg_block<const uint32_t *>(offsetof(FusedTrajArgs, memo_cost))[row];
+  return true;
+}
+
 #ifdef CUROBO_FUSED_STAMP_TERMS
-constexpr bool kStampTerms = true;  // diagnostic builds only: the stamps cost the TERMS variant registers
+constexpr bool kStampTerms = true; // diagnostic builds only: the stamps cost the TERMS variant registers
 #else
 constexpr bool kStampTerms = false;
 #endif
@@ -1073,6 +1118,18 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
   const bool reorder = a.dispatch_ws != nullptr;
   const int b = reorder ? a.dispatch_ws[(size_t)a.dispatch_phase * a.batch + blockIdx.x] : (int)blockIdx.x;
   const long long t_begin = reorder ? wall_clock64() : 0ll;
+  // a trajectory the caller already holds the result of (keyed by b, never by blockIdx) ends here, its dispatch duties done
+  const bool stamp_rows = (!TERMS || kStampTerms) && a.prof != nullptr;
+  const long long t_known = stamp_rows ? wall_clock64() : 0ll;
+  if (fused_reuse_known_row(b, a.bs.u, a.bs.n_knots * D, tid, nt)) {
+    if (stamp_rows && tid == 0) {  // (profile stamps: the phases of a copied row are empty, every boundary after the first is its end)
+      const long long t_end = wall_clock64();
+      a.prof[(size_t)b * 16] = t_known;
+      for (int i = 1; i < 16; i++) a.prof[(size_t)b * 16 + i] = t_end;
+    }
+    if (reorder) fused_dispatch_epilogue(t_begin, b, smem, tid, nt);
+    return;
+  }
   FusedCtx c;
   fused_ctx_carve(c, smem, lay, H, D, L, S, P);
   if (use_lanes) { c.g_pairs = reinterpret_cast<const uint32_t *>(a.pairs); c.lane_len0 = a.lane_len0; c.lane_len1 = a.lane_len1; }
@@ -1540,15 +1597,7 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
   }
   CUROBO_STAMP(4);
 #undef CUROBO_STAMP
-  if (reorder) {
-    int32_t *const ws = kernarg_block<int32_t *>(offsetof(FusedTrajArgs, dispatch_ws));
-    const int phase = kernarg_block<int>(offsetof(FusedTrajArgs, dispatch_phase)), n_traj = kernarg_block<int>(offsetof(FusedTrajArgs, batch));
-    if (tid3 == 0) ws[(size_t)(2 + phase) * n_traj + b] = (int)(wall_clock64() - t_begin);
-    if (blockIdx.x == (gridDim.x - 1) / 2) {
-      __syncthreads();
-      rebuild_dispatch_order(ws, n_traj, phase, reinterpret_cast<int *>(smem), tid3, nt);
-    }
-  }
+  if (reorder) fused_dispatch_epilogue(t_begin, b, smem, tid3, nt);
 }
 
 // ---- compile-time shapes (fused_shapes.hpp): the host predicates their launchers share

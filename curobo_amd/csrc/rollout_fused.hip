@@ -167,6 +167,12 @@ CUROBO_EXPORT int curobo_hip_rollout_fused_shape_id(int padded_horizon, int n_kn
   return 0;
 }
 
+// the optional reuse arguments of the *_reuse entry points (FusedTrajArgs::memo_*); all NULL = every trajectory is evaluated
+struct FusedReuse {
+  const float *x, *cost, *grad;
+  int stride, slot;
+};
+
 static int rollout_trajectory_fused_impl(
     const char *what, const curobo_hip_trajopt_terms *terms,
     float *out_cost, float *out_grad_knots, float *out_position, float *out_robot_spheres, const float *u_position,
@@ -181,7 +187,7 @@ static int rollout_trajectory_fused_impl(
     const int32_t *env_query_idx, int num_envs, int use_multi_env, int batch_size, int padded_horizon, int dof,
     int n_knots, int bspline_degree, int num_links, int num_spheres, int num_collision_pairs, int link_chain_len,
     int sweep_steps, int enable_speed_metric, int32_t *dispatch_ws, int dispatch_phase, const uint32_t *self_lane_lists,
-    int self_lane_len, curobo_hip_stream_t stream) {
+    int self_lane_len, const FusedReuse &reuse, curobo_hip_stream_t stream) {
   CUROBO_REQUIRE(bspline_degree >= 3 && bspline_degree <= 5, "%s: bspline_degree must be 3, 4 or 5", what);
   CUROBO_REQUIRE(sweep_steps == 0 || sweep_steps == 3, "%s: sweep_steps must be 0 or 3", what);
   CUROBO_REQUIRE(num_links >= 1 && num_links <= 128 && dof >= 1 && padded_horizon >= 2 && n_knots >= 1,
@@ -189,6 +195,18 @@ static int rollout_trajectory_fused_impl(
   CUROBO_REQUIRE(num_spheres < 4096, "%s: at most 4095 spheres", what);
   CUROBO_REQUIRE(link_chain_len >= 1, "%s: link_chain_len must be >= 1", what);
   CUROBO_REQUIRE(((uintptr_t)pair_locations & 3) == 0, "%s: pair_locations must be 4-byte aligned", what);
+  const bool any_memo = reuse.x || reuse.cost || reuse.grad;
+  if (any_memo) {
+    CUROBO_REQUIRE(reuse.x && reuse.cost && reuse.grad, "%s: memo_x, memo_cost and memo_grad must be given together (all three or none)", what);
+    CUROBO_REQUIRE(reuse.stride >= 1, "%s: memo_stride must be >= 1", what);
+    CUROBO_REQUIRE(reuse.slot >= 0 && reuse.slot < reuse.stride, "%s: memo_slot must be in [0, memo_stride)", what);
+    CUROBO_REQUIRE(batch_size % reuse.stride == 0, "%s: batch_size must be a multiple of memo_stride", what);
+    // a copied row has no positions, spheres or per-term values to write
+    const bool term_outputs = terms && (terms->out_pose_distance || terms->out_position_distance || terms->out_rotation_distance ||
+                                        terms->out_goalset_idx || terms->out_cspace_cost);
+    CUROBO_REQUIRE(!out_position && !out_robot_spheres && !term_outputs,
+                   "%s: reuse (memo_x) with materialised outputs (out_position, out_robot_spheres, per-term outputs)", what);
+  }
   if (batch_size == 0) return CUROBO_HIP_OK;
   FusedTrajArgs a{};
   a.out_cost = out_cost; a.out_grad_knots = out_grad_knots; a.out_position = out_position;
@@ -213,6 +231,7 @@ static int rollout_trajectory_fused_impl(
   if (g_fused_prof_seq && g_fused_prof_next < g_fused_prof_blocks && batch_size <= g_fused_prof_rows)
     a.prof = g_fused_prof_seq + (size_t)g_fused_prof_next++ * g_fused_prof_rows * 16;
   a.dispatch_ws = dispatch_ws; a.dispatch_phase = dispatch_phase;
+  if (any_memo) { a.memo_x = reuse.x; a.memo_cost = reuse.cost; a.memo_grad = reuse.grad; a.memo_stride = reuse.stride; a.memo_slot = reuse.slot; }
   static const bool no_lanes = getenv("CUROBO_HIP_SELF_ROWS") != nullptr;  // development knob: the row form of the pair pass
   if (self_lane_lists && a.use_self && !no_lanes) {
     a.lane_lists = self_lane_lists; a.lane_len0 = self_lane_len & 0xffff; a.lane_len1 = (self_lane_len >> 16) & 0xffff;
@@ -467,13 +486,28 @@ CUROBO_EXPORT int curobo_hip_self_lane_lists_host(uint32_t *out_lists_host, int 
 }
 
 CUROBO_EXPORT int curobo_hip_rollout_trajectory_fused(CUROBO_TRAJ_PARAMS, curobo_hip_stream_t stream) {
-  return rollout_trajectory_fused_impl("rollout_trajectory_fused", nullptr, CUROBO_TRAJ_ARGS, stream);
+  return rollout_trajectory_fused_impl("rollout_trajectory_fused", nullptr, CUROBO_TRAJ_ARGS, FusedReuse{}, stream);
 }
 
 CUROBO_EXPORT int curobo_hip_rollout_trajopt_fused(CUROBO_TRAJ_PARAMS, const curobo_hip_trajopt_terms *terms,
                                                    curobo_hip_stream_t stream) {
-  return rollout_trajectory_fused_impl("rollout_trajopt_fused", terms, CUROBO_TRAJ_ARGS, stream);
+  return rollout_trajectory_fused_impl("rollout_trajopt_fused", terms, CUROBO_TRAJ_ARGS, FusedReuse{}, stream);
 }
+
+// The same two launches with reuse of evaluations the caller holds (fused_reuse_known_row): trajectories b with
+// b % memo_stride == memo_slot whose knots have the bits of memo_x[b / memo_stride] get memo_cost / memo_grad of that row.
+#define CUROBO_REUSE_PARAMS const float *memo_x, const float *memo_cost, const float *memo_grad, int memo_stride, int memo_slot
+#define CUROBO_REUSE_ARGS FusedReuse{memo_x, memo_cost, memo_grad, memo_stride, memo_slot}
+CUROBO_EXPORT int curobo_hip_rollout_trajectory_fused_reuse(CUROBO_TRAJ_PARAMS, CUROBO_REUSE_PARAMS, curobo_hip_stream_t stream) {
+  return rollout_trajectory_fused_impl("rollout_trajectory_fused_reuse", nullptr, CUROBO_TRAJ_ARGS, CUROBO_REUSE_ARGS, stream);
+}
+
+CUROBO_EXPORT int curobo_hip_rollout_trajopt_fused_reuse(CUROBO_TRAJ_PARAMS, const curobo_hip_trajopt_terms *terms, CUROBO_REUSE_PARAMS,
+                                                         curobo_hip_stream_t stream) {
+  return rollout_trajectory_fused_impl("rollout_trajopt_fused_reuse", terms, CUROBO_TRAJ_ARGS, CUROBO_REUSE_ARGS, stream);
+}
+#undef CUROBO_REUSE_PARAMS
+#undef CUROBO_REUSE_ARGS
 #undef CUROBO_TRAJ_PARAMS
 #undef CUROBO_TRAJ_ARGS
 

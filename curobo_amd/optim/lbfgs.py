@@ -54,6 +54,13 @@ class LBFGSOptCfg:
     #: line search + two-loop + next candidates in one launch (opt_dim <= 128); False = the three
     #: drop-in launches of the reference's iteration
     fused_tail: bool = True
+    #: candidate 0 of an iteration is the exploration point the line search just kept whenever ``line_search_scale[0] == 0``
+    #: (x + 0 * d), and its cost and gradient sit in the exploration buffers: a rollout that offers reuse
+    #: (``offers_reuse`` of the rollout classes) copies them instead of evaluating that trajectory again -- one in four of an
+    #: iteration's evaluations with the default scale list, bit for bit the same iterates.  THE CONTRACT: whatever the rollout
+    #: reads besides the knots (scene, start and goal states, dt, weights) does not change between ``reinitialize`` and the last
+    #: iteration of an optimisation.  False = every candidate is evaluated (the reference's iteration).
+    reuse_exploration_point: bool = True
 
     def improvement_thresholds(self) -> Tuple[float, float]:
         """(cost_delta_threshold, cost_relative_threshold) as the kernels get them.  Reference optim/gradient/gradient_descent.py:
@@ -79,6 +86,11 @@ class LBFGSOpt:
                  action_bounds: Tuple[torch.Tensor, torch.Tensor], device, use_cuda_graph: bool = True):
         self.cfg = cfg
         self.rollout_fn = cost_and_gradient
+        # the rollout behind a bound ``cost_and_gradient`` that can be told which evaluations the optimiser already holds
+        # (``offers_reuse`` / ``cost_and_gradient(x, memo=...)``); any other callable is evaluated in full
+        owner = getattr(cost_and_gradient, "__self__", None)
+        self._reuse_rollout = owner if (getattr(cost_and_gradient, "__name__", "") == "cost_and_gradient"
+                                        and callable(getattr(owner, "offers_reuse", None))) else None
         self.action_horizon, self.action_dim = action_horizon, action_dim
         self.opt_dim = action_horizon * action_dim
         self.device = device
@@ -124,9 +136,19 @@ class LBFGSOpt:
         self.reset_cuda_graph()
 
     # ------------------------------------------------------------------ one iteration
-    def _evaluate_search_points(self) -> None:
+    def _evaluate_search_points(self, reuse: bool = False) -> None:
+        """``reuse`` (the iterations of ``_opt_step`` only, never ``reinitialize``: its exploration buffers are not yet an
+        evaluation of anything): hand the rollout the exploration point's cost and gradient as the known result of candidate 0
+        (``LBFGSOptCfg.reuse_exploration_point``).  The rollout compares the knots bit for bit, so a candidate 0 that is not
+        the exploration point (a non-finite direction, a -0.0) is simply evaluated."""
         B, N, V = self.num_problems, self.n_linesearch, self.opt_dim
-        cost, grad = self.rollout_fn(self.x_set.view(B * N, V))
+        ro = self._reuse_rollout
+        if (reuse and ro is not None and self.cfg.reuse_exploration_point and float(self.cfg.line_search_scale[0]) == 0.0
+                and ro.offers_reuse(N)):
+            cost, grad = ro.cost_and_gradient(self.x_set.view(B * N, V),
+                                              memo=(self.exploration_action, self.exploration_cost, self.exploration_gradient, N))
+        else:
+            cost, grad = self.rollout_fn(self.x_set.view(B * N, V))
         # The rollout returns its own static output buffers; alias them instead of copying
         # (pointers are stable across calls, so this is also what the captured graph sees).
         if cost.data_ptr() != self.search_cost.data_ptr():
@@ -151,7 +173,7 @@ class LBFGSOpt:
         if self._use_fused_tail:
             # x_set / step_scaled of this iteration were produced by the previous tail (or by
             # reinitialize): rollout, then one launch for everything on the optimiser side
-            self._evaluate_search_points()
+            self._evaluate_search_points(reuse=True)
             optimization_hip.launch_lbfgs_iteration_tail(
                 self.best_cost, self.best_action, self.best_iteration, self.current_iteration, self.converged,
                 cfg.convergence_iteration, *cfg.improvement_thresholds(),
@@ -166,7 +188,7 @@ class LBFGSOpt:
         optimization_hip.prepare_search_points(
             self.x_set, self.step_scaled, self.exploration_action, self.step_direction, self._step_max,
             self._alphas, B, N, V, self.action_dim, apply_scale)
-        self._evaluate_search_points()
+        self._evaluate_search_points(reuse=True)
         optimization_hip.launch_line_search(
             self.best_cost, self.best_action, self.best_iteration, self.current_iteration, self.converged,
             cfg.convergence_iteration, *cfg.improvement_thresholds(),

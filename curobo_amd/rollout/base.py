@@ -255,6 +255,43 @@ class BSplineRolloutBase(RobotRolloutBase):
             self._dispatch = rollout_hip.DispatchOrder(self.batch_size, self.cost.device)
         return self._dispatch
 
+    # ------------------------------------------------------------------ reuse of evaluations the caller holds
+    def _reuse_row_arrays(self):
+        """everything a launch reads PER TRAJECTORY besides the knots (the launch's ``memo`` compares only those)"""
+        return [self.start_idx, self.goal_idx, self.env_query_idx]
+
+    def _reuse_launch_ok(self) -> bool:
+        """``cost_and_gradient`` is the fused launch and materialises nothing (a copied row cannot fill such outputs)"""
+        return False
+
+    def offers_reuse(self, stride: int) -> bool:
+        """Whether ``cost_and_gradient(x, memo=(x_held, cost, grad, stride))`` may serve row ``stride * i`` from held row ``i``
+        (an optimiser: the line-search candidate with step 0 from the exploration point it kept).  A held row is the result of
+        ANOTHER row of the same group of ``stride`` rows, evaluated one launch earlier, so the per-trajectory arrays must be
+        equal within every group: the rollouts fill them by repetition per problem, and that is checked here (one read-back,
+        cached until one of the arrays is written again; never under graph capture, where an unchecked state means no reuse).
+        What the check cannot see is the caller's contract: scene, weights and the start / goal rows themselves stay as
+        they are between the evaluation that produced a held row and the launch that reuses it."""
+        B = self.batch_size
+        if stride < 1 or B == 0 or B % stride != 0 or not self._reuse_launch_ok():
+            return False
+        arrays = self._reuse_row_arrays()
+        key = (stride, B, tuple((t.data_ptr(), t._version) for t in arrays))
+        if getattr(self, "_reuse_key", None) != key:
+            if torch.cuda.is_current_stream_capturing():
+                return False
+            groups = [t.reshape(B // stride, stride, -1) for t in arrays]
+            self._reuse_uniform = all(bool((g == g[:, :1]).all()) for g in groups)
+            self._reuse_key = key
+        return self._reuse_uniform
+
+    def _checked_memo(self, memo):
+        """``memo`` as the launch takes it; a memo this rollout cannot honour is an error, not an evaluation in full"""
+        if memo is not None and not self.offers_reuse(int(memo[3])):
+            raise ValueError("memo: this rollout offers no reuse at this stride (offers_reuse): kernel sequence, materialised "
+                             "outputs, or per-trajectory arrays that differ within a group of rows")
+        return memo
+
 
 class PoseTerms:
     """The tool-pose goal term of a rollout (mixin): goal sets per row, per-frame weight factors / tolerances, one launch."""

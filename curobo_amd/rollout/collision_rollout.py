@@ -187,8 +187,12 @@ class CollisionRollout(BSplineRolloutBase):
             cfg.padded_horizon, self.action_dim, k.num_links, k.num_spheres, n_pairs, int(k.link_chain_data.shape[0]),
             self._obstacle_slots()))
 
-    def cost_and_gradient_fused(self, act_seq: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Same numbers as ``evaluate_action`` + ``backward`` from one kernel launch."""
+    def _reuse_launch_ok(self) -> bool:
+        return self.cfg.use_fused and not self.cfg.fused_materialize and self._fused_chosen()
+
+    def cost_and_gradient_fused(self, act_seq: torch.Tensor, memo: Optional[tuple] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Same numbers as ``evaluate_action`` + ``backward`` from one kernel launch.  ``memo = (x, cost, grad, stride[, slot])``:
+        evaluations the caller holds (``offers_reuse``; ``backends.rollout.rollout_trajectory_fused``)."""
         cfg, k, B = self.cfg, self.kin, self.batch_size
         use_self, use_scene = self._use_self, self._use_scene
         sc = k.self_collision
@@ -201,15 +205,17 @@ class CollisionRollout(BSplineRolloutBase):
             self.scene.struct if use_scene else None, self._w_scene if use_scene else None,
             self._eta, self._speed_dt, self.env_query_idx, k.num_envs, self.use_multi_env, B, cfg.padded_horizon,
             self.action_dim, cfg.n_knots, cfg.bspline_degree, 3 if cfg.use_sweep else 0,
-            cfg.use_sweep and cfg.use_speed_metric, self._dispatch_order())
+            cfg.use_sweep and cfg.use_speed_metric, self._dispatch_order(), memo=self._checked_memo(memo))
         return self.cost, self.grad_knots
 
-    def cost_and_gradient(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """x[B, n_knots*D] -> (cost[B], grad[B, n_knots*D]); buffers are reused every call."""
+    def cost_and_gradient(self, x: torch.Tensor, memo: Optional[tuple] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """x[B, n_knots*D] -> (cost[B], grad[B, n_knots*D]); buffers are reused every call.  Without ``memo`` every
+        trajectory is evaluated; with it (only where ``offers_reuse``) the rows the caller holds are copied."""
         act = x.view(self.batch_size, self.cfg.n_knots, self.action_dim)
         if self.cfg.use_fused and self._fused_chosen():
-            cost, grad = self.cost_and_gradient_fused(act)
+            cost, grad = self.cost_and_gradient_fused(act, memo=memo)
             return cost, grad.view(self.batch_size, -1)
+        self._checked_memo(memo)
         cost = self.evaluate_action(act)
         grad = self.backward()
         return cost, grad.view(self.batch_size, -1)

@@ -331,9 +331,23 @@ class TrajOptRollout(PoseTerms, BSplineRolloutBase):
             ok = rollout_hip.rollout_trajopt_fused_torque_fits(*shape)
         return ok
 
-    def cost_and_gradient_fused(self, act_seq: torch.Tensor, with_metrics: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _reuse_row_arrays(self):
+        # (row b tracks _cs_target[b]: _cs_target_idx is the identity)
+        return super()._reuse_row_arrays() + [self.idxs_goal, self.state_dt, self._cs_target]
+
+    def _fused_too_big(self) -> bool:
+        """with torque limits the fused launch loses to the kernel sequence and its side stream beyond fused_torque_max_batch"""
+        c = self.cfg
+        return c.use_torque_limits and c.overlap_dynamics and self.batch_size > c.fused_torque_max_batch
+
+    def _reuse_launch_ok(self) -> bool:
+        return self.cfg.use_fused and self._fused_chosen(veto=self._fused_too_big())
+
+    def cost_and_gradient_fused(self, act_seq: torch.Tensor, with_metrics: bool = False,
+                                memo: Optional[tuple] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Same numbers as ``evaluate_action`` from one launch (the struct of optional terms is
-        rebuilt per call: it only holds pointers of the static buffers)."""
+        rebuilt per call: it only holds pointers of the static buffers).  ``memo = (x, cost, grad, stride[, slot])``:
+        evaluations the caller holds (``offers_reuse``; not together with ``with_metrics``, which a copied row cannot fill)."""
         k, c, B = self.kin, self.cfg, self.batch_size
         sc, m = k.self_collision, with_metrics
         use_scene = self.scene is not None
@@ -364,15 +378,15 @@ class TrajOptRollout(PoseTerms, BSplineRolloutBase):
             sc.collision_pairs, self.scene.struct if use_scene else None, self._w_scene if use_scene else None,
             self._eta_scene, self._speed_dt, self.env_query_idx, k.num_envs, self.use_multi_env, B, c.padded_horizon, self.action_dim,
             c.n_knots, c.bspline_degree, 3 if c.use_sweep else 0, c.use_sweep and c.use_speed_metric,
-            dispatch=self._dispatch_order())
+            dispatch=self._dispatch_order(), memo=self._checked_memo(memo))
         return self.cost, self.grad_knots.view(B, -1)
 
-    def cost_and_gradient(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def cost_and_gradient(self, x: torch.Tensor, memo: Optional[tuple] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Without ``memo`` every trajectory is evaluated; with it (only where ``offers_reuse``) held rows are copied."""
         c = self.cfg
         act = x.view(self.batch_size, c.n_knots, self.action_dim)
-        # (with torque limits the fused launch loses to the kernel sequence and its side stream beyond fused_torque_max_batch)
-        too_big = c.use_torque_limits and c.overlap_dynamics and self.batch_size > c.fused_torque_max_batch
-        if c.use_fused and self._fused_chosen(veto=too_big):
-            return self.cost_and_gradient_fused(act)
+        if c.use_fused and self._fused_chosen(veto=self._fused_too_big()):
+            return self.cost_and_gradient_fused(act, memo=memo)
+        self._checked_memo(memo)
         cost = self.evaluate_action(act, with_gradient=True)
         return cost, self.grad_knots.view(self.batch_size, -1)

@@ -661,6 +661,58 @@ int curobo_hip_rollout_trajopt_fused(
     int dispatch_phase, const uint32_t *self_lane_lists, int self_lane_len, const curobo_hip_trajopt_terms *terms,
     curobo_hip_stream_t stream);
 
+/* The two launches above with reuse of evaluations the caller already holds.  The launch is a pure function of its inputs, so
+ * a trajectory b with b % memo_stride == memo_slot whose knots u_position[b] equal memo_x[b / memo_stride] bit for bit (compared
+ * as 32-bit integers: equal NaN payloads are equal, -0.0 is not +0.0) gets out_cost[b] = memo_cost[b / memo_stride] and
+ * out_grad_knots[b] = memo_grad[b / memo_stride] instead of a rollout; every other trajectory, and every trajectory whose knots
+ * differ in any bit, is evaluated in full.  memo_x / memo_grad [batch_size / memo_stride, n_knots * dof], memo_cost
+ * [batch_size / memo_stride]; all three NULL = the functions above.  THE CALLER'S CONTRACT: the memo row holds what this launch
+ * would compute, i.e. it was produced by an earlier launch with the same scene, weights and robot, and with the start / goal
+ * state, dt and environment that trajectory b has now (an L-BFGS line search whose first step magnitude is 0: the point it kept
+ * is candidate 0 of the next iteration).  Rejected (CUROBO_HIP_ERR_INVALID) before any launch: only some of the three pointers,
+ * memo_stride < 1, memo_slot outside [0, memo_stride), batch_size not a multiple of memo_stride, and reuse together with any
+ * materialised output (out_position, out_robot_spheres, the per-term outputs of curobo_hip_trajopt_terms): a copied row cannot
+ * fill those.  Reference: none (its optimiser re-evaluates the kept point, optim/components/gradient_opt_core.py:445-480). */
+int curobo_hip_rollout_trajectory_fused_reuse(
+    float *out_cost, float *out_grad_knots, float *out_position, float *out_robot_spheres,
+    const float *u_position, const float *start_position, const float *start_velocity,
+    const float *start_acceleration, const float *start_jerk, const float *goal_position,
+    const float *goal_velocity, const float *goal_acceleration, const float *goal_jerk,
+    const int32_t *start_idx, const int32_t *goal_idx, const float *traj_dt,
+    const uint8_t *use_implicit_goal_state, const float *fixed_transform,
+    const float *robot_spheres, const int8_t *joint_map_type, const int16_t *joint_map,
+    const int16_t *link_map, const int16_t *link_sphere_map, const int16_t *link_chain_data,
+    const int16_t *link_chain_offsets, const float *joint_offset_map, const float *sphere_padding,
+    const float *self_collision_weight, const int16_t *pair_locations,
+    const curobo_hip_scene *scene, const float *scene_collision_weight,
+    const float *activation_distance, const float *speed_dt, const int32_t *env_query_idx,
+    int num_envs, int use_multi_env, int batch_size, int padded_horizon, int dof, int n_knots,
+    int bspline_degree, int num_links, int num_spheres, int num_collision_pairs,
+    int link_chain_len, int sweep_steps, int enable_speed_metric, int32_t *dispatch_ws,
+    int dispatch_phase, const uint32_t *self_lane_lists, int self_lane_len,
+    const float *memo_x, const float *memo_cost, const float *memo_grad, int memo_stride, int memo_slot,
+    curobo_hip_stream_t stream);
+
+int curobo_hip_rollout_trajopt_fused_reuse(
+    float *out_cost, float *out_grad_knots, float *out_position, float *out_robot_spheres,
+    const float *u_position, const float *start_position, const float *start_velocity,
+    const float *start_acceleration, const float *start_jerk, const float *goal_position,
+    const float *goal_velocity, const float *goal_acceleration, const float *goal_jerk,
+    const int32_t *start_idx, const int32_t *goal_idx, const float *traj_dt,
+    const uint8_t *use_implicit_goal_state, const float *fixed_transform,
+    const float *robot_spheres, const int8_t *joint_map_type, const int16_t *joint_map,
+    const int16_t *link_map, const int16_t *link_sphere_map, const int16_t *link_chain_data,
+    const int16_t *link_chain_offsets, const float *joint_offset_map, const float *sphere_padding,
+    const float *self_collision_weight, const int16_t *pair_locations,
+    const curobo_hip_scene *scene, const float *scene_collision_weight,
+    const float *activation_distance, const float *speed_dt, const int32_t *env_query_idx,
+    int num_envs, int use_multi_env, int batch_size, int padded_horizon, int dof, int n_knots,
+    int bspline_degree, int num_links, int num_spheres, int num_collision_pairs,
+    int link_chain_len, int sweep_steps, int enable_speed_metric, int32_t *dispatch_ws,
+    int dispatch_phase, const uint32_t *self_lane_lists, int self_lane_len, const curobo_hip_trajopt_terms *terms,
+    const float *memo_x, const float *memo_cost, const float *memo_grad, int memo_stride, int memo_slot,
+    curobo_hip_stream_t stream);
+
 /* 1 if the torque-limit terms fit (they borrow LDS regions that are dead when the inverse dynamics runs) */
 int curobo_hip_rollout_trajopt_fused_torque_fits(
     int padded_horizon, int dof, int num_links, int num_spheres, int num_collision_pairs,
