@@ -261,6 +261,55 @@ __device__ __forceinline__ void mesh_speed_metric(f3 center, f3 pp, f3 np, float
   }
 }
 
+// ---- what every kernel of the launch does with a sphere index, stated once.
+// Batch row, horizon index and environment of sphere `sidx`, and which neighbours exist: they feed the sweep and the speed metric.
+// (IDX: long in the one-kernel form, 32 bits where the queue holds the index in 32 bits.)
+template <int SWEEP, class IDX>
+__device__ __forceinline__ MeshSphere mesh_sphere_at(const MeshCollArgs &a, IDX sidx) {
+  const IDX hs = (IDX)(a.horizon * a.nspheres);
+  const int b = (int)(sidx / hs);
+  const int h = (int)((sidx - (IDX)b * hs) / (IDX)a.nspheres);
+  const bool need_nb = SWEEP > 0 || a.enable_speed_metric != 0;
+  MeshSphere p;
+  p.env = a.use_multi_env ? a.env_query_idx[b] : 0;
+  p.nb_prev = need_nb && h > 0;
+  p.nb_next = need_nb && h < a.horizon - 1;
+  return p;
+}
+// ... and the sphere itself with its neighbours, from memory
+template <int SWEEP, class IDX>
+__device__ __forceinline__ MeshSphere load_mesh_sphere(const MeshCollArgs &a, IDX sidx, float eta) {
+  MeshSphere p = mesh_sphere_at<SWEEP>(a, sidx);
+  const float4 *sph = reinterpret_cast<const float4 *>(a.spheres);
+  const float4 s = sph[sidx];
+  const float4 ps = p.nb_prev ? sph[sidx - a.nspheres] : s, ns = p.nb_next ? sph[sidx + a.nspheres] : s;
+  mesh_sphere_geometry<SWEEP>(p, s, ps, ns, eta);
+  return p;
+}
+
+// The sphere's result.  The speed metric is linear in (cost, gradient): scaling this kind's share on its own and adding it to
+// what the scene launch wrote (accumulate) gives the same sums as the reference's one scaling pass over all kinds
+// (wp_autograd.py:213-231) -- except for its `cost > 0` guard, which the sum passes whenever a share does.
+__device__ __forceinline__ void mesh_write_result(const MeshCollArgs &a, const MeshSphere &p, long sidx, float dsum, f3 gsum) {
+  if (a.enable_speed_metric && p.nb_prev && p.nb_next && dsum > 0.0f) mesh_speed_metric(p.center, p.pp, p.np, a.speed_dt[0], dsum, gsum);
+  float4 *grad = reinterpret_cast<float4 *>(a.gradient);
+  if (a.accumulate) {
+    if (dsum > 0.0f) {
+      a.distance[sidx] += dsum;
+      const float4 g0 = grad[sidx];
+      grad[sidx] = make_float4(g0.x + gsum.x, g0.y + gsum.y, g0.z + gsum.z, g0.w);
+    }
+    return;
+  }
+  a.distance[sidx] = dsum;
+  grad[sidx] = make_float4(gsum.x, gsum.y, gsum.z, 0.0f);
+}
+
+// entry q of a queue filled from both ends: the first n_front entries from its head, the others from q_last backwards
+__device__ __forceinline__ uint2 mesh_queue_entry(const uint2 *queue, uint32_t q, uint32_t n_front, uint32_t q_last) {
+  return queue[q < n_front ? q : q_last - (q - n_front)];
+}
+
 // The mesh share of the scene cost, packed like scene_collision_packed_kernel: every lane first runs the cheap part for
 // ITS sphere -- transform into each mesh's frame + the result-preserving bounding-box reject -- , the workgroup compacts
 // the surviving (sphere, mesh slot) items into an LDS queue (sphere-major, slot ascending) and evaluates the queue
@@ -276,42 +325,27 @@ __global__ void __launch_bounds__(256) sphere_mesh_collision_kernel(const MeshCo
   const long sidx0 = (long)blockIdx.x * NT;
   const int tid = threadIdx.x, lane64 = tid & 63, wave = tid >> 6;
   const long sidx = sidx0 + tid;
-  const int hs = a.horizon * a.nspheres;
   // LDS: sphere stash [3][256] float4 | results [256] float4 | prefix [256 + 8] int | queue [256 * nslots] u16
   float4 *stash = reinterpret_cast<float4 *>(smem);
   float4 *res = stash + 3 * NT;
   int *prefix = reinterpret_cast<int *>(res + NT);
   uint16_t *queue = reinterpret_cast<uint16_t *>(prefix + NT + 8);
   const bool in = sidx < total;
-  const int b = in ? (int)(sidx / hs) : 0;
-  const int h = in ? (int)((sidx - (long)b * hs) / a.nspheres) : 0;
-  const int env = (in && a.use_multi_env) ? a.env_query_idx[b] : 0;
-  const float4 *sph = reinterpret_cast<const float4 *>(a.spheres);
-  const bool need_nb = SWEEP > 0 || a.enable_speed_metric != 0;  // neighbours feed the sweep and the speed metric
-  const bool nb_prev = in && need_nb && h > 0, nb_next = in && need_nb && h < a.horizon - 1;
-  float4 s = make_float4(0.f, 0.f, 0.f, -1.f), ps, ns;
-  if (in) s = sph[sidx];
-  ps = ns = s;
-  if (nb_prev) ps = sph[sidx - a.nspheres];
-  if (nb_next) ns = sph[sidx + a.nspheres];
-  stash[tid] = s; stash[NT + tid] = ps; stash[2 * NT + tid] = ns;
   const float w = a.weight[0], eta = a.eta[0];
   const curobo_hip_mesh_set &ms = a.set;
+  MeshSphere p{};
+  p.radius = -1.0f;
+  if (in) p = load_mesh_sphere<SWEEP>(a, sidx, eta);
+  stash[tid] = make_float4(p.center.x, p.center.y, p.center.z, p.radius);
+  stash[NT + tid] = make_float4(p.pp.x, p.pp.y, p.pp.z, 0.f);
+  stash[2 * NT + tid] = make_float4(p.np.x, p.np.y, p.np.z, 0.f);
   // ---- phase 1: which slots survive the bounding-box reject for my sphere
   uint32_t live = 0u;
-  if (in && s.w >= 0.0f) {
-    const f3 center = make_f3(s.x, s.y, s.z);
-    const float r_adj = s.w + eta;
-    float half_w_prev = 0.0f, half_w_next = 0.0f;
-    if (SWEEP > 0) {
-      if (nb_prev) { const f3 dd = make_f3(ps.x, ps.y, ps.z) - center; half_w_prev = 0.5f * sqrtf(dot(dd, dd)); }
-      if (nb_next) { const f3 dd = make_f3(ns.x, ns.y, ns.z) - center; half_w_next = 0.5f * sqrtf(dot(dd, dd)); }
-    }
-    const float reach = SWEEP > 0 ? fmaxf(half_w_prev, half_w_next) * 1.0001f + 2e-6f : 2e-6f;
+  if (in && p.radius >= 0.0f) {
     for (int k = 0; k < a.nslots; k++) {
-      const MeshSlot slot = load_mesh_slot(ms, env, a.slot0 + k);
+      const MeshSlot slot = load_mesh_slot(ms, p.env, a.slot0 + k);
       if (!slot.enabled) continue;
-      if (!mesh_early_reject(slot, mesh_to_local(slot, center), r_adj, reach)) live |= 1u << k;
+      if (!mesh_early_reject(slot, mesh_to_local(slot, p.center), p.r_adj, p.reach)) live |= 1u << k;
     }
   }
   // ---- exclusive prefix of the item counts over the workgroup
@@ -348,25 +382,14 @@ __global__ void __launch_bounds__(256) sphere_mesh_collision_kernel(const MeshCo
       CUROBO_MESH_COUNT(6, 1);
       const unsigned e = queue[q];
       const int owner = (int)(e & 255u), k = (int)(e >> 8);
-      const long osidx = sidx0 + owner;
-      const int ob = (int)(osidx / hs);
-      const int oh = (int)((osidx - (long)ob * hs) / a.nspheres);
-      const int oenv = a.use_multi_env ? a.env_query_idx[ob] : 0;
-      const float4 cs = stash[owner], cp = stash[NT + owner], cn = stash[2 * NT + owner];
-      const MeshSlot slot = load_mesh_slot(ms, oenv, a.slot0 + k);
-      const f3 center = make_f3(cs.x, cs.y, cs.z), pp = make_f3(cp.x, cp.y, cp.z), np = make_f3(cn.x, cn.y, cn.z);
-      const bool hp = SWEEP > 0 && oh > 0, hn = SWEEP > 0 && oh < a.horizon - 1;
-      const float r_adj = cs.w + eta;
-      float half_w_prev = 0.0f, half_w_next = 0.0f;
-      if (SWEEP > 0) {
-        if (hp) { const f3 dd = pp - center; half_w_prev = 0.5f * sqrtf(dot(dd, dd)); }
-        if (hn) { const f3 dd = np - center; half_w_next = 0.5f * sqrtf(dot(dd, dd)); }
-      }
-      const float reach = SWEEP > 0 ? fmaxf(half_w_prev, half_w_next) * 1.0001f + 2e-6f : 2e-6f;
+      MeshSphere o = mesh_sphere_at<SWEEP>(a, sidx0 + owner);
+      mesh_sphere_geometry<SWEEP>(o, stash[owner], stash[NT + owner], stash[2 * NT + owner], eta);
+      const MeshSlot slot = load_mesh_slot(ms, o.env, a.slot0 + k);
       float cost_sum = 0.0f;
       f3 grad_local = make_f3(0.f, 0.f, 0.f);
-      mesh_contribution<SWEEP>(slot, ms.gradient_mode, mesh_to_local(slot, center), hp, hn, pp, np, r_adj, eta, half_w_prev,
-                               half_w_next, reach, cost_sum, grad_local);
+      mesh_contribution_q<SWEEP>(slot, ms.gradient_mode, o, eta, cost_sum, grad_local, [&](f3 qp, float q_radius, float max_distance, bool may_in, f3 &g) {
+        return mesh_sdf_within(slot.m, qp, q_radius, max_distance, may_in, g);
+      });
       if (cost_sum > 0.0f) {
         const f3 gw = mesh_to_world_vector(slot, grad_local);
         r4 = make_float4(w * gw.x, w * gw.y, w * gw.z, w * cost_sum);
@@ -380,23 +403,7 @@ __global__ void __launch_bounds__(256) sphere_mesh_collision_kernel(const MeshCo
       if (v.w > 0.0f) { dsum += v.w; gsum = gsum + make_f3(v.x, v.y, v.z); }
     }
   }
-  if (!in) return;
-  // the speed metric is linear in (cost, gradient): scaling this kind's share on its own and adding it to what the scene
-  // launch wrote (accumulate) gives the same sums as the reference's one scaling pass over all kinds (wp_autograd.py:
-  // 213-231) -- except for its `cost > 0` guard, which the sum passes whenever a share does
-  if (a.enable_speed_metric && nb_prev && nb_next && dsum > 0.0f)
-    mesh_speed_metric(make_f3(s.x, s.y, s.z), make_f3(ps.x, ps.y, ps.z), make_f3(ns.x, ns.y, ns.z), a.speed_dt[0], dsum, gsum);
-  float4 *grad = reinterpret_cast<float4 *>(a.gradient);
-  if (a.accumulate) {
-    if (dsum > 0.0f) {
-      a.distance[sidx] += dsum;
-      const float4 g0 = grad[sidx];
-      grad[sidx] = make_float4(g0.x + gsum.x, g0.y + gsum.y, g0.z + gsum.z, g0.w);
-    }
-    return;
-  }
-  a.distance[sidx] = dsum;
-  grad[sidx] = make_float4(gsum.x, gsum.y, gsum.z, 0.0f);
+  if (in) mesh_write_result(a, p, sidx, dsum, gsum);
 }
 
 // The same launch split in two (curobo_hip_sphere_mesh_collision_ws): spheres that survive the bounding-box reject for ANY
@@ -482,7 +489,7 @@ __global__ void __launch_bounds__(256) sphere_mesh_select_kernel(const MeshQueue
       const f3 center = make_f3(s[c].x, s[c].y, s[c].z);
       const f3 dp = make_f3(ps.x, ps.y, ps.z) - center, dn = make_f3(ns.x, ns.y, ns.z) - center;
       // (a missing neighbour stands in as the sphere itself: half step 0, as the walk kernel has it)
-      reach[c] = fmaxf(0.5f * sqrtf(dot(dp, dp)), 0.5f * sqrtf(dot(dn, dn))) * 1.0001f + 2e-6f;
+      reach[c] = mesh_reach<SWEEP>(0.5f * sqrtf(dot(dp, dp)), 0.5f * sqrtf(dot(dn, dn)));
     }
   }
   if (staged) __syncthreads();
@@ -504,11 +511,8 @@ __global__ void __launch_bounds__(256) sphere_mesh_select_kernel(const MeshQueue
           const float *rec = recs + k * 16;
           if (rec[13] == 0.0f) continue;
           const f3 lc = quat_rot(rec[3], rec[4], rec[5], rec[6], center) + make_f3(rec[0], rec[1], rec[2]);  // (mesh_to_local)
-          // (mesh_early_reject on the staged root box)
-          const float ex = fmaxf(fmaxf(rec[7] - lc.x, lc.x - rec[10]), 0.0f), ey = fmaxf(fmaxf(rec[8] - lc.y, lc.y - rec[11]), 0.0f),
-                      ez = fmaxf(fmaxf(rec[9] - lc.z, lc.z - rec[12]), 0.0f);
           int list_len;
-          if (!(ex * ex + ey * ey + ez * ez > thr * thr * 1.00001f) &&
+          if (!mesh_box_reject(make_f3(rec[7], rec[8], rec[9]), make_f3(rec[10], rec[11], rec[12]), lc, thr) &&  // (the staged root box)
               !mesh_cell_clear(s_grid[(a.use_multi_env ? (bb[c] - first_b) * a.nslots : 0) + k], lc, thr, list_len)) {
             live[c] |= 1u << k;
             // the long chains of the launch: with cell lists the spheres whose centre's cell has a long list (inside a block every
@@ -578,7 +582,7 @@ __global__ void __launch_bounds__(256) sphere_mesh_select_kernel(const MeshQueue
 }
 
 // ---- the walk kernel: EIGHT LANES per live sphere (queue entry).  All eight run the sphere's scalar program (its slots in
-// ascending order, every sample of a slot through the one query site of mesh_contribution) on the same values; only the
+// ascending order, every sample of a slot by the one chain of mesh_device.hpp::MeshSweep) on the same values; only the
 // tree walks split the work (mesh_device.hpp::mesh_contribution_group: three tree levels per step, one descendant box or
 // one leaf triangle per lane, sibling keys kept in LDS).  Measured on the bench's mesh world (tools/r04/mesh_stats.py: 1024 x 33 points x 65
 // spheres, the C2 world's 4 cuboids as meshes of 3072 triangles each, sweep 3), launch = select + walk:
@@ -619,7 +623,9 @@ __global__ void __launch_bounds__(256) sphere_mesh_select_kernel(const MeshQueue
 #define MESH_WALK_MAX_BLOCKS (1 << 20)
 #endif
 #ifndef MESH_WALK_ATTR
-#define MESH_WALK_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))  // 128 registers: four wavefronts a SIMD, nothing spilled
+// 128 registers: four wavefronts a SIMD.  What the compiler reports at that cap, sweep 3 / 0 (docs/NOTEBOOK.md has every kernel's
+// row): 27 / 0 registers spilled, 60 / 0 bytes of scratch a lane (28 / 0 and 64 / 0 before the sweep chain was stated once)
+#define MESH_WALK_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
 #endif
 template <int SWEEP>
 __global__ void __launch_bounds__(MESH_WALK_THREADS) MESH_WALK_ATTR sphere_mesh_walk_kernel(const MeshQueueArgs qa) {
@@ -628,8 +634,6 @@ __global__ void __launch_bounds__(MESH_WALK_THREADS) MESH_WALK_ATTR sphere_mesh_
   const uint32_t n_front = qa.from_queue2 ? qa.counter[1] : qa.counter[0], n = qa.from_queue2 ? n_front : n_front + qa.counter[2];
   const uint2 *queue = qa.from_queue2 ? qa.queue2 : qa.queue;
   const uint32_t q_last = (uint32_t)((long)a.batch * a.horizon * a.nspheres - 1);
-  const int hs = a.horizon * a.nspheres;
-  const float4 *sph = reinterpret_cast<const float4 *>(a.spheres);
   const float w = a.weight[0], eta = a.eta[0];
   // lane 0 of a group writes
   constexpr unsigned G = MESH_WALK_GROUP, PER_WG = MESH_WALK_THREADS / G;
@@ -638,26 +642,9 @@ __global__ void __launch_bounds__(MESH_WALK_THREADS) MESH_WALK_ATTR sphere_mesh_
     const uint32_t q = q0 + threadIdx.x / G;
     // (a group beyond the end of the queue repeats the last entry so that ballots and shuffles stay whole; it writes nothing)
     const bool live_group = q < n;
-    const uint32_t qq = live_group ? q : n - 1;
-    const uint2 e = queue[qq < n_front ? qq : q_last - (qq - n_front)];
+    const uint2 e = mesh_queue_entry(queue, live_group ? q : n - 1, n_front, q_last);
     if (live_group && (threadIdx.x & (G - 1u)) == 0) CUROBO_MESH_COUNT(6, 1);
-    const long sidx = (long)e.x;
-    const int b = (int)(e.x / (uint32_t)hs);  // (32-bit: the queued form holds sphere indices in 32 bits)
-    const int h = (int)((e.x - (uint32_t)b * (uint32_t)hs) / (uint32_t)a.nspheres);
-    const int env = a.use_multi_env ? a.env_query_idx[b] : 0;
-    const bool need_nb = SWEEP > 0 || a.enable_speed_metric != 0;
-    const bool nb_prev = need_nb && h > 0, nb_next = need_nb && h < a.horizon - 1;
-    const float4 s = sph[sidx];
-    const float4 ps = nb_prev ? sph[sidx - a.nspheres] : s, ns = nb_next ? sph[sidx + a.nspheres] : s;
-    const f3 center = make_f3(s.x, s.y, s.z), pp = make_f3(ps.x, ps.y, ps.z), np = make_f3(ns.x, ns.y, ns.z);
-    const bool hp = SWEEP > 0 && nb_prev, hn = SWEEP > 0 && nb_next;
-    const float r_adj = s.w + eta;
-    float half_w_prev = 0.0f, half_w_next = 0.0f;
-    if (SWEEP > 0) {
-      if (hp) { const f3 dd = pp - center; half_w_prev = 0.5f * sqrtf(dot(dd, dd)); }
-      if (hn) { const f3 dd = np - center; half_w_next = 0.5f * sqrtf(dot(dd, dd)); }
-    }
-    const float reach = SWEEP > 0 ? fmaxf(half_w_prev, half_w_next) * 1.0001f + 2e-6f : 2e-6f;
+    const MeshSphere p = load_mesh_sphere<SWEEP>(a, e.x, eta);  // (32-bit: the queued form holds sphere indices in 32 bits)
     float dsum = 0.0f;
     f3 gsum = make_f3(0.f, 0.f, 0.f);
     uint32_t m = e.y;
@@ -665,31 +652,18 @@ __global__ void __launch_bounds__(MESH_WALK_THREADS) MESH_WALK_ATTR sphere_mesh_
     while (m) {
       const int k = __ffs((int)m) - 1;
       m &= m - 1;
-      const MeshSlot slot = load_mesh_slot(a.set, env, a.slot0 + k);
+      const MeshSlot slot = load_mesh_slot(a.set, p.env, a.slot0 + k);
       float cost_sum = 0.0f;
       f3 grad_local = make_f3(0.f, 0.f, 0.f);
       if ((threadIdx.x & (G - 1u)) == 0) CUROBO_MESH_COUNT(7, 1);
-      mesh_contribution_group<SWEEP, (int)G>(slot, a.set.gradient_mode, mesh_to_local(slot, center), hp, hn, pp, np, r_adj, eta, half_w_prev,
-                                     half_w_next, reach, cost_sum, grad_local, group_keys + threadIdx.x, MESH_WALK_THREADS, q);
+      mesh_contribution_group<SWEEP, (int)G>(slot, a.set.gradient_mode, p, eta, cost_sum, grad_local, group_keys + threadIdx.x, MESH_WALK_THREADS, q);
       if (cost_sum > 0.0f) {
         const f3 gw = mesh_to_world_vector(slot, grad_local);
         dsum += w * cost_sum;
         gsum = gsum + w * gw;
       }
     }
-    if (a.enable_speed_metric && nb_prev && nb_next && dsum > 0.0f) mesh_speed_metric(center, pp, np, a.speed_dt[0], dsum, gsum);
-    if (!live_group || (threadIdx.x & (G - 1u)) != 0) continue;
-    float4 *grad = reinterpret_cast<float4 *>(a.gradient);
-    if (a.accumulate) {
-      if (dsum > 0.0f) {
-        a.distance[sidx] += dsum;
-        const float4 g0 = grad[sidx];
-        grad[sidx] = make_float4(g0.x + gsum.x, g0.y + gsum.y, g0.z + gsum.z, g0.w);
-      }
-    } else {
-      a.distance[sidx] = dsum;
-      grad[sidx] = make_float4(gsum.x, gsum.y, gsum.z, 0.0f);
-    }
+    if (live_group && (threadIdx.x & (G - 1u)) == 0) mesh_write_result(a, p, (long)e.x, dsum, gsum);
   }
 }
 
@@ -710,18 +684,18 @@ __global__ void __launch_bounds__(MESH_WALK_THREADS) MESH_WALK_ATTR sphere_mesh_
 #define MESH_CELLS_HEAVY_UNROLL 2
 #endif
 #ifndef MESH_CELLS_ATTR
-#define MESH_CELLS_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))  // 128 registers (142 unconstrained: three wavefronts a SIMD): 179 -> 156 us
+// 128 registers (142 unconstrained: three wavefronts a SIMD): 179 -> 156 us.  Reported at that cap, sweep 3 / 0: 12 / 0 registers
+// spilled, 52 / 0 bytes of scratch a lane (13 / 0 and 56 / 0 before the sweep chain was stated once)
+#define MESH_CELLS_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
 #endif
 // PART 0: the whole queue; 1: the entries queued from its head (centre inside a live mesh's bounding box: the long lists of
-// cells inside a surface); 2: the entries queued from its tail.
+// cells inside a surface); 2: the entries queued from its tail.  (1 and 2 are instantiated only with MESH_CELLS_HEAVY_GROUP > 0.)
 template <int SWEEP, int GROUP, int UNROLL, int PART>
 __global__ void __launch_bounds__(256) MESH_CELLS_ATTR sphere_mesh_cells_kernel(const MeshQueueArgs qa) {
   const MeshCollArgs &a = qa.c;
   const uint32_t n_front = qa.counter[0], n_all = n_front + qa.counter[2];
   const uint32_t q_begin = PART == 2 ? n_front : 0u, n = PART == 1 ? n_front : n_all;
   const uint32_t q_last = (uint32_t)((long)a.batch * a.horizon * a.nspheres - 1);
-  const int hs = a.horizon * a.nspheres;
-  const float4 *sph = reinterpret_cast<const float4 *>(a.spheres);
   const float w = a.weight[0], eta = a.eta[0];
   constexpr unsigned G = GROUP, PER_WG = 256 / G;
   __shared__ float s_state[PER_WG][MESH_ST_WORDS];  // the groups' LDS records (mesh_device.hpp MESH_ST_*)
@@ -729,28 +703,15 @@ __global__ void __launch_bounds__(256) MESH_CELLS_ATTR sphere_mesh_cells_kernel(
   for (uint32_t q0 = q_begin + blockIdx.x * PER_WG; q0 < n; q0 += gridDim.x * PER_WG) {
     const uint32_t q = q0 + threadIdx.x / G;
     const bool live_group = q < n;
-    const uint32_t qq = live_group ? q : n - 1;
-    const uint2 e = qa.queue[qq < n_front ? qq : q_last - (qq - n_front)];
-    const long sidx = (long)e.x;
-    const int b = (int)(e.x / (uint32_t)hs);
-    const int h = (int)((e.x - (uint32_t)b * (uint32_t)hs) / (uint32_t)a.nspheres);
-    const int env = a.use_multi_env ? a.env_query_idx[b] : 0;
-    const bool need_nb = SWEEP > 0 || a.enable_speed_metric != 0;
-    const bool nb_prev = need_nb && h > 0, nb_next = need_nb && h < a.horizon - 1;
+    const uint2 e = mesh_queue_entry(qa.queue, live_group ? q : n - 1, n_front, q_last);
+    bool nb_prev, nb_next;
+    int env;
     float r_adj, reach;
-    {
-      const float4 s = sph[sidx];
-      const float4 ps = nb_prev ? sph[sidx - a.nspheres] : s, ns = nb_next ? sph[sidx + a.nspheres] : s;
-      const f3 center = make_f3(s.x, s.y, s.z), pp = make_f3(ps.x, ps.y, ps.z), np = make_f3(ns.x, ns.y, ns.z);
-      r_adj = s.w + eta;
-      float half_w_prev = 0.0f, half_w_next = 0.0f;
-      if (SWEEP > 0) {
-        if (nb_prev) { const f3 dd = pp - center; half_w_prev = 0.5f * sqrtf(dot(dd, dd)); }
-        if (nb_next) { const f3 dd = np - center; half_w_next = 0.5f * sqrtf(dot(dd, dd)); }
-      }
-      reach = SWEEP > 0 ? fmaxf(half_w_prev, half_w_next) * 1.0001f + 2e-6f : 2e-6f;
-      st_store3(st, MESH_ST_CENTER, center); st_store3(st, MESH_ST_PREV, pp); st_store3(st, MESH_ST_NEXT, np);
-      st[MESH_ST_HALF_PREV] = half_w_prev; st[MESH_ST_HALF_NEXT] = half_w_next;
+    {  // (the sphere lives in the group's LDS record from here on)
+      const MeshSphere p = load_mesh_sphere<SWEEP>(a, e.x, eta);
+      nb_prev = p.nb_prev; nb_next = p.nb_next; env = p.env; r_adj = p.r_adj; reach = p.reach;
+      st_store3(st, MESH_ST_CENTER, p.center); st_store3(st, MESH_ST_PREV, p.pp); st_store3(st, MESH_ST_NEXT, p.np);
+      st[MESH_ST_HALF_PREV] = p.half_w_prev; st[MESH_ST_HALF_NEXT] = p.half_w_next;
       st[MESH_ST_DSUM] = 0.0f; st_store3(st, MESH_ST_GSUM, make_f3(0.f, 0.f, 0.f));
     }
     const unsigned flags = (SWEEP > 0 && nb_prev ? 1u : 0u) | (SWEEP > 0 && nb_next ? 2u : 0u);
@@ -776,21 +737,10 @@ __global__ void __launch_bounds__(256) MESH_CELLS_ATTR sphere_mesh_cells_kernel(
       else qa.queue2[q_last - atomicAdd(qa.counter + 3, 1u)] = e;
       continue;
     }
-    float dsum = st[MESH_ST_DSUM];
-    f3 gsum = st_load3(st, MESH_ST_GSUM);
-    if (a.enable_speed_metric && nb_prev && nb_next && dsum > 0.0f)
-      mesh_speed_metric(st_load3(st, MESH_ST_CENTER), st_load3(st, MESH_ST_PREV), st_load3(st, MESH_ST_NEXT), a.speed_dt[0], dsum, gsum);
-    float4 *grad = reinterpret_cast<float4 *>(a.gradient);
-    if (a.accumulate) {
-      if (dsum > 0.0f) {
-        a.distance[sidx] += dsum;
-        const float4 g0 = grad[sidx];
-        grad[sidx] = make_float4(g0.x + gsum.x, g0.y + gsum.y, g0.z + gsum.z, g0.w);
-      }
-    } else {
-      a.distance[sidx] = dsum;
-      grad[sidx] = make_float4(gsum.x, gsum.y, gsum.z, 0.0f);
-    }
+    MeshSphere p;  // (what the result needs of the sphere, back from the record)
+    p.nb_prev = nb_prev; p.nb_next = nb_next;
+    p.center = st_load3(st, MESH_ST_CENTER); p.pp = st_load3(st, MESH_ST_PREV); p.np = st_load3(st, MESH_ST_NEXT);
+    mesh_write_result(a, p, (long)e.x, st[MESH_ST_DSUM], st_load3(st, MESH_ST_GSUM));
   }
 }
 
@@ -805,29 +755,11 @@ __global__ void __launch_bounds__(256) sphere_mesh_wide_kernel(const MeshQueueAr
   const MeshCollArgs &a = qa.c;
   const uint32_t n = qa.counter[3];
   const uint32_t q_last = (uint32_t)((long)a.batch * a.horizon * a.nspheres - 1);
-  const int hs = a.horizon * a.nspheres;
-  const float4 *sph = reinterpret_cast<const float4 *>(a.spheres);
   const float w = a.weight[0], eta = a.eta[0];
   __shared__ MeshWideLds lds;
   for (uint32_t q = blockIdx.x; q < n; q += gridDim.x) {
-    const uint2 e = qa.queue2[q_last - q];
-    const long sidx = (long)e.x;
-    const int b = (int)(e.x / (uint32_t)hs);
-    const int h = (int)((e.x - (uint32_t)b * (uint32_t)hs) / (uint32_t)a.nspheres);
-    const int env = a.use_multi_env ? a.env_query_idx[b] : 0;
-    const bool need_nb = SWEEP > 0 || a.enable_speed_metric != 0;
-    const bool nb_prev = need_nb && h > 0, nb_next = need_nb && h < a.horizon - 1;
-    const float4 s = sph[sidx];
-    const float4 ps = nb_prev ? sph[sidx - a.nspheres] : s, ns = nb_next ? sph[sidx + a.nspheres] : s;
-    const f3 center = make_f3(s.x, s.y, s.z), pp = make_f3(ps.x, ps.y, ps.z), np = make_f3(ns.x, ns.y, ns.z);
-    const bool hp = SWEEP > 0 && nb_prev, hn = SWEEP > 0 && nb_next;
-    const float r_adj = s.w + eta;
-    float half_w_prev = 0.0f, half_w_next = 0.0f;
-    if (SWEEP > 0) {
-      if (hp) { const f3 dd = pp - center; half_w_prev = 0.5f * sqrtf(dot(dd, dd)); }
-      if (hn) { const f3 dd = np - center; half_w_next = 0.5f * sqrtf(dot(dd, dd)); }
-    }
-    const float reach = SWEEP > 0 ? fmaxf(half_w_prev, half_w_next) * 1.0001f + 2e-6f : 2e-6f;
+    const uint2 e = mesh_queue_entry(qa.queue2, q, 0u, q_last);  // (all of them from the tail)
+    const MeshSphere p = load_mesh_sphere<SWEEP>(a, e.x, eta);
     float dsum = 0.0f;
     f3 gsum = make_f3(0.f, 0.f, 0.f);
     uint32_t m = e.y;
@@ -835,32 +767,19 @@ __global__ void __launch_bounds__(256) sphere_mesh_wide_kernel(const MeshQueueAr
     while (m) {
       const int k = __ffs((int)m) - 1;
       m &= m - 1;
-      const MeshSlot slot = load_mesh_slot(a.set, env, a.slot0 + k);
+      const MeshSlot slot = load_mesh_slot(a.set, p.env, a.slot0 + k);
       float cost_sum = 0.0f;
       f3 grad_local = make_f3(0.f, 0.f, 0.f);
-      mesh_contribution_q<SWEEP>(slot, a.set.gradient_mode, mesh_to_local(slot, center), hp, hn, pp, np, r_adj, eta, half_w_prev, half_w_next,
-                                 reach, cost_sum, grad_local, [&](f3 qp, float, float max_distance, bool, f3 &g) {
-                                   return mesh_block_sdf(slot.m, qp, max_distance, g, lds);
-                                 });
+      mesh_contribution_q<SWEEP>(slot, a.set.gradient_mode, p, eta, cost_sum, grad_local, [&](f3 qp, float, float max_distance, bool, f3 &g) {
+        return mesh_block_sdf(slot.m, qp, max_distance, g, lds);
+      });
       if (cost_sum > 0.0f) {
         const f3 gw = mesh_to_world_vector(slot, grad_local);
         dsum += w * cost_sum;
         gsum = gsum + w * gw;
       }
     }
-    if (a.enable_speed_metric && nb_prev && nb_next && dsum > 0.0f) mesh_speed_metric(center, pp, np, a.speed_dt[0], dsum, gsum);
-    if (threadIdx.x != 0) continue;
-    float4 *grad = reinterpret_cast<float4 *>(a.gradient);
-    if (a.accumulate) {
-      if (dsum > 0.0f) {
-        a.distance[sidx] += dsum;
-        const float4 g0 = grad[sidx];
-        grad[sidx] = make_float4(g0.x + gsum.x, g0.y + gsum.y, g0.z + gsum.z, g0.w);
-      }
-    } else {
-      a.distance[sidx] = dsum;
-      grad[sidx] = make_float4(gsum.x, gsum.y, gsum.z, 0.0f);
-    }
+    if (threadIdx.x == 0) mesh_write_result(a, p, (long)e.x, dsum, gsum);
   }
 }
 
@@ -991,6 +910,32 @@ CUROBO_EXPORT int curobo_hip_mesh_esdf_bake_bvh(uint16_t *out_esdf_fp16, const c
   return check_launch(what, (hipStream_t)stream);
 }
 
+// the queued cascade of one slot group: select, then the tree walk of the queue -- or, with cell lists, the cell-list kernel (every
+// sphere it can answer), a workgroup each for the spheres it sent to the tail of queue2, the tree walk of those at its head
+template <int SWEEP>
+static void launch_mesh_queued(MeshQueueArgs qa, long total, bool with_cells, hipStream_t st) {
+  const dim3 block(256);
+  hipLaunchKernelGGL(mesh_queue_reset_kernel, dim3(1), dim3(64), 0, st, qa.counter);
+  hipLaunchKernelGGL((sphere_mesh_select_kernel<SWEEP>), dim3((unsigned)ceil_div_l(total, 256 * MESH_SELECT_CHUNKS)), block, 0, st, qa);
+  // the walk's grid covers the chip once (1024 workgroups of four wavefronts); the queue is usually much shorter
+  const unsigned walk_blocks = (unsigned)std::min<long>(MESH_WALK_MAX_BLOCKS, ceil_div_l(total, MESH_WALK_THREADS / MESH_WALK_GROUP));
+  if (!with_cells) {
+    hipLaunchKernelGGL((sphere_mesh_walk_kernel<SWEEP>), dim3(walk_blocks), dim3(MESH_WALK_THREADS), 0, st, qa);
+    return;
+  }
+  const dim3 cells_grid((unsigned)std::min<long>(8192, ceil_div_l(total, 256 / MESH_CELLS_GROUP)));
+#if MESH_CELLS_HEAVY_GROUP > 0  // the head of the queue by a launch of its own
+  hipLaunchKernelGGL((sphere_mesh_cells_kernel<SWEEP, MESH_CELLS_HEAVY_GROUP, MESH_CELLS_HEAVY_UNROLL, 1>), cells_grid, block, 0, st, qa);
+  hipLaunchKernelGGL((sphere_mesh_cells_kernel<SWEEP, MESH_CELLS_GROUP, MESH_CELLS_UNROLL, 2>), cells_grid, block, 0, st, qa);
+#else
+  hipLaunchKernelGGL((sphere_mesh_cells_kernel<SWEEP, MESH_CELLS_GROUP, MESH_CELLS_UNROLL, 0>), cells_grid, block, 0, st, qa);
+#endif
+  qa.from_queue2 = 1;
+  const unsigned wide_blocks = (unsigned)std::min<long>(2048, total);  // (a workgroup per sphere sent there: usually none)
+  hipLaunchKernelGGL((sphere_mesh_wide_kernel<SWEEP>), dim3(wide_blocks), block, 0, st, qa);
+  hipLaunchKernelGGL((sphere_mesh_walk_kernel<SWEEP>), dim3(std::min(walk_blocks, 4096u)), dim3(MESH_WALK_THREADS), 0, st, qa);
+}
+
 static int sphere_mesh_collision_impl(
     const char *what, float *distance, float *gradient, const float *spheres, const curobo_hip_mesh_set *meshes, const float *weight,
     const float *activation_distance, const int32_t *env_query_idx, int batch_size, int horizon, int num_spheres, int use_multi_env,
@@ -1005,7 +950,7 @@ static int sphere_mesh_collision_impl(
   const long total = (long)batch_size * horizon * num_spheres;
   if (total == 0) return CUROBO_HIP_OK;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)ceil_div_l(total, 256)), block(256), select_grid((unsigned)ceil_div_l(total, 256 * MESH_SELECT_CHUNKS));
+  const dim3 grid((unsigned)ceil_div_l(total, 256)), block(256);
   if (meshes->max_n == 0) {  // no mesh slots: this kind's share is zero -- which an overwriting launch still has to write
     if (!accumulate) hipLaunchKernelGGL(mesh_zero_outputs_kernel, grid, block, 0, st, distance, reinterpret_cast<float4 *>(gradient), total);
     return check_launch(what, st);
@@ -1031,44 +976,8 @@ static int sphere_mesh_collision_impl(
       qa.c = a; qa.counter = reinterpret_cast<uint32_t *>(workspace);
       qa.queue = reinterpret_cast<uint2 *>(reinterpret_cast<char *>(workspace) + 16);
       qa.queue2 = qa.queue + total;
-      hipLaunchKernelGGL(mesh_queue_reset_kernel, dim3(1), dim3(64), 0, st, qa.counter);
-      // the walk's grid covers the chip once (1024 workgroups of four wavefronts); the queue is usually much shorter
-      const unsigned walk_blocks = (unsigned)std::min<long>(MESH_WALK_MAX_BLOCKS, ceil_div_l(total, MESH_WALK_THREADS / MESH_WALK_GROUP));
-      // with cell lists: select -> cell-list kernel (every sphere it can answer) -> tree walk of the few it could not
-      const unsigned cells_blocks = (unsigned)std::min<long>(8192, ceil_div_l(total, 256 / MESH_CELLS_GROUP));
-      const unsigned rest_blocks = std::min(walk_blocks, 4096u);
-      const unsigned wide_blocks = (unsigned)std::min<long>(2048, total);  // (a workgroup per sphere sent there: usually none)
-      if (sweep_steps > 0) {
-        hipLaunchKernelGGL((sphere_mesh_select_kernel<3>), select_grid, block, 0, st, qa);
-        if (with_cells) {
-          if (MESH_CELLS_HEAVY_GROUP > 0) {
-            hipLaunchKernelGGL((sphere_mesh_cells_kernel<3, MESH_CELLS_HEAVY_GROUP ? MESH_CELLS_HEAVY_GROUP : 8, MESH_CELLS_HEAVY_UNROLL, 1>), dim3(cells_blocks), block, 0, st, qa);
-            hipLaunchKernelGGL((sphere_mesh_cells_kernel<3, MESH_CELLS_GROUP, MESH_CELLS_UNROLL, 2>), dim3(cells_blocks), block, 0, st, qa);
-          } else {
-            hipLaunchKernelGGL((sphere_mesh_cells_kernel<3, MESH_CELLS_GROUP, MESH_CELLS_UNROLL, 0>), dim3(cells_blocks), block, 0, st, qa);
-          }
-          qa.from_queue2 = 1;
-          hipLaunchKernelGGL((sphere_mesh_wide_kernel<3>), dim3(wide_blocks), dim3(256), 0, st, qa);
-          hipLaunchKernelGGL((sphere_mesh_walk_kernel<3>), dim3(rest_blocks), dim3(MESH_WALK_THREADS), 0, st, qa);
-        } else {
-          hipLaunchKernelGGL((sphere_mesh_walk_kernel<3>), dim3(walk_blocks), dim3(MESH_WALK_THREADS), 0, st, qa);
-        }
-      } else {
-        hipLaunchKernelGGL((sphere_mesh_select_kernel<0>), select_grid, block, 0, st, qa);
-        if (with_cells) {
-          if (MESH_CELLS_HEAVY_GROUP > 0) {
-            hipLaunchKernelGGL((sphere_mesh_cells_kernel<0, MESH_CELLS_HEAVY_GROUP ? MESH_CELLS_HEAVY_GROUP : 8, MESH_CELLS_HEAVY_UNROLL, 1>), dim3(cells_blocks), block, 0, st, qa);
-            hipLaunchKernelGGL((sphere_mesh_cells_kernel<0, MESH_CELLS_GROUP, MESH_CELLS_UNROLL, 2>), dim3(cells_blocks), block, 0, st, qa);
-          } else {
-            hipLaunchKernelGGL((sphere_mesh_cells_kernel<0, MESH_CELLS_GROUP, MESH_CELLS_UNROLL, 0>), dim3(cells_blocks), block, 0, st, qa);
-          }
-          qa.from_queue2 = 1;
-          hipLaunchKernelGGL((sphere_mesh_wide_kernel<0>), dim3(wide_blocks), dim3(256), 0, st, qa);
-          hipLaunchKernelGGL((sphere_mesh_walk_kernel<0>), dim3(rest_blocks), dim3(MESH_WALK_THREADS), 0, st, qa);
-        } else {
-          hipLaunchKernelGGL((sphere_mesh_walk_kernel<0>), dim3(walk_blocks), dim3(MESH_WALK_THREADS), 0, st, qa);
-        }
-      }
+      if (sweep_steps > 0) launch_mesh_queued<3>(qa, total, with_cells, st);
+      else launch_mesh_queued<0>(qa, total, with_cells, st);
       continue;
     }
     const size_t lds = (size_t)(3 + 1) * 256 * 16 + (256 + 8) * 4 + (((size_t)256 * a.nslots * 2 + 15) & ~(size_t)15);

@@ -406,101 +406,165 @@ __device__ __forceinline__ MeshSlot load_mesh_slot(const curobo_hip_mesh_set &ms
 __device__ __forceinline__ f3 mesh_to_local(const MeshSlot &s, f3 v) { return quat_rot(s.qw, s.qx, s.qy, s.qz, v) + s.t; }
 
 // Early reject (result preserving): the surface lies inside the mesh's bounding box (root of the tree), so the signed
-// distance of a point outside the box is at least its distance to the box; when that exceeds r_adj + the half sweep
+// distance of a point outside the box is at least its distance to the box; when that exceeds thr = r_adj + the half sweep
 // length (+ rounding) neither the centre nor any sweep sample can penetrate.
-__device__ __forceinline__ bool mesh_early_reject(const MeshSlot &s, f3 lc, float r_adj, float reach) {
-  const float *rb = s.m.node_box + 8;
-  const float ex = fmaxf(fmaxf(rb[0] - lc.x, lc.x - rb[4]), 0.0f), ey = fmaxf(fmaxf(rb[1] - lc.y, lc.y - rb[5]), 0.0f),
-              ez = fmaxf(fmaxf(rb[2] - lc.z, lc.z - rb[6]), 0.0f);
-  const float thr = r_adj + reach;
+__device__ __forceinline__ bool mesh_box_reject(f3 lo, f3 hi, f3 lc, float thr) {
+  const float ex = fmaxf(fmaxf(lo.x - lc.x, lc.x - hi.x), 0.0f), ey = fmaxf(fmaxf(lo.y - lc.y, lc.y - hi.y), 0.0f),
+              ez = fmaxf(fmaxf(lo.z - lc.z, lc.z - hi.z), 0.0f);
   return ex * ex + ey * ey + ez * ez > thr * thr * 1.00001f;
 }
+__device__ __forceinline__ bool mesh_early_reject(const MeshSlot &s, f3 lc, float r_adj, float reach) {
+  const float *rb = s.m.node_box + 8;
+  return mesh_box_reject(make_f3(rb[0], rb[1], rb[2]), make_f3(rb[4], rb[5], rb[6]), lc, r_adj + reach);
+}
 
-// Cost and mesh-frame gradient of ONE sphere against ONE mesh that passed the early reject: the centre sample plus the
-// sweep towards the previous / next point (wp_sweep_collision_kernel.py:176-254; the mesh twin of
-// scene_device.hpp::obstacle_contribution).  lc = centre in the mesh frame, reach as for mesh_early_reject.
-// (QUERY: sdf = query(point, radius that matters, max_distance, may be inside, gradient&) -- mesh_sdf_within for a lane on its own,
-// mesh_block_sdf for a workgroup that answers one sphere's queries together)
-template <int SWEEP, class QUERY>
-__device__ __forceinline__ void mesh_contribution_q(const MeshSlot &s, int gradient_mode, f3 lc, bool has_prev, bool has_next, f3 prev_c,
-                                                    f3 next_c, float r_adj, float eta, float half_w_prev, float half_w_next,
-                                                    float reach, float &cost_sum, f3 &grad_local, QUERY query) {
-  // max_distance = max(half the bounding-box diagonal, the query distance) (data_mesh.py:660-668)
-  const float max_distance = fmaxf(s.max_half_diag, r_adj);
-  // how far the centre's distance matters: its cost below r_adj, the sweep culling below r_adj + the half segment
-  const float cull_slack = 2e-6f + 1e-6f * max_distance;
-  // The samples of an item -- the centre, then up to SWEEP - 1 per direction -- are queried by ONE loop (one inlined copy of
-  // the walk; in a wavefront the lanes' i-th queries run together).  dir = -1: the centre.
-  f3 g_c = make_f3(0.f, 0.f, 0.f), ln = lc, qp = lc;
-  float sdf_c = 0.0f, pen_c = 0.0f, c_c = 0.0f, gs_c = 0.0f, half_dist = 0.0f, inv_half = 0.0f, jump = 0.0f;
-  float q_radius = (r_adj + reach + cull_slack) * 1.0001f + 1e-6f;
+// One query sphere as every kernel of the mesh launch consumes it (filled by mesh_bvh.hip::load_mesh_sphere).
+struct MeshSphere {
+  int env;                // the environment of its trajectory
+  f3 center, pp, np;      // the sphere and its neighbours along the horizon (a missing neighbour stands in as the sphere itself)
+  float radius;           // negative: the sphere is switched off
+  bool nb_prev, nb_next;  // the neighbours exist (speed metric) ...
+  bool hp, hn;            // ... and the sweep walks towards them
+  float r_adj, half_w_prev, half_w_next, reach;
+};
+// how far a sweep sample can lie from the centre: half the longer step to a neighbour (+ rounding)
+template <int SWEEP>
+__device__ __forceinline__ float mesh_reach(float half_w_prev, float half_w_next) {
+  return SWEEP > 0 ? fmaxf(half_w_prev, half_w_next) * 1.0001f + 2e-6f : 2e-6f;
+}
+// the geometry of a sphere whose env / nb_prev / nb_next are set, from the sphere and its neighbours as loaded
+template <int SWEEP>
+__device__ __forceinline__ void mesh_sphere_geometry(MeshSphere &p, float4 s, float4 ps, float4 ns, float eta) {
+  p.center = make_f3(s.x, s.y, s.z); p.pp = make_f3(ps.x, ps.y, ps.z); p.np = make_f3(ns.x, ns.y, ns.z);
+  p.radius = s.w;
+  p.hp = SWEEP > 0 && p.nb_prev; p.hn = SWEEP > 0 && p.nb_next;
+  p.r_adj = s.w + eta;
+  p.half_w_prev = p.half_w_next = 0.0f;
+  if (SWEEP > 0) {
+    if (p.hp) { const f3 dd = p.pp - p.center; p.half_w_prev = 0.5f * sqrtf(dot(dd, dd)); }
+    if (p.hn) { const f3 dd = p.np - p.center; p.half_w_next = 0.5f * sqrtf(dot(dd, dd)); }
+  }
+  p.reach = mesh_reach<SWEEP>(p.half_w_prev, p.half_w_next);
+}
+
+// ---- The sample chain of ONE sphere against ONE mesh that passed the early reject: the centre sample, then up to SWEEP - 1
+// samples towards the previous / next point (wp_sweep_collision_kernel.py:176-254; the mesh twin of
+// scene_device.hpp::obstacle_contribution), stated once for every kernel of the launch.  A caller answers the current query
+// (qp, q_radius, q_may_in) its own way, hands the answer to settle() and asks next() for the following sample.  STORE says where
+// the values live that the callers keep differently -- the item's sums, the centre sample's terms, the neighbours, the half steps,
+// which neighbours exist: MeshSweepRegs (registers, over a MeshSlot) or MeshSweepLds (the group's LDS record, further down).
+// Every lane that runs a chain together with others (the groups' lanes, the workgroup of sphere_mesh_wide_kernel) holds the same
+// values, so the chain's branches are uniform over them.
+template <int SWEEP, class STORE>
+struct MeshSweep {
+  STORE st;
+  int gradient_mode;
+  float r_adj, eta, max_distance;
+  f3 lc, ln, qp;  // centre and the direction's neighbour in the mesh frame; the current query
+  float half_dist = 0.0f, jump = 0.0f, q_radius;
   bool q_may_in = true;
-  int dir = -1, k = 0;
-#pragma unroll 1
-  for (;;) {
-    f3 g;
-    const float sdf = query(qp, q_radius, max_distance, q_may_in, g);
+  int dir = -1, k = 0;  // dir = -1: the centre
+
+  __device__ __forceinline__ MeshSweep(STORE store, int gradient_mode_, f3 lc_, float r_adj_, float eta_, float max_half_diag, float reach)
+      : st(store), gradient_mode(gradient_mode_), r_adj(r_adj_), eta(eta_), lc(lc_), ln(lc_), qp(lc_) {
+    max_distance = fmaxf(max_half_diag, r_adj);  // max(half the bounding-box diagonal, the query distance) (data_mesh.py:660-668)
+    // how far the centre's distance matters: its cost below r_adj, the sweep culling below r_adj + the half segment
+    q_radius = (r_adj + reach + cull_slack()) * 1.0001f + 1e-6f;
+  }
+  __device__ __forceinline__ float cull_slack() const { return 2e-6f + 1e-6f * max_distance; }
+  // the step along the segment that a sample with penetration `pen` allows (wp_sweep_collision_kernel.py:204-212)
+  __device__ __forceinline__ void advance(float pen) {
+    if (pen > 0.0f) jump += pen;
+    else if (-pen >= 1000.0f) jump += r_adj;
+    else jump += fmaxf(-pen, r_adj);
+  }
+
+  // the answer to the current query: its terms, then the centre's record or the step along the segment
+  __device__ __forceinline__ void settle(float sdf, f3 g) {
     if (gradient_mode == 1 && sdf > 0.0f) g = -1.0f * g;
     const float pen = -sdf + r_adj;
     float c = 0.0f, gs = 0.0f;
     if (pen > 0.0f) {
       activation_m(pen, eta, c, gs);
-      cost_sum += c;
-      grad_local = grad_local + gs * g;
+      st.add(c, gs, g);
     }
-    if (dir < 0) { sdf_c = sdf; pen_c = pen; c_c = c; gs_c = gs; g_c = g; }
-    else {  // a sweep sample: the step along the segment (wp_sweep_collision_kernel.py:204-212)
-      if (pen > 0.0f) jump += pen;
-      else if (-pen >= 1000.0f) jump += r_adj;
-      else jump += fmaxf(-pen, r_adj);
-      k++;
-    }
-    if (SWEEP == 0) break;
-    // ---- the next sample to query, if any
+    if (dir < 0) st.keep_centre(sdf, pen, c, gs, g);
+    else { advance(pen); k++; }
+  }
+  // the next sample to query, if any
+  __device__ __forceinline__ bool next() {
+    if (SWEEP == 0) return false;
     bool have = false;
 #pragma unroll 1
     while (!have) {
       if (dir >= 0 && k < SWEEP && !(jump >= half_dist)) { have = true; break; }
       dir++;
       if (dir >= 2) break;
-      if (!(dir == 0 ? has_prev : has_next)) continue;
+      if (!st.has(dir)) continue;
       // sweep culling (result preserving, as for cuboids: scene_device.hpp): every sample lies within the half segment
       // length of the centre and the signed distance is 1-Lipschitz, so a centre that is clear by more than that cannot
       // have a penetrating sample.  (Closed meshes only: under the reference's ray rule an open mesh's sign changes across
-      // the shadow lines of its rim, far from any surface -- sign_rule 1 culls nothing by continuity.)  (A centre that found no surface within its search radius is clear by more than any
-      // half segment -- or beyond max_distance, where the samples find nothing either.)
-      if (s.m.sign_rule == 0 && -pen_c > (dir == 0 ? half_w_prev : half_w_next) * 1.0001f + cull_slack) continue;
-      ln = mesh_to_local(s, dir == 0 ? prev_c : next_c);
+      // the shadow lines of its rim, far from any surface -- sign_rule 1 culls nothing by continuity.)  (A centre that found
+      // no surface within its search radius is clear by more than any half segment -- or beyond max_distance, where the
+      // samples find nothing either.)
+      const float pen_c = st.pen_c();
+      if (st.lipschitz() && -pen_c > st.half_w(dir) * 1.0001f + cull_slack()) continue;
+      ln = st.neighbour(dir);
       const f3 dd = ln - lc;
       half_dist = sqrtf(dot(dd, dd)) * 0.5f;
-      inv_half = 1.0f / fmaxf(half_dist, 0.001f);
       jump = 0.0f;
       k = SWEEP;  // (no sample unless the direction is entered below)
       if (jump >= half_dist) continue;
       // k = 0 of the reference's loop samples t = 1, the centre itself: its terms are added again, not walked again
-      if (pen_c > 0.0f) { cost_sum += c_c; grad_local = grad_local + gs_c * g_c; jump += pen_c; }
-      else if (-pen_c >= 1000.0f) jump += r_adj;
-      else jump += fmaxf(-pen_c, r_adj);
+      if (pen_c > 0.0f) st.add_centre();
+      advance(pen_c);
       k = 1;
     }
-    if (!have) break;
-    const float tt = 1.0f - 0.5f * jump * inv_half;
+    if (!have) return false;
+    const float tt = 1.0f - 0.5f * jump * (1.0f / fmaxf(half_dist, 0.001f));
     qp = tt * lc + (1.0f - tt) * ln;
     // the sample's distance matters below r_adj (cost) and below r_adj + the rest of the half segment (next step);
     // it lies within half_dist of the centre, so it can only be deep inside when the centre is inside
     q_radius = (r_adj + (half_dist - jump)) * 1.0001f + 1e-6f;
-    q_may_in = s.m.sign_rule != 0 || sdf_c < half_dist;
+    q_may_in = !st.lipschitz() || st.sdf_c() < half_dist;
+    return true;
   }
-}
+};
 
-template <int SWEEP>
-__device__ __forceinline__ void mesh_contribution(const MeshSlot &s, int gradient_mode, f3 lc, bool has_prev, bool has_next, f3 prev_c,
-                                                  f3 next_c, float r_adj, float eta, float half_w_prev, float half_w_next,
-                                                  float reach, float &cost_sum, f3 &grad_local) {
-  mesh_contribution_q<SWEEP>(s, gradient_mode, lc, has_prev, has_next, prev_c, next_c, r_adj, eta, half_w_prev, half_w_next, reach, cost_sum,
-                             grad_local, [&](f3 qp, float q_radius, float max_distance, bool may_in, f3 &g) {
-                               return mesh_sdf_within(s.m, qp, q_radius, max_distance, may_in, g);
-                             });
+// the chain's values in registers: the slot and the sphere as loaded, the item's sums by reference
+struct MeshSweepRegs {
+  const MeshSlot &s;
+  const MeshSphere &p;
+  float &cost_sum;
+  f3 &grad_local;
+  float sdf_c_ = 0.0f, pen_c_ = 0.0f, c_c = 0.0f, gs_c = 0.0f;
+  f3 g_c = {0.f, 0.f, 0.f};
+  __device__ __forceinline__ bool lipschitz() const { return s.m.sign_rule == 0; }
+  __device__ __forceinline__ bool has(int dir) const { return dir == 0 ? p.hp : p.hn; }
+  __device__ __forceinline__ float half_w(int dir) const { return dir == 0 ? p.half_w_prev : p.half_w_next; }
+  __device__ __forceinline__ f3 neighbour(int dir) const { return mesh_to_local(s, dir == 0 ? p.pp : p.np); }
+  __device__ __forceinline__ void add(float c, float gs, f3 g) { cost_sum += c; grad_local = grad_local + gs * g; }
+  __device__ __forceinline__ void keep_centre(float sdf, float pen, float c, float gs, f3 g) { sdf_c_ = sdf; pen_c_ = pen; c_c = c; gs_c = gs; g_c = g; }
+  __device__ __forceinline__ void add_centre() { add(c_c, gs_c, g_c); }
+  __device__ __forceinline__ float pen_c() const { return pen_c_; }
+  __device__ __forceinline__ float sdf_c() const { return sdf_c_; }
+};
+
+// Cost and mesh-frame gradient of one sphere against one mesh, every query of the chain through ONE call site (one inlined copy
+// of the walk; in a wavefront the lanes' i-th queries run together).
+// (QUERY: sdf = query(point, radius that matters, max_distance, may be inside, gradient&) -- mesh_sdf_within for a lane on its own,
+// mesh_block_sdf for a workgroup that answers one sphere's queries together)
+template <int SWEEP, class QUERY>
+__device__ __forceinline__ void mesh_contribution_q(const MeshSlot &s, int gradient_mode, const MeshSphere &p, float eta, float &cost_sum,
+                                                    f3 &grad_local, QUERY query) {
+  MeshSweep<SWEEP, MeshSweepRegs> sw(MeshSweepRegs{s, p, cost_sum, grad_local}, gradient_mode, mesh_to_local(s, p.center), p.r_adj, eta,
+                                     s.max_half_diag, p.reach);
+#pragma unroll 1
+  do {
+    f3 g;
+    const float sdf = query(sw.qp, sw.q_radius, sw.max_distance, sw.q_may_in, g);
+    sw.settle(sdf, g);
+  } while (sw.next());
 }
 
 // ---- the same contribution by a GROUP of G lanes (sphere_mesh_walk_kernel), every query of the item in ONE loop.
@@ -511,9 +575,8 @@ __device__ __forceinline__ void mesh_contribution(const MeshSlot &s, int gradien
 // Per pass every group makes one move (down into the nearest descendant / to the nearest sibling still owed / a leaf's
 // triangles) or one transition between queries.
 template <int SWEEP, int G>
-__device__ __forceinline__ void mesh_contribution_group(const MeshSlot &s, int gradient_mode, f3 lc, bool has_prev, bool has_next, f3 prev_c,
-                                                        f3 next_c, float r_adj, float eta, float half_w_prev, float half_w_next,
-                                                        float reach, float &cost_sum, f3 &grad_local, float *keys, int key_stride, unsigned stat_q = 0u) {
+__device__ __forceinline__ void mesh_contribution_group(const MeshSlot &s, int gradient_mode, const MeshSphere &p, float eta, float &cost_sum,
+                                                        f3 &grad_local, float *keys, int key_stride, unsigned stat_q = 0u) {
   constexpr int LV = G == 16 ? 4 : 3;  // tree levels per step
   constexpr unsigned GM = (1u << G) - 1u;
   constexpr float FAR = 3.0e38f;
@@ -522,19 +585,16 @@ __device__ __forceinline__ void mesh_contribution_group(const MeshSlot &s, int g
   const TriRec *tri = reinterpret_cast<const TriRec *>(m.tri);
   const int g = threadIdx.x & (G - 1), gbase = threadIdx.x & (64 - G);
   const int depth_leaves = 31 - __builtin_clz(m.n_leaves);
-  const float max_distance = fmaxf(s.max_half_diag, r_adj);      // (mesh_contribution)
-  const float cull_slack = 2e-6f + 1e-6f * max_distance;
-  // the item's sweep state (mesh_contribution)
-  f3 g_c = make_f3(0.f, 0.f, 0.f), ln = lc, qp = lc;
-  float sdf_c = 0.0f, pen_c = 0.0f, c_c = 0.0f, gs_c = 0.0f, half_dist = 0.0f, inv_half = 0.0f, jump = 0.0f;
-  float q_radius = (r_adj + reach + cull_slack) * 1.0001f + 1e-6f;
-  bool q_may_in = true;
-  int dir = -1, k = 0;
+  // the item's chain; what is this function's own is the walk that answers its queries, interleaved with it
+  MeshSweep<SWEEP, MeshSweepRegs> sw(MeshSweepRegs{s, p, cost_sum, grad_local}, gradient_mode, mesh_to_local(s, p.center), p.r_adj, eta,
+                                     s.max_half_diag, p.reach);
+  const f3 &qp = sw.qp;
+  const float max_distance = sw.max_distance;
   // the running query (mesh_sdf_within + the walk): every lane keeps the best of ITS triangles, only the
   // distance is shared while walking (it prunes); which lane holds the closest point is settled when the walk is over
-  bool full = !(q_radius < max_distance);
+  bool full = !(sw.q_radius < max_distance);
   float best_d2 = 0.0f, limit_d2 = 0.0f, l_d2 = FAR;
-  f3 l_c = lc;
+  f3 l_c = sw.lc;
   int l_t = 0, l_region = 0, node = 0, gl = 0;
   bool l_tie = false;
   unsigned long long owed = 0ull;
@@ -545,10 +605,10 @@ __device__ __forceinline__ void mesh_contribution_group(const MeshSlot &s, int g
   // half diagonal.  Only the pruning bound shrinks (never below the true distance): the same closest point is found.
   bool have_prev = false;
   float prev_d = 0.0f;
-  f3 prev_qp = lc;
+  f3 prev_qp = sw.lc;
   auto begin_query = [&]() {
     if (g == 0) CUROBO_MESH_COUNT(0, 1);
-    const float r = full ? max_distance : q_radius;
+    const float r = full ? max_distance : sw.q_radius;
     limit_d2 = best_d2 = r * r;
     if (MESH_PREV_BOUND && have_prev) {
       const f3 dq = qp - prev_qp;
@@ -636,7 +696,7 @@ __device__ __forceinline__ void mesh_contribution_group(const MeshSlot &s, int g
     // ================= the walk of a query is over: settle it (mesh_sdf_within)
     const float dmin = group_min<G>(l_d2);
     const bool found = dmin <= limit_d2;
-    if (!found && !full && q_may_in) {
+    if (!found && !full && sw.q_may_in) {
       const float *rb = m.node_box + 8;  // root box: a point outside it is outside the (closed) surface
       if (!(qp.x < rb[0] || qp.y < rb[1] || qp.z < rb[2] || qp.x > rb[4] || qp.y > rb[5] || qp.z > rb[6])) {
         full = true;  // inside the box, nothing within the radius: far outside in a concavity -- or deep inside
@@ -660,49 +720,10 @@ __device__ __forceinline__ void mesh_contribution_group(const MeshSlot &s, int g
       sdf = inside ? -d : d;
       have_prev = true; prev_d = d; prev_qp = qp;
     }
-    // ================= its terms, and the next sample (mesh_contribution)
-    if (gradient_mode == 1 && sdf > 0.0f) gq = -1.0f * gq;
-    const float pen = -sdf + r_adj;
-    float c = 0.0f, gs = 0.0f;
-    if (pen > 0.0f) {
-      activation_m(pen, eta, c, gs);
-      cost_sum += c;
-      grad_local = grad_local + gs * gq;
-    }
-    if (dir < 0) { sdf_c = sdf; pen_c = pen; c_c = c; gs_c = gs; g_c = gq; }
-    else {
-      if (pen > 0.0f) jump += pen;
-      else if (-pen >= 1000.0f) jump += r_adj;
-      else jump += fmaxf(-pen, r_adj);
-      k++;
-    }
-    if (SWEEP == 0) break;
-    bool have = false;
-#pragma unroll 1
-    while (!have) {
-      if (dir >= 0 && k < SWEEP && !(jump >= half_dist)) { have = true; break; }
-      dir++;
-      if (dir >= 2) break;
-      if (!(dir == 0 ? has_prev : has_next)) continue;
-      if (s.m.sign_rule == 0 && -pen_c > (dir == 0 ? half_w_prev : half_w_next) * 1.0001f + cull_slack) continue;
-      ln = mesh_to_local(s, dir == 0 ? prev_c : next_c);
-      const f3 dd = ln - lc;
-      half_dist = sqrtf(dot(dd, dd)) * 0.5f;
-      inv_half = 1.0f / fmaxf(half_dist, 0.001f);
-      jump = 0.0f;
-      k = SWEEP;
-      if (jump >= half_dist) continue;
-      if (pen_c > 0.0f) { cost_sum += c_c; grad_local = grad_local + gs_c * g_c; jump += pen_c; }
-      else if (-pen_c >= 1000.0f) jump += r_adj;
-      else jump += fmaxf(-pen_c, r_adj);
-      k = 1;
-    }
-    if (!have) break;
-    const float tt = 1.0f - 0.5f * jump * inv_half;
-    qp = tt * lc + (1.0f - tt) * ln;
-    q_radius = (r_adj + (half_dist - jump)) * 1.0001f + 1e-6f;
-    q_may_in = s.m.sign_rule != 0 || sdf_c < half_dist;
-    full = !(q_radius < max_distance);
+    // ================= its terms, and the next sample
+    sw.settle(sdf, gq);
+    if (!sw.next()) break;
+    full = !(sw.q_radius < max_distance);
     begin_query();
   }
 }
@@ -1004,73 +1025,45 @@ __device__ __forceinline__ f3 mesh_to_world_vector_st(const float *st, f3 v) {
   return quat_rot(st[MESH_ST_Q], -st[MESH_ST_Q + 1], -st[MESH_ST_Q + 2], -st[MESH_ST_Q + 3], v);
 }
 
-// mesh_contribution with every query through the cell lists, by a group of G lanes; the item's cost and mesh-frame gradient are
-// ADDED to st[MESH_ST_COST] / st[MESH_ST_GRAD..].  The sphere (centre, neighbours, half steps) and the slot's pose are read from
-// the group's LDS record.  flags: bit 0 / 1 = the previous / next point exists.  Returns false when a query of the item could
-// not be answered by the lists: the caller then hands the sphere to the tree walk.
+// the chain's values in the group's LDS record (MeshSweep): the sphere, its neighbours and half steps, the slot's pose, the
+// centre sample's terms, the item's sums.  flags: bit 0 / 1 = the previous / next point exists.  The cell lists need neither the
+// centre's distance nor "may be inside": neither is kept.
+struct MeshSweepLds {
+  float *st;
+  unsigned flags;
+  bool lipschitz_;
+  __device__ __forceinline__ bool lipschitz() const { return lipschitz_; }
+  __device__ __forceinline__ bool has(int dir) const { return ((flags >> dir) & 1u) != 0u; }
+  __device__ __forceinline__ float half_w(int dir) const { return st[MESH_ST_HALF_PREV + dir]; }
+  __device__ __forceinline__ f3 neighbour(int dir) const { return mesh_to_local_st(st, st_load3(st, dir == 0 ? MESH_ST_PREV : MESH_ST_NEXT)); }
+  __device__ __forceinline__ void add(float c, float gs, f3 g) {
+    st[MESH_ST_COST] += c;
+    st_store3(st, MESH_ST_GRAD, st_load3(st, MESH_ST_GRAD) + gs * g);
+  }
+  __device__ __forceinline__ void keep_centre(float, float pen, float c, float gs, f3 g) {
+    st[MESH_ST_PEN_C] = pen; st[MESH_ST_C_C] = c; st[MESH_ST_GS_C] = gs; st_store3(st, MESH_ST_GC, g);
+  }
+  __device__ __forceinline__ void add_centre() { add(st[MESH_ST_C_C], st[MESH_ST_GS_C], st_load3(st, MESH_ST_GC)); }
+  __device__ __forceinline__ float pen_c() const { return st[MESH_ST_PEN_C]; }
+  __device__ __forceinline__ float sdf_c() const { return 0.0f; }
+};
+
+// The chain with every query through the cell lists, by a group of G lanes; the item's cost and mesh-frame gradient are ADDED to
+// st[MESH_ST_COST] / st[MESH_ST_GRAD..].  Returns the code of the first query the lists could not answer (the caller then hands
+// the whole sphere on), else MESH_CELLS_OK.
 template <int SWEEP, int G, int U>
 __device__ __forceinline__ int mesh_contribution_cells(const MeshPoseSlot &s, int gradient_mode, float *st, unsigned flags,
                                                        float r_adj, float eta, float reach, unsigned stat_q = 0u) {
-  const float max_distance = fmaxf(s.max_half_diag, r_adj);
-  const float cull_slack = 2e-6f + 1e-6f * max_distance;
-  const bool lipschitz = s.mp->sign_rule == 0;
   const MeshCellsView mv = load_cells_view(s.mp, st);
-  const f3 lc = mesh_to_local_st(st, st_load3(st, MESH_ST_CENTER));
-  f3 ln = lc, qp = lc;
-  float half_dist = 0.0f, inv_half = 0.0f, jump = 0.0f;
-  float q_radius = (r_adj + reach + cull_slack) * 1.0001f + 1e-6f;
-  int dir = -1, k = 0;
+  MeshSweep<SWEEP, MeshSweepLds> sw(MeshSweepLds{st, flags, s.mp->sign_rule == 0}, gradient_mode,
+                                    mesh_to_local_st(st, st_load3(st, MESH_ST_CENTER)), r_adj, eta, s.max_half_diag, reach);
 #pragma unroll 1
-  for (;;) {
+  do {
     f3 g;
     float sdf;
-    if (const int code = mesh_cells_sdf<G, U>(mv, qp, q_radius, max_distance, sdf, g, stat_q)) return code;
-    if (gradient_mode == 1 && sdf > 0.0f) g = -1.0f * g;
-    const float pen = -sdf + r_adj;
-    float c = 0.0f, gs = 0.0f;
-    if (pen > 0.0f) {
-      activation_m(pen, eta, c, gs);
-      st[MESH_ST_COST] += c;
-      st_store3(st, MESH_ST_GRAD, st_load3(st, MESH_ST_GRAD) + gs * g);
-    }
-    if (dir < 0) { st[MESH_ST_PEN_C] = pen; st[MESH_ST_C_C] = c; st[MESH_ST_GS_C] = gs; st_store3(st, MESH_ST_GC, g); }
-    else {
-      if (pen > 0.0f) jump += pen;
-      else if (-pen >= 1000.0f) jump += r_adj;
-      else jump += fmaxf(-pen, r_adj);
-      k++;
-    }
-    if (SWEEP == 0) break;
-    bool have = false;
-#pragma unroll 1
-    while (!have) {
-      if (dir >= 0 && k < SWEEP && !(jump >= half_dist)) { have = true; break; }
-      dir++;
-      if (dir >= 2) break;
-      if (!((flags >> dir) & 1u)) continue;
-      const float pen_c = st[MESH_ST_PEN_C];
-      if (lipschitz && -pen_c > st[MESH_ST_HALF_PREV + dir] * 1.0001f + cull_slack) continue;
-      ln = mesh_to_local_st(st, st_load3(st, dir == 0 ? MESH_ST_PREV : MESH_ST_NEXT));
-      const f3 dd = ln - lc;
-      half_dist = sqrtf(dot(dd, dd)) * 0.5f;
-      inv_half = 1.0f / fmaxf(half_dist, 0.001f);
-      jump = 0.0f;
-      k = SWEEP;
-      if (jump >= half_dist) continue;
-      if (pen_c > 0.0f) {
-        st[MESH_ST_COST] += st[MESH_ST_C_C];
-        st_store3(st, MESH_ST_GRAD, st_load3(st, MESH_ST_GRAD) + st[MESH_ST_GS_C] * st_load3(st, MESH_ST_GC));
-        jump += pen_c;
-      }
-      else if (-pen_c >= 1000.0f) jump += r_adj;
-      else jump += fmaxf(-pen_c, r_adj);
-      k = 1;
-    }
-    if (!have) break;
-    const float tt = 1.0f - 0.5f * jump * inv_half;
-    qp = tt * lc + (1.0f - tt) * ln;
-    q_radius = (r_adj + (half_dist - jump)) * 1.0001f + 1e-6f;
-  }
+    if (const int code = mesh_cells_sdf<G, U>(mv, sw.qp, sw.q_radius, sw.max_distance, sdf, g, stat_q)) return code;
+    sw.settle(sdf, g);
+  } while (sw.next());
   return MESH_CELLS_OK;
 }
 
