@@ -32,7 +32,8 @@
 // This header holds the device machinery every fused launch shares (argument block, LDS layout, staging, the per-point
 // phases) and the trajectory kernel template.  Its users: rollout_fused.hip (generic instantiations, dispatch, C ABI),
 // rollout_fused_shape.hip (one compile-time shape per translation unit), rollout_ik_fused.hip (horizon-1 IK launch) and
-// graph_planner.hip (edge steering).  Device code and a few pure host predicates only: no global state, no exports.
+// graph_planner.hip (edge steering).  Device code, a few pure host predicates and the host functions their entry points share
+// (argument block, dimension checks, launch): no global state, no exports.
 #pragma once
 
 #include <cstddef>
@@ -275,6 +276,49 @@ __device__ __forceinline__ float self_pair_apply(const FusedCtx &c, int h, float
   wrench_add(wr, cumul, c.sph_link[i], make_f3(s1.x, s1.y, s1.z), g);
   wrench_add(wr, cumul, c.sph_link[j], make_f3(s2.x, s2.y, s2.z), -1.0f * g);
   return 0.5f * c.w_self * m;
+}
+// ... named by a pair_key (its inverse: penetration in the high word, 0x7fffffff - pair index in the low one)
+__device__ __forceinline__ float self_pair_apply_key(const FusedCtx &c, int h, unsigned long long key) {
+  return self_pair_apply(c, h, __uint_as_float((uint32_t)(key >> 32)), (int)(0x7fffffffu - (uint32_t)key));
+}
+
+// Arg-max of a 16-lane row over the staged pair list of its point (spheres sph; reference self_collision_kernel.cuh:19-111):
+// returns the largest penetration and, in kmin, the lowest pair index at it (0x7fffffff when nothing penetrates).
+// One pass over the padded list (no bounds checks; disabled / padding spheres are NaN and lose every max).  Per pair only a
+// v_max; the arg-max is tracked per group of U pairs (one compare per group) and resolved inside the winning group afterwards.
+__device__ __forceinline__ float row_pair_argmax(const FusedCtx &c, const float4 *sph, int lane, int &kmin) {
+  constexpr int U = 4;
+  const int P_pad = (c.P + 63) & ~63;
+  float best = 0.0f;
+  int best_k0 = 0x7fffffff;
+  for (int k0 = lane; k0 < P_pad; k0 += kFkLanes * U) {
+    uint32_t ij[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) ij[u] = c.pairs[k0 + u * kFkLanes];
+    float gmax = staged_pair_penetration(sph, ij[0]);
+#pragma unroll
+    for (int u = 1; u < U; u++) gmax = fmaxf(gmax, staged_pair_penetration(sph, ij[u]));
+    if (gmax > best) { best = gmax; best_k0 = k0; }
+  }
+  float m = row16_max(best);
+  kmin = 0x7fffffff;
+  if (m > 0.0f) {  // rows in self collision: lowest pair index of the largest penetration
+    int best_k = 0x7fffffff;
+    if (best == m) {
+      float f_best = 0.0f;
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const float f = staged_pair_penetration(sph, c.pairs[best_k0 + u * kFkLanes]);
+        if (f > f_best) { f_best = f; best_k = best_k0 + u * kFkLanes; }
+      }
+      best = f_best;
+    } else {
+      best = 0.0f;
+    }
+    m = row16_max(best);
+    kmin = row16_min((best == m && best > 0.0f) ? best_k : 0x7fffffff);
+  }
+  return m;
 }
 
 // order-preserving float <-> int map (its own inverse) so that integer atomic min/max order floats
@@ -622,6 +666,26 @@ __device__ __forceinline__ void point_sphere(const FusedCtx &c, const FusedTrajA
   // disabled spheres (negative radius) carry NaN: every pair test against them compares false
   w4.w = (w4.w + c.sph_pad[s]) >= 0.0f ? w4.w + c.sph_pad[s] : __builtin_nanf("");
   reinterpret_cast<float4 *>(c.work + (size_t)h * c.ws)[s] = w4;
+}
+// the all-NaN sphere behind the last one of point h: what the padding entries of the pair lists name
+__device__ __forceinline__ void point_sentinel_sphere(const FusedCtx &c, int h) {
+  reinterpret_cast<float4 *>(c.work + (size_t)h * c.ws)[c.S] = make_float4(0.f, 0.f, 0.f, __builtin_nanf(""));
+}
+
+// FK of point h on its own 16-lane row (the IK and steering launches: one row per configuration): local transforms -> chain ->
+// world spheres -> sentinel; b = the row of the optional sphere output.  The row's later readers sit behind a workgroup barrier
+// or a wavefront fence of the caller's.
+__device__ __forceinline__ void point_fk_row(const FusedCtx &c, const FusedTrajArgs &a, int b, int h, int lane) {
+  point_fk_locals(c, h, lane);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  float *const cm[1] = {c.cumul + (size_t)h * c.L * 12};
+  const float *const lc[1] = {c.work + (size_t)h * c.ws};
+  fk_chain_16_multi<1>(cm, lc, c.parent, c.fixed, c.L, lane);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  for (int s = lane; s < c.S; s += kFkLanes) point_sphere(c, a, b, h, s);
+  if (lane == 0) point_sentinel_sphere(c, h);
 }
 
 // Tool-pose goal-set cost of point h (batch row n, horizon position hh of tp.horizon) for every
@@ -1212,8 +1276,7 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
       sp += step_s; h += step_h;
       if (sp >= S) { sp -= S; h++; }
     }
-    for (int hh = tid; hh < H; hh += nt)
-      reinterpret_cast<float4 *>(c.work + (size_t)hh * c.ws)[S] = make_float4(0.f, 0.f, 0.f, __builtin_nanf(""));
+    for (int hh = tid; hh < H; hh += nt) point_sentinel_sphere(c, hh);
   }
   CUROBO_STAMP(10);
   if (tid == 0) { c.key[0] = 0ull; c.key[1] = 0ull; }  // leftover point: arg-max key of its pair list, ticket for its scene pass
@@ -1253,6 +1316,8 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
         sp[r] = reinterpret_cast<const char *>(c.spheres(ok[r] ? hr : 0));
       }
       float bm[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      // (the lane-list walk stands three times in this kernel -- here, the index search and the leftover point's slice below:
+      // stated once it moved the register allocation of the compile-time shapes, docs/NOTEBOOK.md)
       const uint32_t *ll = c.lanel + lane64;
       for (int pass = 0; pass < 2; pass++) {
         const int len = pass == 0 ? c.lane_len0 : c.lane_len1;
@@ -1277,7 +1342,7 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
         const float m = wave64_max(bm[r]);
         if (m > 0.0f && ok[r]) {  // (wave-uniform) in self collision: lowest pair index of the largest penetration
           int kb = 0x7fffffff;
-          const uint32_t *l2 = c.lanel + lane64;
+          const uint32_t *l2 = c.lanel + lane64;  // (a copy of the lane-list walk above)
           for (int pass = 0; pass < 2; pass++) {
             const int len = pass == 0 ? c.lane_len0 : c.lane_len1;
             const int own_i = pass * 64 + lane64;
@@ -1297,41 +1362,9 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
         any_grad = true;
         if (lane == 0) cost_pt += self_pair_apply(c, h, m_row, k_row);
       }
-    } else if (a.use_self && valid) {  // reference self_collision_kernel.cuh:19-111
-      // One pass over the padded pair list (no bounds checks; disabled / padding spheres are NaN and
-      // lose every max).  Per pair only a v_max; the arg-max is tracked per group of U pairs (one
-      // compare per group) and resolved inside the winning group afterwards.
-      constexpr int U = 4;
-      const int P_pad = (P + 63) & ~63;
-      float best = 0.0f;
-      int best_k0 = 0x7fffffff;
-      for (int k0 = lane; k0 < P_pad; k0 += kFkLanes * U) {
-        uint32_t ij[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) ij[u] = c.pairs[k0 + u * kFkLanes];
-        float gmax = staged_pair_penetration(sph, ij[0]);
-#pragma unroll
-        for (int u = 1; u < U; u++) gmax = fmaxf(gmax, staged_pair_penetration(sph, ij[u]));
-        if (gmax > best) { best = gmax; best_k0 = k0; }
-      }
-      float m = row16_max(best);
-      int kmin = 0x7fffffff;
-      if (m > 0.0f) {  // rows in self collision: lowest pair index of the largest penetration
-        int best_k = 0x7fffffff;
-        if (best == m) {
-          float f_best = 0.0f;
-#pragma unroll
-          for (int u = 0; u < U; u++) {
-            const float f = staged_pair_penetration(sph, c.pairs[best_k0 + u * kFkLanes]);
-            if (f > f_best) { f_best = f; best_k = best_k0 + u * kFkLanes; }
-          }
-          best = f_best;
-        } else {
-          best = 0.0f;
-        }
-        m = row16_max(best);
-        kmin = row16_min((best == m && best > 0.0f) ? best_k : 0x7fffffff);
-      }
+    } else if (a.use_self && valid) {  // the pair list as staged (i, j) offsets: the row's own arg-max
+      int kmin;
+      const float m = row_pair_argmax(c, sph, lane, kmin);
       if (kmin != 0x7fffffff && m > 0.0f) {
         any_grad = true;
         if (lane == 0) cost_pt += self_pair_apply(c, h, m, kmin);
@@ -1345,7 +1378,7 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
       int kl = 0x7fffffff;
       if (use_lanes) {  // the list entries of a lane are dealt over the wavefronts
         const char *spl = reinterpret_cast<const char *>(sphl);
-        const uint32_t *ll = c.lanel + lane64;
+        const uint32_t *ll = c.lanel + lane64;  // (a copy of the lane-list walk above, entries dealt over the wavefronts)
         for (int pass = 0; pass < 2; pass++) {
           const int len = pass == 0 ? c.lane_len0 : c.lane_len1;
           const int own_i = pass * 64 + lane64;
@@ -1377,6 +1410,8 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
         wave_scene_pass<SWEEP, KINDS, !TERMS && KINDS == 1>(c, a.sc, h, valid, lane, lane64, c.lists + (tid >> 6) * kRings * kSceneListEntries, row_stride,
                                               a.scene_rows == 2 ? 1 : 64);
       } else if (valid) {  // beyond the ring's entry format: one sphere per lane, all its obstacles
+        // (the sphere-per-lane scene loop stands four times -- here, the leftover point below, rollout_ik_fused.hip, graph_planner.hip:
+        // stated once it moved the register allocation of every kernel that holds it, docs/NOTEBOOK.md)
         const float *wr = c.wrench + (size_t)h * c.wl;
         float cost_scene = 0.0f;
         bool any_scene = false;
@@ -1421,7 +1456,7 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
       const float *wr = c.wrench + (size_t)h * c.wl;
       float cost_scene = 0.0f;
       bool any_scene = false;
-      for (int s0 = 0; s0 < S; s0 += 64) {
+      for (int s0 = 0; s0 < S; s0 += 64) {  // (a copy of the sphere-per-lane scene loop of the row fallback above, on 64 lanes)
         const int s = s0 + lane64;
         float d = 0.0f;
         f3 g = make_f3(0.f, 0.f, 0.f);
@@ -1471,7 +1506,7 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
       const unsigned long long key = *c.key;
       if (key != 0ull) {
         any_grad = true;
-        if (lane == 0) cost_pt += self_pair_apply(c, h, __uint_as_float((uint32_t)(key >> 32)), (int)(0x7fffffffu - (uint32_t)key));
+        if (lane == 0) cost_pt += self_pair_apply_key(c, h, key);
       }
       if (a.use_scene) {
         const float4 *sph = c.spheres(h);
@@ -1491,7 +1526,7 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
   if (fold_left && a.use_self && grp == 0) {
     const unsigned long long key = *c.key;
     if (key != 0ull && lane == 0) {
-      c.cost[H_main] += self_pair_apply(c, H_main, __uint_as_float((uint32_t)(key >> 32)), (int)(0x7fffffffu - (uint32_t)key));
+      c.cost[H_main] += self_pair_apply_key(c, H_main, key);
       c.flag[H_main] = 1;
     }
   }
@@ -1598,6 +1633,59 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
   CUROBO_STAMP(4);
 #undef CUROBO_STAMP
   if (reorder) fused_dispatch_epilogue(t_begin, b, smem, tid3, nt);
+}
+
+// ---- host: what the entry points of the fused launches (trajectory, IK, steering) share
+// The robot / self / scene members of an argument block from an entry point's arguments.  The rules: self collision needs a pair
+// list with pairs in it, scene collision a scene -- and each its weight where the launch has weights (need_weights; steering
+// has none); npairs is 0 without self collision, the scene's counts are 0 without scene collision; num_envs is at least 1.
+inline void fused_fill_robot_args(FusedTrajArgs &a, bool need_weights, const float *fixed_transform, const float *robot_spheres,
+                                  const int8_t *joint_map_type, const int16_t *joint_map, const int16_t *link_map,
+                                  const int16_t *link_sphere_map, const int16_t *link_chain_data, const int16_t *link_chain_offsets,
+                                  const float *joint_offset_map, const float *sphere_padding, const float *self_collision_weight,
+                                  const int16_t *pair_locations, const curobo_hip_scene *scene, const float *scene_collision_weight,
+                                  const float *activation_distance, const int32_t *env_query_idx, int num_envs, int use_multi_env,
+                                  int batch_size, int dof, int num_links, int num_spheres, int num_collision_pairs, int link_chain_len) {
+  a.bs.dof = dof;
+  a.fixed_transform = fixed_transform; a.robot_spheres = robot_spheres; a.joint_offset = joint_offset_map;
+  a.joint_map_type = joint_map_type; a.joint_map = joint_map; a.link_map = link_map; a.link_sphere_map = link_sphere_map;
+  a.link_chain_data = link_chain_data; a.link_chain_offsets = link_chain_offsets;
+  a.sphere_padding = sphere_padding; a.w_self = self_collision_weight; a.pairs = pair_locations;
+  a.use_self = (pair_locations && (self_collision_weight || !need_weights) && num_collision_pairs > 0) ? 1 : 0;
+  a.use_scene = (scene && (scene_collision_weight || !need_weights)) ? 1 : 0;
+  if (scene) a.sc = *scene;
+  if (!a.use_scene) { a.sc.max_cuboids = 0; a.sc.max_voxel_grids = 0; }
+  a.w_scene = scene_collision_weight; a.eta = activation_distance; a.env_query_idx = env_query_idx;
+  a.batch = batch_size; a.nlinks = num_links; a.nspheres = num_spheres; a.npairs = a.use_self ? num_collision_pairs : 0;
+  a.chain_len = link_chain_len; a.num_envs = num_envs > 1 ? num_envs : 1; a.use_multi_env = use_multi_env ? 1 : 0;
+}
+// the dimension checks every fused entry point makes (a launch's own checks stay with it)
+inline int fused_check_dimensions(const char *what, int num_links, int num_spheres, int link_chain_len, const void *pair_locations) {
+  CUROBO_REQUIRE(num_links >= 1 && num_links <= 128, "%s: bad dimensions", what);
+  CUROBO_REQUIRE(num_spheres < 4096, "%s: at most 4095 spheres", what);
+  CUROBO_REQUIRE(link_chain_len >= 1, "%s: link_chain_len must be >= 1", what);
+  CUROBO_REQUIRE(((uintptr_t)pair_locations & 3) == 0, "%s: pair_locations must be 4-byte aligned", what);
+  return CUROBO_HIP_OK;
+}
+// obstacle kinds of a scene = the KINDS instantiation its launch takes: 1 cuboids, 2 voxel grids, 3 both; scenes with analytic
+// primitives in the cuboid store run the one instantiation that tests the tag (7)
+inline int fused_scene_kinds(const curobo_hip_scene &sc) {
+  return (sc.max_cuboids > 0 && sc.cuboid_has_primitives) ? 7 : ((sc.max_cuboids > 0 ? 1 : 0) | (sc.max_voxel_grids > 0 ? 2 : 0));
+}
+// Launches kfn with `lds` bytes of dynamic LDS, after raising the kernel's limit when that is more than `raise_above` (64 KB is
+// what a kernel may take unasked; a kernel with static LDS of its own passes less).  Returns the attribute call's error, in
+// which case nothing was launched.
+constexpr size_t kFusedLdsUnasked = 64 * 1024;
+template <class Kernel, class Args>
+inline hipError_t fused_launch(Kernel kfn, dim3 grid, dim3 block, size_t lds, size_t raise_above, hipStream_t st, const Args &args) {
+  const hipError_t e = lds > raise_above ? hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+  if (e == hipSuccess) hipLaunchKernelGGL(kfn, grid, block, lds, st, args);
+  return e;
+}
+// ... and what the entry point returns after it
+inline int fused_launch_status(const char *what, hipError_t e, hipStream_t st) {
+  if (e != hipSuccess) return set_error(CUROBO_HIP_ERR_LAUNCH, "%s: cannot raise LDS limit: %s", what, hipGetErrorString(e));
+  return check_launch(what, st);
 }
 
 // ---- compile-time shapes (fused_shapes.hpp): the host predicates their launchers share

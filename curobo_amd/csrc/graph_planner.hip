@@ -169,17 +169,8 @@ __global__ void __launch_bounds__(256, 4) graph_steer_kernel(const FusedSteerArg
       __syncthreads();
       bool bad = false;
       if (live) {
-        point_fk_locals(c, h, lane);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        float *const cm[1] = {c.cumul + (size_t)h * L * 12};
-        const float *const lc[1] = {c.work + (size_t)h * c.ws};
-        fk_chain_16_multi<1>(cm, lc, c.parent, c.fixed, L, lane);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int sp = lane; sp < S; sp += kFkLanes) point_sphere(c, a, 0, h, sp);
-        if (lane == 0) reinterpret_cast<float4 *>(c.work + (size_t)h * c.ws)[S] = make_float4(0.f, 0.f, 0.f, __builtin_nanf(""));
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        point_fk_row(c, a, 0, h, lane);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (no workgroup barrier between the row's spheres and their readers here)
         __builtin_amdgcn_wave_barrier();
         // joint bounds (cspace_bound_term with unit weight and no activation margin, as RobotCollisionChecker.get_bound)
         float viol = 0.0f;
@@ -199,7 +190,7 @@ __global__ void __launch_bounds__(256, 4) graph_steer_kernel(const FusedSteerArg
         if (a.use_scene) {
           point_link_masks<0, KINDS>(c, a.sc, h, lane);
           const float *wr = c.wrench + (size_t)h * c.wl;
-          for (int s0 = 0; s0 < S; s0 += kFkLanes) {
+          for (int s0 = 0; s0 < S; s0 += kFkLanes) {  // (a copy of the sphere-per-lane scene loop of the trajectory kernel's row fallback, without the wrenches)
             const int sp = s0 + lane;
             float d = 0.0f;
             f3 g = make_f3(0.f, 0.f, 0.f);
@@ -236,26 +227,16 @@ CUROBO_EXPORT int curobo_hip_graph_steer(
     const float *joint_offset_map, const float *sphere_padding, const int16_t *pair_locations, const curobo_hip_scene *scene,
     int dof, int num_links, int num_spheres, int num_collision_pairs, int link_chain_len, curobo_hip_stream_t stream) {
   const char *what = "graph_steer";
-  CUROBO_REQUIRE(num_links >= 1 && num_links <= 128 && dof >= 1 && dof <= 64 && ld >= dof, "%s: bad dimensions", what);
-  CUROBO_REQUIRE(link_chain_len >= 1, "%s: link_chain_len must be >= 1", what);
-  CUROBO_REQUIRE(num_spheres < 4096, "%s: at most 4095 spheres", what);
-  CUROBO_REQUIRE(((uintptr_t)pair_locations & 3) == 0, "%s: pair_locations must be 4-byte aligned", what);
+  if (const int bad = fused_check_dimensions(what, num_links, num_spheres, link_chain_len, pair_locations)) return bad;
+  CUROBO_REQUIRE(dof >= 1 && dof <= 64 && ld >= dof, "%s: bad dimensions", what);
   CUROBO_REQUIRE(point_mode ? out_feasible != nullptr : (out_node && out_index && max_steps_ws && cspace_distance_weight
                  && target && cspace_similarity_threshold > 0.0f), "%s: missing outputs / inputs for this mode", what);
   if (n == 0) return CUROBO_HIP_OK;
   FusedSteerArgs ga{};
   FusedTrajArgs &a = ga.r;
-  a.bs.dof = dof;
-  a.fixed_transform = fixed_transform; a.robot_spheres = robot_spheres; a.joint_offset = joint_offset_map;
-  a.joint_map_type = joint_map_type; a.joint_map = joint_map; a.link_map = link_map; a.link_sphere_map = link_sphere_map;
-  a.link_chain_data = link_chain_data; a.link_chain_offsets = link_chain_offsets;
-  a.sphere_padding = sphere_padding; a.pairs = pair_locations;
-  a.use_self = (pair_locations && num_collision_pairs > 0) ? 1 : 0;
-  a.use_scene = scene ? 1 : 0;
-  if (scene) a.sc = *scene;
-  if (!a.use_scene) { a.sc.max_cuboids = 0; a.sc.max_voxel_grids = 0; }
-  a.batch = n; a.nlinks = num_links; a.nspheres = num_spheres; a.npairs = a.use_self ? num_collision_pairs : 0;
-  a.chain_len = link_chain_len; a.num_envs = 1; a.use_multi_env = 0;
+  fused_fill_robot_args(a, false, fixed_transform, robot_spheres, joint_map_type, joint_map, link_map, link_sphere_map, link_chain_data,
+                        link_chain_offsets, joint_offset_map, sphere_padding, nullptr, pair_locations, scene, nullptr, nullptr, nullptr,
+                        1, 0, n, dof, num_links, num_spheres, num_collision_pairs, link_chain_len);
   ga.start = start; ga.target = point_mode ? start : target; ga.p_b = p_b; ga.max_steps = max_steps_ws;
   ga.out_node = out_node; ga.out_index = out_index; ga.out_feasible = out_feasible;
   ga.n = n; ga.ld = ld; ga.point_mode = point_mode ? 1 : 0;
@@ -270,24 +251,11 @@ CUROBO_EXPORT int curobo_hip_graph_steer(
     const int err = check_launch("graph_steer_max_steps", st);
     if (err != CUROBO_HIP_OK) return err;
   }
-  const int kinds = (a.sc.max_cuboids > 0 && a.sc.cuboid_has_primitives) ? 7 : ((a.sc.max_cuboids > 0 ? 1 : 0) | (a.sc.max_voxel_grids > 0 ? 2 : 0));
-  const int items = point_mode ? ceil_div(n, kIkPoints) : n;
+  const int kinds = fused_scene_kinds(a.sc), items = point_mode ? ceil_div(n, kIkPoints) : n;
   const dim3 grid((unsigned)(items < 2048 ? items : 2048)), block(kIkPoints * kFkLanes);
-#define CUROBO_STEER_LAUNCH(KD)                                                                                 \
-  do {                                                                                                          \
-    auto kfn = graph_steer_kernel<KD>;                                                                          \
-    if (lds > 60 * 1024) {                                                                                      \
-      hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      if (e != hipSuccess) return set_error(CUROBO_HIP_ERR_LAUNCH, "%s: cannot raise LDS limit: %s", what, hipGetErrorString(e)); \
-    }                                                                                                           \
-    hipLaunchKernelGGL(kfn, grid, block, lds, st, ga);                                                          \
-  } while (0)
-  if (kinds == 2) CUROBO_STEER_LAUNCH(2);
-  else if (kinds == 3) CUROBO_STEER_LAUNCH(3);
-  else if (kinds == 7) CUROBO_STEER_LAUNCH(7);
-  else CUROBO_STEER_LAUNCH(1);
-#undef CUROBO_STEER_LAUNCH
-  return check_launch(what, st);
+  const auto kfn = kinds == 2 ? graph_steer_kernel<2> : kinds == 3 ? graph_steer_kernel<3> : kinds == 7 ? graph_steer_kernel<7> : graph_steer_kernel<1>;
+  // (the kernel also has static LDS: the limit is raised 4 KB below what a kernel may take unasked)
+  return fused_launch_status(what, fused_launch(kfn, grid, block, lds, 60 * 1024, st, ga), st);
 }
 
 }  // namespace curobo_hip

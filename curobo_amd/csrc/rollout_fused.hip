@@ -190,11 +190,8 @@ static int rollout_trajectory_fused_impl(
     int self_lane_len, const FusedReuse &reuse, curobo_hip_stream_t stream) {
   CUROBO_REQUIRE(bspline_degree >= 3 && bspline_degree <= 5, "%s: bspline_degree must be 3, 4 or 5", what);
   CUROBO_REQUIRE(sweep_steps == 0 || sweep_steps == 3, "%s: sweep_steps must be 0 or 3", what);
-  CUROBO_REQUIRE(num_links >= 1 && num_links <= 128 && dof >= 1 && padded_horizon >= 2 && n_knots >= 1,
-                 "%s: bad dimensions", what);
-  CUROBO_REQUIRE(num_spheres < 4096, "%s: at most 4095 spheres", what);
-  CUROBO_REQUIRE(link_chain_len >= 1, "%s: link_chain_len must be >= 1", what);
-  CUROBO_REQUIRE(((uintptr_t)pair_locations & 3) == 0, "%s: pair_locations must be 4-byte aligned", what);
+  if (const int bad = fused_check_dimensions(what, num_links, num_spheres, link_chain_len, pair_locations)) return bad;
+  CUROBO_REQUIRE(dof >= 1 && padded_horizon >= 2 && n_knots >= 1, "%s: bad dimensions", what);
   const bool any_memo = reuse.x || reuse.cost || reuse.grad;
   if (any_memo) {
     CUROBO_REQUIRE(reuse.x && reuse.cost && reuse.grad, "%s: memo_x, memo_cost and memo_grad must be given together (all three or none)", what);
@@ -216,16 +213,11 @@ static int rollout_trajectory_fused_impl(
   a.bs.goal[0] = goal_position; a.bs.goal[1] = goal_velocity; a.bs.goal[2] = goal_acceleration; a.bs.goal[3] = goal_jerk;
   a.bs.start_idx = start_idx; a.bs.goal_idx = goal_idx; a.bs.traj_dt = traj_dt; a.bs.use_implicit_goal = use_implicit_goal_state;
   a.bs.batch = batch_size; a.bs.padded_horizon = padded_horizon; a.bs.dof = dof; a.bs.n_knots = n_knots;
-  a.fixed_transform = fixed_transform; a.robot_spheres = robot_spheres; a.joint_offset = joint_offset_map;
-  a.joint_map_type = joint_map_type; a.joint_map = joint_map; a.link_map = link_map; a.link_sphere_map = link_sphere_map;
-  a.link_chain_data = link_chain_data; a.link_chain_offsets = link_chain_offsets;
-  a.sphere_padding = sphere_padding; a.w_self = self_collision_weight; a.pairs = pair_locations;
-  a.use_self = (pair_locations && self_collision_weight && num_collision_pairs > 0) ? 1 : 0;
-  a.use_scene = (scene && scene_collision_weight) ? 1 : 0;
-  if (scene) a.sc = *scene;
-  a.w_scene = scene_collision_weight; a.eta = activation_distance; a.speed_dt = speed_dt; a.env_query_idx = env_query_idx;
-  a.batch = batch_size; a.nlinks = num_links; a.nspheres = num_spheres; a.npairs = a.use_self ? num_collision_pairs : 0;
-  a.chain_len = link_chain_len; a.dpad = dof | 1; a.num_envs = num_envs; a.use_multi_env = use_multi_env;
+  fused_fill_robot_args(a, true, fixed_transform, robot_spheres, joint_map_type, joint_map, link_map, link_sphere_map, link_chain_data,
+                        link_chain_offsets, joint_offset_map, sphere_padding, self_collision_weight, pair_locations, scene,
+                        scene_collision_weight, activation_distance, env_query_idx, num_envs, use_multi_env, batch_size, dof, num_links,
+                        num_spheres, num_collision_pairs, link_chain_len);
+  a.speed_dt = speed_dt; a.dpad = dof | 1;
   a.enable_speed_metric = (a.use_scene && enable_speed_metric) ? 1 : 0;
   a.prof = g_fused_prof;
   if (g_fused_prof_seq && g_fused_prof_next < g_fused_prof_blocks && batch_size <= g_fused_prof_rows)
@@ -242,8 +234,7 @@ static int rollout_trajectory_fused_impl(
   a.scene_rows = scene_rows;
   CUROBO_REQUIRE(!dispatch_ws || dispatch_phase == 0 || dispatch_phase == 1, "%s: dispatch_phase must be 0 or 1", what);
   CUROBO_REQUIRE(!a.enable_speed_metric || speed_dt, "%s: speed metric needs speed_dt", what);
-  const int n_rec = a.use_scene ? a.sc.max_cuboids + a.sc.max_voxel_grids : 0;
-  if (!a.use_scene) { a.sc.max_cuboids = 0; a.sc.max_voxel_grids = 0; }
+  const int n_rec = a.sc.max_cuboids + a.sc.max_voxel_grids;
   if (terms) {
     const curobo_hip_trajopt_terms &t = *terms;
     a.use_pose = (t.n_tool_frames > 0 && t.goal_position) ? 1 : 0;
@@ -305,26 +296,8 @@ static int rollout_trajectory_fused_impl(
   CUROBO_REQUIRE(!a.use_torque || fused_torque_fits(lay, padded_horizon, dof, num_links, num_spheres),
                  "%s: the inverse-dynamics state of this robot does not fit the LDS regions it borrows; run the torque "
                  "limits on the kernel sequence (curobo_hip_rollout_trajopt_fused_torque_fits)", what);
-  // scenes with analytic primitives in the cuboid store run the one instantiation that tests the tag (KINDS = 7)
-  const int kinds = (a.sc.max_cuboids > 0 && a.sc.cuboid_has_primitives) ? 7 : ((a.sc.max_cuboids > 0 ? 1 : 0) | (a.sc.max_voxel_grids > 0 ? 2 : 0));
+  const int kinds = fused_scene_kinds(a.sc);
   hipStream_t st = (hipStream_t)stream;
-#define CUROBO_FUSED_KERNEL_OF(DG, SW, KD) \
-  (with_terms ? rollout_trajectory_fused_kernel<DG, SW, KD, true> : rollout_trajectory_fused_kernel<DG, SW, KD, false>)
-#define CUROBO_FUSED_LAUNCH(DG, SW, KD)                                                                        \
-  do {                                                                                                         \
-    auto kfn = CUROBO_FUSED_KERNEL_OF(DG, SW, KD);                                                             \
-    if (lds > 64 * 1024) {                                                                                     \
-      hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      if (e != hipSuccess) return set_error(CUROBO_HIP_ERR_LAUNCH, "%s: cannot raise LDS limit: %s", what, hipGetErrorString(e)); \
-    }                                                                                                          \
-    static const bool dbg = getenv("CUROBO_HIP_FUSED_DEBUG") != nullptr;                                      \
-    if (dbg) {                                                                                                 \
-      int nb = -1;                                                                                             \
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kfn, threads, lds);                      \
-      fprintf(stderr, "[curobo_hip] fused: threads %d lds %zu -> %d workgroups/CU\n", threads, lds, nb); \
-    }                                                                                                          \
-    hipLaunchKernelGGL(kfn, dim3((unsigned)batch_size), dim3(threads), lds, st, a);                            \
-  } while (0)
   {  // a compile-time shape that matches every dimension of this launch (fused_shapes.hpp), most specific first
     static const bool env_off = getenv("CUROBO_HIP_FUSED_NO_SHAPES") != nullptr;  // development knob: always the generic kernel
     const bool no_shapes = env_off || !g_fused_shapes_enabled;
@@ -332,39 +305,35 @@ static int rollout_trajectory_fused_impl(
     if (!no_shapes) {  // shapes compiled at run time for this robot / horizon
       for (fused_jit_launcher_t fn : fused_jit_shapes()) {
         int e = 0;
-        if (fn(&a, bspline_degree, sweep_steps, kinds, with_terms ? 1 : 0, batch_size, threads, lds, (void *)st, &e)) {
-          if (e != 0) return set_error(CUROBO_HIP_ERR_LAUNCH, "%s: cannot raise LDS limit: %s", what, hipGetErrorString((hipError_t)e));
-          return check_launch(what, st);
-        }
+        if (fn(&a, bspline_degree, sweep_steps, kinds, with_terms ? 1 : 0, batch_size, threads, lds, (void *)st, &e))
+          return fused_launch_status(what, (hipError_t)e, st);
       }
     }
-#define CUROBO_FUSED_TRY_SHAPE(ID)                                                                                              \
-    if (!no_shapes && fused_shape_launch_##ID(a, bspline_degree, sweep_steps, kinds, with_terms, batch_size, threads, lds, st, &se)) { \
-      if (se != hipSuccess) return set_error(CUROBO_HIP_ERR_LAUNCH, "%s: cannot raise LDS limit: %s", what, hipGetErrorString(se));  \
-      return check_launch(what, st);                                                                                            \
-    }
+#define CUROBO_FUSED_TRY_SHAPE(ID)                                                                                            \
+    if (!no_shapes && fused_shape_launch_##ID(a, bspline_degree, sweep_steps, kinds, with_terms, batch_size, threads, lds, st, &se)) \
+      return fused_launch_status(what, se, st);
     CUROBO_FUSED_FOR_EACH_SHAPE(CUROBO_FUSED_TRY_SHAPE)
 #undef CUROBO_FUSED_TRY_SHAPE
   }
-#define CUROBO_FUSED_KINDS(DG, SW)                         \
-  do {                                                     \
-    if (kinds == 2) CUROBO_FUSED_LAUNCH(DG, SW, 2);        \
-    else if (kinds == 3) CUROBO_FUSED_LAUNCH(DG, SW, 3);   \
-    else if (kinds == 7) CUROBO_FUSED_LAUNCH(DG, SW, 7);   \
-    else CUROBO_FUSED_LAUNCH(DG, SW, 1);                   \
-  } while (0)
-#define CUROBO_FUSED_SWEEP(DG)                             \
-  do {                                                     \
-    if (sweep_steps == 0) CUROBO_FUSED_KINDS(DG, 0);       \
-    else CUROBO_FUSED_KINDS(DG, 3);                        \
-  } while (0)
-  if (bspline_degree == 3) CUROBO_FUSED_SWEEP(3);
-  else if (bspline_degree == 4) CUROBO_FUSED_SWEEP(4);
-  else CUROBO_FUSED_SWEEP(5);
-#undef CUROBO_FUSED_SWEEP
-#undef CUROBO_FUSED_KINDS
-#undef CUROBO_FUSED_LAUNCH
-  return check_launch(what, st);
+  // the generic instantiations: one per B-spline degree, sweep and obstacle kinds, with and without the optional terms
+  void (*kfn)(const FusedTrajArgs) = nullptr;
+#define CUROBO_FUSED_KERNEL_OF(DG, SW, KD) \
+  if (bspline_degree == DG && sweep_steps == SW && (kinds ? kinds : 1) == KD) /* (no scene: the cuboid instantiation) */ \
+    kfn = with_terms ? rollout_trajectory_fused_kernel<DG, SW, KD, true> : rollout_trajectory_fused_kernel<DG, SW, KD, false>;
+#define CUROBO_FUSED_KINDS_OF(DG, SW) \
+  CUROBO_FUSED_KERNEL_OF(DG, SW, 1) CUROBO_FUSED_KERNEL_OF(DG, SW, 2) CUROBO_FUSED_KERNEL_OF(DG, SW, 3) CUROBO_FUSED_KERNEL_OF(DG, SW, 7)
+  CUROBO_FUSED_KINDS_OF(3, 0) CUROBO_FUSED_KINDS_OF(3, 3) CUROBO_FUSED_KINDS_OF(4, 0) CUROBO_FUSED_KINDS_OF(4, 3)
+  CUROBO_FUSED_KINDS_OF(5, 0) CUROBO_FUSED_KINDS_OF(5, 3)
+#undef CUROBO_FUSED_KINDS_OF
+#undef CUROBO_FUSED_KERNEL_OF
+  const hipError_t e = fused_launch(kfn, dim3((unsigned)batch_size), dim3(threads), lds, kFusedLdsUnasked, st, a);
+  static const bool dbg = getenv("CUROBO_HIP_FUSED_DEBUG") != nullptr;
+  if (dbg && e == hipSuccess) {
+    int nb = -1;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kfn, threads, lds);
+    fprintf(stderr, "[curobo_hip] fused: threads %d lds %zu -> %d workgroups/CU\n", threads, lds, nb);
+  }
+  return fused_launch_status(what, e, st);
 }
 
 __global__ void dispatch_ws_init_kernel(int32_t *ws, int B) {

@@ -21,8 +21,7 @@ int CUROBO_FUSED_CAT(fused_shape_launch_, CUROBO_FUSED_SHAPE_TU)(CUROBO_FUSED_SH
   if (deg == DG && sweep == SW && kinds == KD && terms == TM && (!(TM) || !SH::kPlain || fused_plain_terms(a))) {      \
     auto kfn = rollout_trajectory_fused_kernel<DG, SW, KD, TM, SH>;                                                    \
     if (batch <= 0) return 1; /* query only */                                                                         \
-    *err = lds > 64 * 1024 ? hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess; \
-    if (*err == hipSuccess) hipLaunchKernelGGL(kfn, dim3((unsigned)batch), dim3(threads), lds, st, a);                 \
+    *err = fused_launch(kfn, dim3((unsigned)batch), dim3(threads), lds, kFusedLdsUnasked, st, a);                      \
     return 1;                                                                                                          \
   }
   CUROBO_FUSED_CAT3(CUROBO_FUSED_SHAPE_, CUROBO_FUSED_SHAPE_TU, _KERNELS)(CUROBO_FUSED_SHAPE_KERNEL)

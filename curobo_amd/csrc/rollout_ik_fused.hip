@@ -52,18 +52,7 @@ __global__ void __launch_bounds__(256, 4) rollout_ik_fused_kernel(const FusedIkA
   const bool live = h < npts;
   const int n = pt0 + h;
   // ---- FK
-  if (live) {
-    point_fk_locals(c, h, lane);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    float *const cm[1] = {c.cumul + (size_t)h * L * 12};
-    const float *const lc[1] = {c.work + (size_t)h * c.ws};
-    fk_chain_16_multi<1>(cm, lc, c.parent, c.fixed, L, lane);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (int s = lane; s < S; s += kFkLanes) point_sphere(c, a, blockIdx.x, h, s);
-    if (lane == 0) reinterpret_cast<float4 *>(c.work + (size_t)h * c.ws)[S] = make_float4(0.f, 0.f, 0.f, __builtin_nanf(""));
-  }
+  if (live) point_fk_row(c, a, blockIdx.x, h, lane);
   __syncthreads();  // derived tables (other waves) + this row's spheres
   if (!live) return;
 
@@ -72,45 +61,17 @@ __global__ void __launch_bounds__(256, 4) rollout_ik_fused_kernel(const FusedIkA
   float *wr = c.wrench + (size_t)h * c.wl;
   float cost_pt = 0.0f;
   bool any_grad = false;
-  if (a.use_self) {  // reference self_collision_kernel.cuh:19-111 (same loop as the trajectory kernel)
-    constexpr int U = 4;
-    const int P_pad = (P + 63) & ~63;
-    float best = 0.0f;
-    int best_k0 = 0x7fffffff;
-    for (int k0 = lane; k0 < P_pad; k0 += kFkLanes * U) {
-      uint32_t ij[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) ij[u] = c.pairs[k0 + u * kFkLanes];
-      float gmax = staged_pair_penetration(sph, ij[0]);
-#pragma unroll
-      for (int u = 1; u < U; u++) gmax = fmaxf(gmax, staged_pair_penetration(sph, ij[u]));
-      if (gmax > best) { best = gmax; best_k0 = k0; }
-    }
-    float m = row16_max(best);
-    if (m > 0.0f) {
-      int best_k = 0x7fffffff;
-      if (best == m) {
-        float f_best = 0.0f;
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-          const float f = staged_pair_penetration(sph, c.pairs[best_k0 + u * kFkLanes]);
-          if (f > f_best) { f_best = f; best_k = best_k0 + u * kFkLanes; }
-        }
-        best = f_best;
-      } else {
-        best = 0.0f;
-      }
-      m = row16_max(best);
-      const int kmin = row16_min((best == m && best > 0.0f) ? best_k : 0x7fffffff);
-      if (kmin != 0x7fffffff && m > 0.0f) {
-        any_grad = true;
-        if (lane == 0) cost_pt += self_pair_apply(c, h, m, kmin);
-      }
+  if (a.use_self) {
+    int kmin;
+    const float m = row_pair_argmax(c, sph, lane, kmin);
+    if (kmin != 0x7fffffff && m > 0.0f) {
+      any_grad = true;
+      if (lane == 0) cost_pt += self_pair_apply(c, h, m, kmin);
     }
   }
   if (a.use_scene) {
     point_link_masks<0, KINDS>(c, a.sc, h, lane);
-    for (int s0 = 0; s0 < S; s0 += kFkLanes) {
+    for (int s0 = 0; s0 < S; s0 += kFkLanes) {  // (a copy of the sphere-per-lane scene loop of the trajectory kernel's row fallback, fused_device.hpp)
       const int s = s0 + lane;
       float d = 0.0f;
       f3 g = make_f3(0.f, 0.f, 0.f);
@@ -177,28 +138,17 @@ CUROBO_EXPORT int curobo_hip_rollout_ik_fused(
     int link_chain_len, const int32_t *env_query_idx, int num_envs, int use_multi_env, curobo_hip_stream_t stream) {
   const char *what = "rollout_ik_fused";
   CUROBO_REQUIRE((!use_multi_env && num_envs <= 1) || env_query_idx, "%s: per-environment scenes / sphere sets need env_query_idx", what);
-  CUROBO_REQUIRE(num_links >= 1 && num_links <= 128 && dof >= 1 && dof <= 64, "%s: bad dimensions", what);
+  if (const int bad = fused_check_dimensions(what, num_links, num_spheres, link_chain_len, pair_locations)) return bad;
+  CUROBO_REQUIRE(dof >= 1 && dof <= 64, "%s: bad dimensions", what);
   CUROBO_REQUIRE(n_tool_frames >= 1 && num_goalset >= 1, "%s: need at least one tool frame / goal", what);
-  CUROBO_REQUIRE(link_chain_len >= 1, "%s: link_chain_len must be >= 1", what);
-  CUROBO_REQUIRE(num_spheres < 4096, "%s: at most 4095 spheres", what);
-  CUROBO_REQUIRE(((uintptr_t)pair_locations & 3) == 0, "%s: pair_locations must be 4-byte aligned", what);
   if (batch_size == 0) return CUROBO_HIP_OK;
   FusedIkArgs ia{};
   FusedTrajArgs &a = ia.r;
   a.out_cost = out_cost; a.out_spheres = out_robot_spheres;
-  a.bs.dof = dof;
-  a.fixed_transform = fixed_transform; a.robot_spheres = robot_spheres; a.joint_offset = joint_offset_map;
-  a.joint_map_type = joint_map_type; a.joint_map = joint_map; a.link_map = link_map; a.link_sphere_map = link_sphere_map;
-  a.link_chain_data = link_chain_data; a.link_chain_offsets = link_chain_offsets;
-  a.sphere_padding = sphere_padding; a.w_self = self_collision_weight; a.pairs = pair_locations;
-  a.use_self = (pair_locations && self_collision_weight && num_collision_pairs > 0) ? 1 : 0;
-  a.use_scene = (scene && scene_collision_weight) ? 1 : 0;
-  if (scene) a.sc = *scene;
-  if (!a.use_scene) { a.sc.max_cuboids = 0; a.sc.max_voxel_grids = 0; }
-  a.w_scene = scene_collision_weight; a.eta = activation_distance;
-  a.batch = batch_size; a.nlinks = num_links; a.nspheres = num_spheres; a.npairs = a.use_self ? num_collision_pairs : 0;
-  a.chain_len = link_chain_len; a.num_envs = num_envs > 1 ? num_envs : 1; a.use_multi_env = use_multi_env ? 1 : 0;
-  a.env_query_idx = env_query_idx;
+  fused_fill_robot_args(a, true, fixed_transform, robot_spheres, joint_map_type, joint_map, link_map, link_sphere_map, link_chain_data,
+                        link_chain_offsets, joint_offset_map, sphere_padding, self_collision_weight, pair_locations, scene,
+                        scene_collision_weight, activation_distance, env_query_idx, num_envs, use_multi_env, batch_size, dof, num_links,
+                        num_spheres, num_collision_pairs, link_chain_len);
   ia.x = q; ia.out_grad_q = out_grad_q; ia.tool_frame_map = tool_frame_map; ia.n_tool_frames = n_tool_frames;
   ia.n_points = batch_size; ia.out_link_pos = out_link_pos; ia.out_link_quat = out_link_quat;
   ToolPoseArgs &tp = ia.tp;
@@ -218,21 +168,8 @@ CUROBO_EXPORT int curobo_hip_rollout_ik_fused(
   const FusedLayout lay = fused_layout(kIkPoints, dof, num_links, num_spheres, link_chain_len, a.npairs, n_rec, 0, 0, 1, 0, false);
   const size_t lds = (size_t)lay.total * sizeof(float);
   CUROBO_REQUIRE(lds <= 160 * 1024, "%s: 16 configurations do not fit in LDS (%zu bytes); use the unfused kernels", what, lds);
-  const int kinds = (a.sc.max_cuboids > 0 && a.sc.cuboid_has_primitives) ? 7 : ((a.sc.max_cuboids > 0 ? 1 : 0) | (a.sc.max_voxel_grids > 0 ? 2 : 0));
+  const int kinds = fused_scene_kinds(a.sc);
   const dim3 grid((unsigned)ceil_div(batch_size, kIkPoints)), block(kIkPoints * kFkLanes);
-#define CUROBO_IK_LAUNCH(KD)                                                                                    \
-  do {                                                                                                          \
-    auto kfn = rollout_ik_fused_kernel<KD>;                                                                     \
-    if (lds > 64 * 1024) {                                                                                      \
-      hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      if (e != hipSuccess) return set_error(CUROBO_HIP_ERR_LAUNCH, "%s: cannot raise LDS limit: %s", what, hipGetErrorString(e)); \
-    }                                                                                                           \
-    hipLaunchKernelGGL(kfn, grid, block, lds, st, ia);                                                          \
-  } while (0)
-  if (kinds == 2) CUROBO_IK_LAUNCH(2);
-  else if (kinds == 3) CUROBO_IK_LAUNCH(3);
-  else if (kinds == 7) CUROBO_IK_LAUNCH(7);
-  else CUROBO_IK_LAUNCH(1);
-#undef CUROBO_IK_LAUNCH
-  return check_launch(what, st);
+  const auto kfn = kinds == 2 ? rollout_ik_fused_kernel<2> : kinds == 3 ? rollout_ik_fused_kernel<3> : kinds == 7 ? rollout_ik_fused_kernel<7> : rollout_ik_fused_kernel<1>;
+  return fused_launch_status(what, fused_launch(kfn, grid, block, lds, kFusedLdsUnasked, st, ia), st);
 }
