@@ -127,6 +127,29 @@ def launch_lbfgs_iteration_tail(
     ))
 
 
+#: forms of the one-launch tail (``tail_form``)
+TAIL_PLAIN, TAIL_ROW, TAIL_WAVE, TAIL_WORKGROUP = 0, 1, 2, 3
+
+
+def tail_shape_id(opt_dim: int, history: int, n_linesearch: int, action_dim: int) -> int:
+    """Id (>= 1) of the compile-time shape of the one-launch tail with exactly these dimensions, 0 = none (the launch
+    then reads them from its arguments; csrc/tail_shapes.hpp).  Host-side query, no GPU work."""
+    return int(load().curobo_hip_lbfgs_tail_shape_id(int(opt_dim), int(history), int(n_linesearch), int(action_dim)))
+
+
+def set_tail_shapes_enabled(enabled: bool) -> None:
+    """False: every ``launch_lbfgs_iteration_tail`` takes the run-time kernels (tests, A/B timing)."""
+    check(load().curobo_hip_lbfgs_set_tail_shapes_enabled(1 if enabled else 0))
+
+
+def tail_form(opt_dim: int, history: int, n_linesearch: int, action_dim: int, batchsize: int, overlapped: bool = False):
+    """``(form, shape)`` that ``launch_lbfgs_iteration_tail`` runs for these arguments: one of ``TAIL_PLAIN`` /
+    ``TAIL_ROW`` / ``TAIL_WAVE`` / ``TAIL_WORKGROUP`` and the compile-time shape taken (0 = run-time dimensions)."""
+    code = int(load().curobo_hip_lbfgs_tail_form(int(opt_dim), int(history), int(n_linesearch), int(action_dim),
+                                                 int(batchsize), int(overlapped)))
+    return code & 15, code >> 4
+
+
 def mppi_update_distribution(
     new_mean, new_cov, new_scale_tril, best_traj, weights, costs, gamma_seq, actions, mean, cov,
     beta: float, step_size_mean: float, step_size_cov: float, kappa: float,

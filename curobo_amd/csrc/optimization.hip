@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "tail_shapes.hpp"
 
 namespace curobo_hip {
 
@@ -166,16 +167,55 @@ __device__ __forceinline__ unsigned long long gballot(bool p) {
 
 // The (y, s, rho) history of one problem plus its previous iterate, as one lane group holds it in VGPRs
 // (separate arrays, not a struct: a struct this size stays an alloca and lands in scratch).
-template <int G>
+// S = a TailShape (tail_shapes.hpp) sizes the arrays for exactly its m slots, TailShapeDyn for the largest history.
+template <int G, class S = TailShapeDyn>
 struct LbfgsLimits {
-  static constexpr int MMAX = G == kWave ? 32 : 16;
+  static constexpr int MMAX = S::kStatic ? (S::kM > 0 ? S::kM : 1) : (G == kWave ? 32 : 16);
 };
-#define LBFGS_HISTORY_DECL(VPL, G) \
-  float h_ys[LbfgsLimits<G>::MMAX][VPL], h_ss[LbfgsLimits<G>::MMAX][VPL], h_g0[VPL], h_x0[VPL], h_rho
-#define LBFGS_HISTORY_PARAMS(VPL, G)                                                                             \
-  float (&h_ys)[LbfgsLimits<G>::MMAX][VPL], float (&h_ss)[LbfgsLimits<G>::MMAX][VPL], float (&h_g0)[VPL], \
+#define LBFGS_HISTORY_DECL(VPL, G, S) \
+  float h_ys[LbfgsLimits<G, S>::MMAX][VPL], h_ss[LbfgsLimits<G, S>::MMAX][VPL], h_g0[VPL], h_x0[VPL], h_rho
+#define LBFGS_HISTORY_PARAMS(VPL, G, S)                                                                          \
+  float (&h_ys)[LbfgsLimits<G, S>::MMAX][VPL], float (&h_ss)[LbfgsLimits<G, S>::MMAX][VPL], float (&h_g0)[VPL], \
       float (&h_x0)[VPL], float &h_rho
 #define LBFGS_HISTORY_ARGS h_ys, h_ss, h_g0, h_x0, h_rho
+
+// Row addressing.  A row of a [.][B][V] array is named by a wave-uniform 64-bit base (array + slot * B V, + b V where the
+// problem index is wave-uniform: the 64-lane forms) and a per-lane byte offset that is computed once per element of the
+// lane, not once per row: OFF = uint32_t makes every access `global_load_dword v, v_off, s[base:base+1]` (one scalar add
+// per row instead of a 64-bit multiply-add and shifts per lane and row).  In the 16-lane row form the problem differs per
+// row of lanes and goes into the lane offset: the host takes uint32_t there only when the largest offset fits 31 bits
+// (tail_offsets_fit).  OFF = size_t is the 64-bit per-lane address of the three-launch kernels.
+template <typename T, typename OFF>
+__device__ __forceinline__ T &row_at(T *row, OFF off_bytes) {
+  return *(T *)((const char *)row + off_bytes);
+}
+// The scalar-base form is matched per basic block: base + zext(offset) has to be formed in the block of the access, and
+// the zext of an offset computed in a dominating block is hoisted there (the access then pays a 64-bit VALU add).  A
+// block of several accesses therefore takes an opaque copy of its lane offset first: one v_mov for the block.
+template <typename OFF>
+__device__ __forceinline__ OFF block_offset(OFF off) {
+  if constexpr (sizeof(OFF) == 4) asm volatile("" : "+v"(off));
+  return off;
+}
+// A wave-uniform zero the optimiser cannot see through: row bases formed from `array + fresh_zero()` are computed where
+// they are used.  Without it the write-back of the history reuses the ~4 m row bases of the loads, which then stay live
+// across the whole recursion: more SGPRs than a wavefront has, spilled to VGPR lanes (a v_writelane and a v_readlane
+// each, against two scalar adds).  (An integer, not the pointer: a pointer through asm comes back as a flat address.)
+__device__ __forceinline__ size_t fresh_zero() {
+  int z = 0;
+  asm volatile("" : "+s"(z));
+  return (size_t)(unsigned)z;
+}
+template <int G>
+__device__ __forceinline__ int uniform_part(int b) { return G == kWave ? b : 0; }
+template <int G, typename OFF>
+__device__ __forceinline__ OFF lane_part(int b) { return G == kWave ? (OFF)0 : (OFF)b; }
+// byte offset of element min(lane + e G, V - 1) of the [row_len]-float row of problem b
+template <int G, typename OFF>
+__device__ __forceinline__ OFF lane_offset(int b, int lane, int e, int V, int row_len) {
+  const int v = lane + e * G, vc = v < V ? v : V - 1;
+  return (lane_part<G, OFF>(b) * (OFF)row_len + (OFF)vc) * (OFF)sizeof(float);
+}
 
 // v & mask with a mask the optimiser cannot see through.  Out-of-range lanes load from a clamped address and
 // are zeroed with this: written as `in_range ? load : 0` the compiler moves each load under its own branch
@@ -191,32 +231,42 @@ __device__ __forceinline__ float and_mask(float v, int mk) {
 }
 
 // slot i <- old slot i+1 (the shift of the reference), every load independent of every other
-template <int VPL, int G>
-__device__ __forceinline__ void lbfgs_history_load(const LbfgsArgs &a, int b, int lane, LBFGS_HISTORY_PARAMS(VPL, G)) {
-  constexpr int MMAX = LbfgsLimits<G>::MMAX;
-  const int V = a.v_dim, m = a.m, B = a.batch;
-  const size_t bv = (size_t)b * V;
+template <int VPL, int G, class S, typename OFF>
+__device__ __forceinline__ void lbfgs_history_load(const LbfgsArgs &a, int b, int lane, LBFGS_HISTORY_PARAMS(VPL, G, S)) {
+  constexpr int MMAX = LbfgsLimits<G, S>::MMAX;
+  const int V = S::kStatic ? S::kV : a.v_dim, m = S::kStatic ? S::kM : a.m, B = a.batch;
+  const size_t bv = (size_t)uniform_part<G>(b) * V;
   const size_t hist_stride = (size_t)B * V;
   // Unconditional loads at clamped addresses: lanes past V are zeroed with the opaque mask; slots >= m-1 receive
   // a copy of the newest old slot, which nothing reads (slot m-1 is overwritten by the append, the recursion
   // stops at m).
   int mk[VPL];
+  OFF off[VPL];
 #pragma unroll
   for (int e = 0; e < VPL; e++) {
-    const int v = lane + e * G, vc = v < V ? v : V - 1;
-    mk[e] = opaque_lane_mask(v < V);
-    h_g0[e] = and_mask(a.grad_0[bv + vc], mk[e]);
-    h_x0[e] = and_mask(a.x_0[bv + vc], mk[e]);
+    mk[e] = opaque_lane_mask(lane + e * G < V);
+    off[e] = lane_offset<G, OFF>(b, lane, e, V, V);
+    h_g0[e] = and_mask(row_at(a.grad_0 + bv, off[e]), mk[e]);
+    h_x0[e] = and_mask(row_at(a.x_0 + bv, off[e]), mk[e]);
   }
   if (m > 0) {
+    if (!S::kStatic) {  // (a block of its own only where m is a run-time value)
+#pragma unroll
+      for (int e = 0; e < VPL; e++) off[e] = block_offset(off[e]);
+    }
 #pragma unroll
     for (int i = MMAX - 1; i >= 0; i--) {  // newest first: the order the recursion consumes them in
+      if (S::kStatic && i >= m - 1) {  // (a shape knows which slots nothing reads)
+#pragma unroll
+        for (int e = 0; e < VPL; e++) h_ys[i][e] = h_ss[i][e] = 0.0f;
+        continue;
+      }
       const int slot = i + 1 < m ? i + 1 : m - 1;
+      const float *yrow = a.y_buffer + (size_t)slot * hist_stride + bv, *srow = a.s_buffer + (size_t)slot * hist_stride + bv;
 #pragma unroll
       for (int e = 0; e < VPL; e++) {
-        const int v = lane + e * G, vc = v < V ? v : V - 1;
-        h_ys[i][e] = and_mask(a.y_buffer[(size_t)slot * hist_stride + bv + vc], mk[e]);
-        h_ss[i][e] = and_mask(a.s_buffer[(size_t)slot * hist_stride + bv + vc], mk[e]);
+        h_ys[i][e] = and_mask(row_at(yrow, off[e]), mk[e]);
+        h_ss[i][e] = and_mask(row_at(srow, off[e]), mk[e]);
       }
     }
     const int rl = lane + 1 < m ? lane + 1 : m - 1;
@@ -233,14 +283,17 @@ __device__ __forceinline__ void lbfgs_history_load(const LbfgsArgs &a, int b, in
 
 // body for one problem b on one lane group; g_in / x_in = current gradient / iterate of the lane's
 // elements (v = lane + e * G), dir_out = the new step direction (also stored to a.step_vec)
-template <int VPL, int G, bool STORE_SHIFTED>
+template <int VPL, int G, bool STORE_SHIFTED, class S, typename OFF>
 __device__ __forceinline__ void lbfgs_step_from_history(const LbfgsArgs &a, int b, int lane, const float (&g_in)[VPL],
-                                                        const float (&x_in)[VPL], LBFGS_HISTORY_PARAMS(VPL, G),
+                                                        const float (&x_in)[VPL], LBFGS_HISTORY_PARAMS(VPL, G, S),
                                                         float (&dir_out)[VPL]) {
-  constexpr int MMAX = LbfgsLimits<G>::MMAX;
-  const int V = a.v_dim, m = a.m, B = a.batch;
-  const size_t bv = (size_t)b * V;
+  constexpr int MMAX = LbfgsLimits<G, S>::MMAX;
+  const int V = S::kStatic ? S::kV : a.v_dim, m = S::kStatic ? S::kM : a.m, B = a.batch;
+  const size_t bv = (size_t)uniform_part<G>(b) * V;
   const size_t hist_stride = (size_t)B * V;
+  OFF off[VPL];  // (lanes past V hold a clamped offset and store nothing)
+#pragma unroll
+  for (int e = 0; e < VPL; e++) off[e] = lane_offset<G, OFF>(b, lane, e, V, V);
   float (&ys)[MMAX][VPL] = h_ys;
   float (&ss)[MMAX][VPL] = h_ss;
   float rho_mine = h_rho;
@@ -254,8 +307,9 @@ __device__ __forceinline__ void lbfgs_step_from_history(const LbfgsArgs &a, int 
       const float g = g_in[e], x = x_in[e];
       y[e] = g - h_g0[e];
       s[e] = x - h_x0[e];
-      a.grad_0[bv + v] = g;
-      a.x_0[bv + v] = x;
+      const OFF o = block_offset(off[e]);
+      row_at(a.grad_0 + bv, o) = g;
+      row_at(a.x_0 + bv, o) = x;
       gq[e] = g;
       part = __builtin_fmaf(y[e], s[e], part);
     }
@@ -313,19 +367,28 @@ __device__ __forceinline__ void lbfgs_step_from_history(const LbfgsArgs &a, int 
   for (int e = 0; e < VPL; e++) {
     const int v = lane + e * G;
     dir_out[e] = -gq[e];
-    if (v < V) a.step_vec[bv + v] = -gq[e];
+    if (v < V) row_at(a.step_vec + bv, off[e]) = -gq[e];
   }
   // the shifted history goes back to memory last: 4 m stores per lane that nothing in this launch waits for
   // (!STORE_SHIFTED: only the appended pair, somebody else moves the rest)
+  const size_t bv_late = sizeof(OFF) == 4 ? bv + fresh_zero() : bv;
+  float *const y0 = a.y_buffer + bv_late, *const s0 = a.s_buffer + bv_late;
 #pragma unroll
-  for (int i = 0; i < MMAX; i++) {
-    if (i < m && (STORE_SHIFTED || i == m - 1)) {
+  for (int e = 0; e < VPL; e++) {
+    if (lane + e * G < V) {
+      const OFF o = block_offset(off[e]);
+      if (!STORE_SHIFTED) {  // (the pair itself, not ys[m - 1]: a dynamic index would take the history out of registers)
+        if (m > 0) {
+          row_at(y0 + (size_t)(m - 1) * hist_stride, o) = y[e];
+          row_at(s0 + (size_t)(m - 1) * hist_stride, o) = s[e];
+        }
+        continue;
+      }
 #pragma unroll
-      for (int e = 0; e < VPL; e++) {
-        const int v = lane + e * G;
-        if (v < V) {
-          a.y_buffer[(size_t)i * hist_stride + bv + v] = ys[i][e];
-          a.s_buffer[(size_t)i * hist_stride + bv + v] = ss[i][e];
+      for (int i = 0; i < MMAX; i++) {
+        if (i < m) {
+          row_at(y0 + (size_t)i * hist_stride, o) = ys[i][e];
+          row_at(s0 + (size_t)i * hist_stride, o) = ss[i][e];
         }
       }
     }
@@ -335,9 +398,9 @@ __device__ __forceinline__ void lbfgs_step_from_history(const LbfgsArgs &a, int 
 template <int VPL, int G = kWave>
 __device__ __forceinline__ void lbfgs_step_reg_body(const LbfgsArgs &a, int b, int lane, const float (&g_in)[VPL],
                                                     const float (&x_in)[VPL], float (&dir_out)[VPL]) {
-  LBFGS_HISTORY_DECL(VPL, G);
-  lbfgs_history_load<VPL, G>(a, b, lane, LBFGS_HISTORY_ARGS);
-  lbfgs_step_from_history<VPL, G, true>(a, b, lane, g_in, x_in, LBFGS_HISTORY_ARGS, dir_out);
+  LBFGS_HISTORY_DECL(VPL, G, TailShapeDyn);
+  lbfgs_history_load<VPL, G, TailShapeDyn, size_t>(a, b, lane, LBFGS_HISTORY_ARGS);
+  lbfgs_step_from_history<VPL, G, true, TailShapeDyn, size_t>(a, b, lane, g_in, x_in, LBFGS_HISTORY_ARGS, dir_out);
 }
 
 template <int VPL>
@@ -471,6 +534,17 @@ __global__ void __launch_bounds__(256) trajectory_cost_sum_kernel(float *out, co
   if (tid == 0) out[b] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
 }
 
+// a / b as the library's fp32 division is built (-fno-hip-fp32-correctly-rounded-divide-sqrt: frexp both operands, v_rcp_f32
+// of the divisor's mantissa, one multiply, ldexp), spelled out.  The `/` operator gets that sequence only while the
+// optimiser carries its 2.5 ulp marking along: in the one-element instantiations of the one-launch tail the quotient
+// |d_v| / step_max lost it and ran the IEEE sequence (v_div_scale / v_div_fmas / v_div_fixup), so their step scale differed
+// in the last bit from the two-element instantiations and from prepare_search_points_kernel (and d / scale likewise in the
+// one-element plain kernel).  Same bits as `/` wherever the marking survives.  Used for the step scale in all three places.
+__device__ __forceinline__ float div_frexp_rcp(float a, float b) {
+  const float q = __builtin_amdgcn_frexp_mantf(a) * __builtin_amdgcn_rcpf(__builtin_amdgcn_frexp_mantf(b));
+  return __builtin_amdgcn_ldexpf(q, __builtin_amdgcn_frexp_expf(a) - __builtin_amdgcn_frexp_expf(b));
+}
+
 // ------------------------------------------------------------------------------------------
 // Line-search candidate generation, fused (reference optim/gradient/line_search_strategy.py:
 // 134-204 `_prepare_search_points` = scale_action (:301-325) + jit_get_x_set (:281-299), three to
@@ -487,13 +561,13 @@ __global__ void __launch_bounds__(256) prepare_search_points_kernel(
   float scale = 1.0f;
   if (apply_scale) {
     float mx = 0.0f;
-    for (int v = lane; v < opt_dim; v += kWave) mx = fmaxf(mx, fabsf(d[o + v]) / step_max[v % action_dim]);
+    for (int v = lane; v < opt_dim; v += kWave) mx = fmaxf(mx, div_frexp_rcp(fabsf(d[o + v]), step_max[v % action_dim]));
 #pragma unroll
     for (int off = kWave / 2; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, kWave));
     scale = fmaxf(mx, 1.0f);
   }
   for (int v = lane; v < opt_dim; v += kWave) {
-    const float dv = d[o + v] / scale;
+    const float dv = div_frexp_rcp(d[o + v], scale);
     const float xv = x[o + v];
     d_out[o + v] = dv;
     for (int k = 0; k < nls; k++) x_set[((size_t)b * nls + k) * opt_dim + v] = __builtin_fmaf(alphas[k], dv, xv);
@@ -536,7 +610,7 @@ __global__ void __launch_bounds__(256) lbfgs_iteration_tail_kernel(const LineSea
 #pragma unroll
     for (int e = 0; e < VPL; e++) {
       const int v = lane + e * G;
-      if (v < V) mx = fmaxf(mx, fabsf(dir[e]) / pr.step_max[v % pr.action_dim]);
+      if (v < V) mx = fmaxf(mx, div_frexp_rcp(fabsf(dir[e]), pr.step_max[v % pr.action_dim]));
     }
 #pragma unroll
     for (int off = G / 2; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, G));
@@ -546,7 +620,7 @@ __global__ void __launch_bounds__(256) lbfgs_iteration_tail_kernel(const LineSea
   for (int e = 0; e < VPL; e++) {
     const int v = lane + e * G;
     if (v < V) {
-      const float dv = dir[e] / scale;
+      const float dv = div_frexp_rcp(dir[e], scale);
       pr.d_out[(size_t)b * V + v] = dv;
       for (int k = 0; k < NLS; k++) pr.x_set[((size_t)b * NLS + k) * V + v] = __builtin_fmaf(pr.alphas[k], dv, x[e]);
     }
@@ -583,14 +657,15 @@ __device__ __forceinline__ void touch_kernarg_lines() {
       float &t_mag, float &t_bc, int &t_cur, int &t_bi
 #define TAIL_INPUTS_ARGS t_sg, t_sa, t_dir, t_smax, t_cost, t_mag, t_bc, t_cur, t_bi
 
-template <int VPL, int G, int NLSMAX>
+template <int VPL, int G, int NLSMAX, class S, typename OFF>
 __device__ __forceinline__ void tail_inputs_load(const LineSearchArgs &ls, const PrepareArgs &pr, int b, int lane,
                                                  TAIL_INPUTS_PARAMS(VPL, NLSMAX)) {
-  const int V = ls.opt_dim, NLS = ls.n_linesearch;
-  const size_t o = (size_t)b * V;
+  const int V = S::kStatic ? S::kV : ls.opt_dim, NLS = S::kStatic ? S::kNLS : ls.n_linesearch;
+  const int action_dim = S::kStatic ? S::kAD : pr.action_dim;
+  const size_t o = (size_t)uniform_part<G>(b) * V, oc = (size_t)uniform_part<G>(b) * NLS;
   const int ln = lane < NLS ? lane : NLS - 1;
   const int lane_is_cand = opaque_lane_mask(lane < NLS);
-  t_cost = and_mask(ls.search_cost[(size_t)b * NLS + ln], lane_is_cand);
+  t_cost = and_mask(row_at(ls.search_cost + oc, (lane_part<G, OFF>(b) * (OFF)NLS + (OFF)ln) * (OFF)sizeof(float)), lane_is_cand);
   t_mag = and_mask(ls.search_magnitudes[ln], lane_is_cand);
   t_bc = ls.best_cost[b];
   t_cur = (int)ls.current_iteration[b] + 1;
@@ -601,23 +676,24 @@ __device__ __forceinline__ void tail_inputs_load(const LineSearchArgs &ls, const
   for (int e = 0; e < VPL; e++) {
     const int v = lane + e * G, vc = v < V ? v : V - 1;
     const int mk = opaque_lane_mask(v < V);
-    t_dir[e] = and_mask(ls.step_direction[o + vc], mk);
+    t_dir[e] = and_mask(row_at(ls.step_direction + o, lane_offset<G, OFF>(b, lane, e, V, V)), mk);
+    const OFF off = lane_offset<G, OFF>(b, lane, e, V, NLS * V);  // candidate rows: [B][NLS][V]
 #pragma unroll
     for (int k = 0; k < NLSMAX; k++) {
       const int kc = k < NLS ? k : NLS - 1;
-      t_sg[k][e] = and_mask(ls.search_gradient[((size_t)b * NLS + kc) * V + vc], mk);
-      t_sa[k][e] = and_mask(ls.search_action[((size_t)b * NLS + kc) * V + vc], mk);
+      t_sg[k][e] = and_mask(row_at(ls.search_gradient + (oc + kc) * V, off), mk);
+      t_sa[k][e] = and_mask(row_at(ls.search_action + (oc + kc) * V, off), mk);
     }
-    t_smax[e] = pr.step_max[vc % pr.action_dim];
+    t_smax[e] = pr.step_max[vc % action_dim];
   }
 }
 
 // line_search_body from registers; g / x = gradient / iterate of the exploration candidate
-template <int VPL, int G, int NLSMAX>
+template <int VPL, int G, int NLSMAX, class S, typename OFF>
 __device__ __forceinline__ void tail_line_search(const LineSearchArgs &ls, int b, int lane, TAIL_INPUTS_PARAMS(VPL, NLSMAX),
                                                  float (&g)[VPL], float (&x)[VPL]) {
-  const int V = ls.opt_dim, NLS = ls.n_linesearch;
-  const size_t o = (size_t)b * V;
+  const int V = S::kStatic ? S::kV : ls.opt_dim, NLS = S::kStatic ? S::kNLS : ls.n_linesearch;
+  const size_t o = (size_t)uniform_part<G>(b) * V;
   float gd_mine = 0.0f, gd0 = 0.0f;
 #pragma unroll
   for (int k = 0; k < NLSMAX; k++) {
@@ -670,32 +746,35 @@ __device__ __forceinline__ void tail_line_search(const LineSearchArgs &ls, int b
       if (k == sel) { gs = t_sg[k][e]; xs = t_sa[k][e]; }
     }
     if (v < V) {
-      ls.exploration_action[o + v] = x[e];
-      ls.exploration_gradient[o + v] = g[e];
-      ls.selected_action[o + v] = xs;
-      ls.selected_gradient[o + v] = gs;
-      if (update_best) ls.best_action[o + v] = xs;
+      const OFF off = block_offset(lane_offset<G, OFF>(b, lane, e, V, V));
+      row_at(ls.exploration_action + o, off) = x[e];
+      row_at(ls.exploration_gradient + o, off) = g[e];
+      row_at(ls.selected_action + o, off) = xs;
+      row_at(ls.selected_gradient + o, off) = gs;
+      if (update_best) row_at(ls.best_action + o, off) = xs;
     }
   }
   if (lane < NLS) {
-    ls.exploration_idx[(size_t)b * NLS + lane] = expl;
-    ls.selected_idx[(size_t)b * NLS + lane] = sel;
+    const size_t oc = (size_t)uniform_part<G>(b) * NLS;
+    const OFF off = (lane_part<G, OFF>(b) * (OFF)NLS + (OFF)lane) * (OFF)sizeof(int32_t);
+    row_at(ls.exploration_idx + oc, off) = expl;
+    row_at(ls.selected_idx + oc, off) = sel;
   }
 }
 
 // prepare_search_points_kernel from registers
-template <int VPL, int G, int NLSMAX>
+template <int VPL, int G, int NLSMAX, typename OFF>
 __device__ __forceinline__ void tail_next_candidates(const PrepareArgs &pr, int b, int lane, int V, int NLS,
                                                      const float (&x)[VPL], const float (&dir)[VPL],
                                                      const float (&smax)[VPL], float mag_mine) {
-  const size_t o = (size_t)b * V;
+  const size_t o = (size_t)uniform_part<G>(b) * V, oc = (size_t)uniform_part<G>(b) * NLS;
   float scale = 1.0f;
   if (pr.apply_scale) {
     float mx = 0.0f;
 #pragma unroll
     for (int e = 0; e < VPL; e++) {
       const int v = lane + e * G;
-      if (v < V) mx = fmaxf(mx, fabsf(dir[e]) / smax[e]);
+      if (v < V) mx = fmaxf(mx, div_frexp_rcp(fabsf(dir[e]), smax[e]));
     }
 #pragma unroll
     for (int off = G / 2; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, G));
@@ -704,12 +783,16 @@ __device__ __forceinline__ void tail_next_candidates(const PrepareArgs &pr, int 
 #pragma unroll
   for (int e = 0; e < VPL; e++) {
     const int v = lane + e * G;
-    const float dv = dir[e] / scale;
-    if (v < V) pr.d_out[o + v] = dv;
+    const float dv = div_frexp_rcp(dir[e], scale);
+    float xk[NLSMAX];
 #pragma unroll
-    for (int k = 0; k < NLSMAX; k++) {
-      const float ak = gbcast<G>(mag_mine, k);
-      if (k < NLS && v < V) pr.x_set[((size_t)b * NLS + k) * V + v] = __builtin_fmaf(ak, dv, x[e]);
+    for (int k = 0; k < NLSMAX; k++) xk[k] = __builtin_fmaf(gbcast<G>(mag_mine, k), dv, x[e]);
+    if (v < V) {
+      row_at(pr.d_out + o, lane_offset<G, OFF>(b, lane, e, V, V)) = dv;
+      const OFF off = block_offset(lane_offset<G, OFF>(b, lane, e, V, NLS * V));
+#pragma unroll
+      for (int k = 0; k < NLSMAX; k++)
+        if (k < NLS) row_at(pr.x_set + (oc + k) * V, off) = xk[k];
     }
   }
 }
@@ -721,23 +804,28 @@ __device__ __forceinline__ void tail_raise_priority() {
   __builtin_amdgcn_s_setprio(3);
 }
 
-// (a) one lane group per problem: everything in one burst of loads.  Used for the 16-lane-row problems (IK).
-template <int VPL, int G, int NLSMAX>
+// (a) one lane group per problem: everything in one burst of loads.  Used for the 16-lane-row problems (IK) and, one
+// wavefront per problem, between the rollouts of other seed shards.  S: a compile-time shape (tail_shapes.hpp) or the
+// run-time dimensions of the arguments; row offsets are 32-bit (the host checks tail_offsets_fit for the row form).
+template <int VPL, int G, int NLSMAX, class S = TailShapeDyn>
 __global__ void __launch_bounds__(256) lbfgs_iteration_tail_prefetch_kernel(const LineSearchArgs ls, const LbfgsArgs lb,
                                                                             const PrepareArgs pr) {
+  typedef uint32_t OFF;
   tail_raise_priority();
   touch_kernarg_lines();
   const int grp = threadIdx.x / G, lane = threadIdx.x % G;
-  const int b = blockIdx.x * (blockDim.x / G) + grp;
+  int b = blockIdx.x * (blockDim.x / G) + grp;
+  if (G == kWave) b = __builtin_amdgcn_readfirstlane(b);  // one problem per wavefront: its row bases live in SGPRs
   if (b >= ls.batch) return;
+  const int V = S::kStatic ? S::kV : ls.opt_dim, NLS = S::kStatic ? S::kNLS : ls.n_linesearch;
   TAIL_INPUTS_DECL(VPL, NLSMAX);
-  tail_inputs_load<VPL, G, NLSMAX>(ls, pr, b, lane, TAIL_INPUTS_ARGS);
-  LBFGS_HISTORY_DECL(VPL, G);
-  lbfgs_history_load<VPL, G>(lb, b, lane, LBFGS_HISTORY_ARGS);
+  tail_inputs_load<VPL, G, NLSMAX, S, OFF>(ls, pr, b, lane, TAIL_INPUTS_ARGS);
+  LBFGS_HISTORY_DECL(VPL, G, S);
+  lbfgs_history_load<VPL, G, S, OFF>(lb, b, lane, LBFGS_HISTORY_ARGS);
   float g[VPL], x[VPL], dir[VPL];
-  tail_line_search<VPL, G, NLSMAX>(ls, b, lane, TAIL_INPUTS_ARGS, g, x);
-  lbfgs_step_from_history<VPL, G, true>(lb, b, lane, g, x, LBFGS_HISTORY_ARGS, dir);
-  tail_next_candidates<VPL, G, NLSMAX>(pr, b, lane, ls.opt_dim, ls.n_linesearch, x, dir, t_smax, t_mag);
+  tail_line_search<VPL, G, NLSMAX, S, OFF>(ls, b, lane, TAIL_INPUTS_ARGS, g, x);
+  lbfgs_step_from_history<VPL, G, true, S, OFF>(lb, b, lane, g, x, LBFGS_HISTORY_ARGS, dir);
+  tail_next_candidates<VPL, G, NLSMAX, OFF>(pr, b, lane, V, NLS, x, dir, t_smax, t_mag);
 }
 
 // (b) one 256-lane workgroup per problem, for wavefront-sized problems (trajectory optimisation: V = 84, m = 27).
@@ -750,7 +838,7 @@ __global__ void __launch_bounds__(256) lbfgs_iteration_tail_prefetch_kernel(cons
 // 1..3 write the shifted history back from the registers they staged it through -- off the critical path.
 constexpr int kStageLanes = 192;
 constexpr int kHistRow = 36;
-template <int VPL, int NLSMAX, int RMAX>
+template <int VPL, int NLSMAX, int RMAX, class S = TailShapeDyn>
 __global__ void __launch_bounds__(256) lbfgs_iteration_tail_wg_kernel(const LineSearchArgs ls, const LbfgsArgs lb,
                                                                       const PrepareArgs pr) {
   // y then s, each [V + 1][kHistRow]: row v = the slots 0..m-2 (new numbering) of element v, so that the lane that
@@ -758,31 +846,34 @@ __global__ void __launch_bounds__(256) lbfgs_iteration_tail_wg_kernel(const Line
   // float4 reads of 16 consecutive lanes fall into distinct banks.
   extern __shared__ float s_hist[];
   constexpr int G = kWave;
-  const int s_off = (lb.v_dim + 1) * kHistRow;
+  constexpr int MMAX = LbfgsLimits<G, S>::MMAX;
+  typedef uint32_t OFF;  // (the host checks tail_offsets_fit: a staging lane's offset spans the slots it moves)
   tail_raise_priority();
   touch_kernarg_lines();
   const int b = blockIdx.x;
   const int tid = threadIdx.x, lane = tid % kWave;
-  const int V = lb.v_dim, m = lb.m;
+  const int V = S::kStatic ? S::kV : lb.v_dim, m = S::kStatic ? S::kM : lb.m;
+  const int s_off = (V + 1) * kHistRow;
   const int n = m > 0 ? (m - 1) * V : 0;  // floats per array that move
   const size_t hist_stride = (size_t)lb.batch * V;
+  const OFF hist_stride32 = (OFF)lb.batch * (OFF)V;
   float g[VPL], x[VPL];
   TAIL_INPUTS_DECL(VPL, NLSMAX);
-  LBFGS_HISTORY_DECL(VPL, G);
+  LBFGS_HISTORY_DECL(VPL, G, S);
   float stage_y[RMAX], stage_s[RMAX];
   if (tid < kWave) {
-    tail_inputs_load<VPL, G, NLSMAX>(ls, pr, b, lane, TAIL_INPUTS_ARGS);
+    tail_inputs_load<VPL, G, NLSMAX, S, OFF>(ls, pr, b, lane, TAIL_INPUTS_ARGS);
     int mk[VPL];
 #pragma unroll
     for (int e = 0; e < VPL; e++) {
-      const int v = lane + e * G, vc = v < V ? v : V - 1;
-      mk[e] = opaque_lane_mask(v < V);
-      h_g0[e] = and_mask(lb.grad_0[(size_t)b * V + vc], mk[e]);
-      h_x0[e] = and_mask(lb.x_0[(size_t)b * V + vc], mk[e]);
+      const OFF off = lane_offset<G, OFF>(b, lane, e, V, V);
+      mk[e] = opaque_lane_mask(lane + e * G < V);
+      h_g0[e] = and_mask(row_at(lb.grad_0 + (size_t)b * V, off), mk[e]);
+      h_x0[e] = and_mask(row_at(lb.x_0 + (size_t)b * V, off), mk[e]);
     }
     const int rl = lane + 1 < m ? lane + 1 : (m > 0 ? m - 1 : 0);
     h_rho = m > 0 ? and_mask(lb.rho_buffer[(size_t)rl * lb.batch + b], opaque_lane_mask(lane < m - 1)) : 0.0f;
-    tail_line_search<VPL, G, NLSMAX>(ls, b, lane, TAIL_INPUTS_ARGS, g, x);
+    tail_line_search<VPL, G, NLSMAX, S, OFF>(ls, b, lane, TAIL_INPUTS_ARGS, g, x);
   } else if (n > 0) {
     // element idx = i * V + v of the new numbering comes from old slot i + 1; idx advances by 192 per round:
     // (i, v) are stepped, not divided
@@ -796,8 +887,9 @@ __global__ void __launch_bounds__(256) lbfgs_iteration_tail_wg_kernel(const Line
       const int idx = t + r * kStageLanes;
       // past the end: re-read the last element (and re-write it below), no predication
       const int ic = idx < n ? i : m - 2, vc = idx < n ? v : V - 1;
-      stage_y[r] = ysrc[(size_t)ic * hist_stride + vc];
-      stage_s[r] = ssrc[(size_t)ic * hist_stride + vc];
+      const OFF off = ((OFF)ic * hist_stride32 + (OFF)vc) * (OFF)sizeof(float);
+      stage_y[r] = row_at(ysrc, off);
+      stage_s[r] = row_at(ssrc, off);
       v += step_v; i += step_i;
       if (v >= V) { v -= V; i++; }
     }
@@ -824,22 +916,24 @@ __global__ void __launch_bounds__(256) lbfgs_iteration_tail_wg_kernel(const Line
         const float4 *ry = reinterpret_cast<const float4 *>(s_hist + (v < V ? v : V) * kHistRow);
         const float4 *rs = reinterpret_cast<const float4 *>(s_hist + s_off + (v < V ? v : V) * kHistRow);
 #pragma unroll
-        for (int j = 0; j < LbfgsLimits<G>::MMAX / 4; j++) {  // (slots >= m-1 of a row: never written, never used)
+        for (int j = 0; j < (MMAX + 3) / 4; j++) {  // (slots >= m-1 of a row: never written, never used)
           const float4 qy = ry[j], qs = rs[j];
-          h_ys[4 * j][e] = qy.x; h_ys[4 * j + 1][e] = qy.y; h_ys[4 * j + 2][e] = qy.z; h_ys[4 * j + 3][e] = qy.w;
-          h_ss[4 * j][e] = qs.x; h_ss[4 * j + 1][e] = qs.y; h_ss[4 * j + 2][e] = qs.z; h_ss[4 * j + 3][e] = qs.w;
+          const float cy[4] = {qy.x, qy.y, qy.z, qy.w}, cs[4] = {qs.x, qs.y, qs.z, qs.w};
+#pragma unroll
+          for (int c = 0; c < 4; c++)
+            if (4 * j + c < MMAX) { h_ys[4 * j + c][e] = cy[c]; h_ss[4 * j + c][e] = cs[c]; }
         }
       }
     } else {
 #pragma unroll
-      for (int i = 0; i < LbfgsLimits<G>::MMAX; i++) {
+      for (int i = 0; i < MMAX; i++) {
 #pragma unroll
         for (int e = 0; e < VPL; e++) h_ys[i][e] = h_ss[i][e] = 0.0f;
       }
     }
     float dir[VPL];
-    lbfgs_step_from_history<VPL, G, false>(lb, b, lane, g, x, LBFGS_HISTORY_ARGS, dir);
-    tail_next_candidates<VPL, G, NLSMAX>(pr, b, lane, V, ls.n_linesearch, x, dir, t_smax, t_mag);
+    lbfgs_step_from_history<VPL, G, false, S, OFF>(lb, b, lane, g, x, LBFGS_HISTORY_ARGS, dir);
+    tail_next_candidates<VPL, G, NLSMAX, OFF>(pr, b, lane, V, S::kStatic ? S::kNLS : ls.n_linesearch, x, dir, t_smax, t_mag);
   } else if (n > 0) {
     const int t = tid - kWave;
     const int step_i = kStageLanes / V, step_v = kStageLanes % V;
@@ -850,8 +944,9 @@ __global__ void __launch_bounds__(256) lbfgs_iteration_tail_wg_kernel(const Line
     for (int r = 0; r < RMAX; r++) {
       const int idx = t + r * kStageLanes;
       if (idx < n) {
-        ydst[(size_t)i * hist_stride + v] = stage_y[r];
-        sdst[(size_t)i * hist_stride + v] = stage_s[r];
+        const OFF off = ((OFF)i * hist_stride32 + (OFF)v) * (OFF)sizeof(float);
+        row_at(ydst, off) = stage_y[r];
+        row_at(sdst, off) = stage_s[r];
       }
       v += step_v; i += step_i;
       if (v >= V) { v -= V; i++; }
@@ -941,6 +1036,67 @@ CUROBO_EXPORT int curobo_hip_prepare_search_points(float *x_set, float *step_dir
   return check_launch(what, st);
 }
 
+// ---- which kernel a one-launch tail runs: decided in ONE place, for the launch and for the host-side queries --------
+static bool g_tail_shapes_enabled = true;
+
+template <class S>
+static bool tail_shape_matches(int opt_dim, int history_m, int n_linesearch, int action_dim) {
+  return opt_dim == S::kV && history_m == S::kM && n_linesearch == S::kNLS && action_dim == S::kAD;
+}
+static int tail_shape_of(int opt_dim, int history_m, int n_linesearch, int action_dim) {
+  if (tail_shape_matches<CUROBO_TAIL_SHAPE_1>(opt_dim, history_m, n_linesearch, action_dim)) return 1;
+  if (tail_shape_matches<CUROBO_TAIL_SHAPE_2>(opt_dim, history_m, n_linesearch, action_dim)) return 2;
+  return 0;
+}
+// 32-bit lane offsets (row_at with OFF = uint32_t): the largest byte offset a lane forms must stay below 2^31.
+//   row form: the problem index is part of the offset, the largest row is a candidate row: batch * n_linesearch * opt_dim
+//   workgroup form: a staging lane's offset spans the history slots it moves: history_m * batch * opt_dim
+// Both imply batch * opt_dim * 4 < 2^31.  The 64-lane wavefront form keeps the problem in the scalar base: always fits.
+static bool tail_offsets_fit(long long rows, int batchsize, int opt_dim) {
+  return rows * (long long)batchsize * opt_dim * 4 < (1ll << 31);
+}
+enum TailForm { kTailPlain = 0, kTailRow = 1, kTailWave = 2, kTailWorkgroup = 3 };
+struct TailChoice { int form, shape; };
+static TailChoice tail_choose(int opt_dim, int history_m, int n_linesearch, int action_dim, int batchsize, int overlapped) {
+  static const bool no_row16 = getenv("CUROBO_HIP_NO_ROW16") != nullptr;
+  static const bool no_prefetch = getenv("CUROBO_HIP_TAIL_NO_PREFETCH") != nullptr;
+  static const bool no_wg_env = getenv("CUROBO_HIP_TAIL_NO_WG") != nullptr;
+  static const bool wg_env = getenv("CUROBO_HIP_TAIL_WG") != nullptr;  // (tuning knobs: force either form)
+  static const bool no_shapes_env = getenv("CUROBO_HIP_TAIL_NO_SHAPES") != nullptr;
+  const bool row16 = !no_row16 && opt_dim <= 16 && history_m <= 16 && n_linesearch <= 16;
+  TailChoice c{kTailPlain, 0};
+  if (n_linesearch <= 4 && !no_prefetch) {
+    // a workgroup per problem pays while the problems do not fill the chip (64 / 256: 9.0 / 10.1 us against 12.3 /
+    // 12.9 us for a wavefront per problem); at 1024 problems the extra wavefronts cost more than they hide (19 vs 15).
+    // Between the rollout workgroups of other seed shards (`overlapped`) it is the other way round: the workgroup form
+    // needs 24 KB of LDS and four 179-VGPR wavefronts per problem on CUs that the rollouts fill to 151 of 160 KB and
+    // 384 of 512 VGPRs per SIMD (C2, 100-iteration blocks: 65.1 us per iteration with it, 60.4 us without)
+    const bool no_wg = !wg_env && (no_wg_env || overlapped != 0 || batchsize > 512);
+    if (row16) c.form = tail_offsets_fit(n_linesearch, batchsize, opt_dim) ? kTailRow : kTailPlain;
+    else if (no_wg || !tail_offsets_fit(history_m, batchsize, opt_dim)) c.form = kTailWave;
+    else c.form = kTailWorkgroup;
+  }
+  if (c.form != kTailPlain && g_tail_shapes_enabled && !no_shapes_env) {
+    const int id = tail_shape_of(opt_dim, history_m, n_linesearch, action_dim);
+    // (a shape is held by the forms its problems run in: 1 = wavefront and workgroup, 2 = row)
+    if ((id == 1 && (c.form == kTailWave || c.form == kTailWorkgroup)) || (id == 2 && c.form == kTailRow)) c.shape = id;
+  }
+  return c;
+}
+
+CUROBO_EXPORT int curobo_hip_lbfgs_tail_shape_id(int opt_dim, int history, int n_linesearch, int action_dim) {
+  return tail_shape_of(opt_dim, history, n_linesearch, action_dim);
+}
+CUROBO_EXPORT int curobo_hip_lbfgs_set_tail_shapes_enabled(int enabled) {
+  g_tail_shapes_enabled = enabled != 0;
+  return CUROBO_HIP_OK;
+}
+CUROBO_EXPORT int curobo_hip_lbfgs_tail_form(int opt_dim, int history, int n_linesearch, int action_dim, int batchsize,
+                                             int overlapped) {
+  const TailChoice c = tail_choose(opt_dim, history, n_linesearch, action_dim, batchsize, overlapped);
+  return c.form | (c.shape << 4);
+}
+
 CUROBO_EXPORT int curobo_hip_launch_lbfgs_iteration_tail(
     float *best_cost, float *best_action, int16_t *best_iteration, int16_t *current_iteration,
     uint8_t *converged_global, int convergence_iteration, float cost_delta_threshold,
@@ -974,32 +1130,27 @@ CUROBO_EXPORT int curobo_hip_launch_lbfgs_iteration_tail(
   hipStream_t st = (hipStream_t)stream;
   static const bool wg64 = getenv("CUROBO_HIP_TAIL_WG64") != nullptr;
   const dim3 grid((unsigned)ceil_div(batchsize, wg64 ? 1 : 4)), block(wg64 ? 64 : 256);
-  static const bool no_row16 = getenv("CUROBO_HIP_NO_ROW16") != nullptr;
-  static const bool no_prefetch = getenv("CUROBO_HIP_TAIL_NO_PREFETCH") != nullptr;
-  const bool row16 = !no_row16 && opt_dim <= 16 && history_m <= 16 && n_linesearch <= 16;
   const dim3 grid16((unsigned)ceil_div(batchsize, 16));
-  if (n_linesearch <= 4 && !no_prefetch) {
-    // a workgroup per problem pays while the problems do not fill the chip (64 / 256: 9.0 / 10.1 us against 12.3 /
-    // 12.9 us for a wavefront per problem); at 1024 problems the extra wavefronts cost more than they hide (19 vs 15).
-    // Between the rollout workgroups of other seed shards (`overlapped`) it is the other way round: the workgroup form
-    // needs 24 KB of LDS and four 179-VGPR wavefronts per problem on CUs that the rollouts fill to 151 of 160 KB and
-    // 384 of 512 VGPRs per SIMD (C2, 100-iteration blocks: 65.1 us per iteration with it, 60.4 us without)
-    static const bool no_wg_env = getenv("CUROBO_HIP_TAIL_NO_WG") != nullptr;
-    static const bool wg_env = getenv("CUROBO_HIP_TAIL_WG") != nullptr;  // (tuning knobs: force either form)
-    const bool no_wg = !wg_env && (no_wg_env || overlapped != 0 || batchsize > 512);
+  const TailChoice c = tail_choose(opt_dim, history_m, n_linesearch, action_dim, batchsize, overlapped);
+  if (c.form == kTailRow) {
+    if (c.shape == 2) hipLaunchKernelGGL((lbfgs_iteration_tail_prefetch_kernel<1, 16, 4, CUROBO_TAIL_SHAPE_2>), grid16, block, 0, st, ls, lb, pr);
+    else hipLaunchKernelGGL((lbfgs_iteration_tail_prefetch_kernel<1, 16, 4>), grid16, block, 0, st, ls, lb, pr);
+  } else if (c.form == kTailWave) {
+    if (c.shape == 1) hipLaunchKernelGGL((lbfgs_iteration_tail_prefetch_kernel<2, kWave, 4, CUROBO_TAIL_SHAPE_1>), grid, block, 0, st, ls, lb, pr);
+    else if (opt_dim <= kWave) hipLaunchKernelGGL((lbfgs_iteration_tail_prefetch_kernel<1, kWave, 4>), grid, block, 0, st, ls, lb, pr);
+    else hipLaunchKernelGGL((lbfgs_iteration_tail_prefetch_kernel<2, kWave, 4>), grid, block, 0, st, ls, lb, pr);
+  } else if (c.form == kTailWorkgroup) {
     const int n_move = history_m > 0 ? (history_m - 1) * opt_dim : 0;
     const int rounds = ceil_div(n_move, kStageLanes);
     const size_t lds = (size_t)2 * (opt_dim + 1) * kHistRow * sizeof(float);
     const dim3 grid_wg((unsigned)batchsize);
-    if (row16) hipLaunchKernelGGL((lbfgs_iteration_tail_prefetch_kernel<1, 16, 4>), grid16, block, 0, st, ls, lb, pr);
-    else if (no_wg && opt_dim <= kWave) hipLaunchKernelGGL((lbfgs_iteration_tail_prefetch_kernel<1, kWave, 4>), grid, block, 0, st, ls, lb, pr);
-    else if (no_wg) hipLaunchKernelGGL((lbfgs_iteration_tail_prefetch_kernel<2, kWave, 4>), grid, block, 0, st, ls, lb, pr);
+    if (c.shape == 1) hipLaunchKernelGGL((lbfgs_iteration_tail_wg_kernel<2, 4, 12, CUROBO_TAIL_SHAPE_1>), grid_wg, block, lds, st, ls, lb, pr);
     else if (opt_dim <= kWave && rounds <= 12) hipLaunchKernelGGL((lbfgs_iteration_tail_wg_kernel<1, 4, 12>), grid_wg, block, lds, st, ls, lb, pr);
     else if (opt_dim <= kWave) hipLaunchKernelGGL((lbfgs_iteration_tail_wg_kernel<1, 4, 20>), grid_wg, block, lds, st, ls, lb, pr);
     else if (rounds <= 12) hipLaunchKernelGGL((lbfgs_iteration_tail_wg_kernel<2, 4, 12>), grid_wg, block, lds, st, ls, lb, pr);
     else hipLaunchKernelGGL((lbfgs_iteration_tail_wg_kernel<2, 4, 20>), grid_wg, block, lds, st, ls, lb, pr);
-  } else if (row16)  // IK-sized problems: one 16-lane row each
-    hipLaunchKernelGGL((lbfgs_iteration_tail_kernel<1, 16>), grid16, block, 0, st, ls, lb, pr);
+  } else if (opt_dim <= 16 && history_m <= 16 && n_linesearch <= 16 && getenv("CUROBO_HIP_NO_ROW16") == nullptr)
+    hipLaunchKernelGGL((lbfgs_iteration_tail_kernel<1, 16>), grid16, block, 0, st, ls, lb, pr);  // IK-sized problems: one 16-lane row each
   else if (opt_dim <= kWave) hipLaunchKernelGGL((lbfgs_iteration_tail_kernel<1>), grid, block, 0, st, ls, lb, pr);
   else hipLaunchKernelGGL((lbfgs_iteration_tail_kernel<2>), grid, block, 0, st, ls, lb, pr);
   return check_launch(what, st);

@@ -918,6 +918,22 @@ int curobo_hip_launch_lbfgs_iteration_tail(
     const float *action_step_max, int action_dim, int apply_step_scale, int overlapped,
     curobo_hip_stream_t stream);
 
+/* Compile-time shapes of the one-launch tail (csrc/tail_shapes.hpp), after the fused rollout's: for the problem sizes listed
+ * there (trajectory optimisation of a 7-dof arm: opt_dim 84, history 27; its inverse kinematics: opt_dim 7, history 7; four
+ * candidates each) the library holds instantiations whose opt_dim, history, n_linesearch and action_dim are constants.  A
+ * launch takes one only when ALL four match, otherwise the kernels that read them from their arguments -- same results, bit
+ * for bit.  Host-side, no GPU work:
+ * curobo_hip_lbfgs_tail_shape_id: the id (>= 1) of the shape with these dimensions, 0 = none.
+ * curobo_hip_lbfgs_set_tail_shapes_enabled(0) makes every launch take the run-time kernels (tests, A/B timing).
+ * curobo_hip_lbfgs_tail_form: what curobo_hip_launch_lbfgs_iteration_tail runs for these arguments, as form | shape << 4:
+ *   form 0 = the plain kernel (64-bit addresses), 1 = 16-lane row per problem, 2 = wavefront per problem, 3 = workgroup per
+ *   problem; shape = the compile-time shape taken (0 = run-time dimensions).  Forms 1 and 3 keep part of the row address in a
+ *   32-bit lane offset and are taken only when it fits (batchsize * opt_dim * 4 bytes times n_linesearch resp. history stays
+ *   below 2^31); past that the launch runs form 0 resp. 2. */
+int curobo_hip_lbfgs_tail_shape_id(int opt_dim, int history, int n_linesearch, int action_dim);
+int curobo_hip_lbfgs_set_tail_shapes_enabled(int enabled);
+int curobo_hip_lbfgs_tail_form(int opt_dim, int history, int n_linesearch, int action_dim, int batchsize, int overlapped);
+
 /* ---------------------------------------------------------------- rollout glue
  * Per-trajectory cost sum (reference rollout/metrics.py:233-265 + util/tensor_util.py:104:
  * torch cat + sum): out[b] = sum_h( self_cost[b,h] + sum_s scene_cost[b,h,s] ), one wavefront
