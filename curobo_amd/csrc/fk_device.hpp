@@ -8,6 +8,19 @@ namespace curobo_hip {
 
 constexpr int kFkLanes = 16;  // lanes per point
 
+// Hands out the regions of a launch's dynamic LDS in 16-byte granules (offsets and sizes in floats), as fused_layout does:
+// the kernel carves its pointers (lds_at) and the launcher sizes the allocation from the same *_layout function, and
+// every region that `take` hands out may be accessed through float4.  `words` packs a table of 4-byte words directly
+// behind the previous one; `align` closes such a run on a granule.
+struct LdsCarver {
+  int o = 0;
+  __host__ __device__ constexpr int words(int n) { const int at = o; o += n; return at; }
+  __host__ __device__ constexpr int take(int n) { return words((n + 3) & ~3); }
+  __host__ __device__ constexpr void align() { o = (o + 3) & ~3; }
+};
+template <typename T>
+__device__ __forceinline__ T *lds_at(float *smem, int offset) { return reinterpret_cast<T *>(smem + offset); }
+
 // reference kinematics_forward_helper.cuh:316-393 / kinematics_util.cuh:62-74, in two steps so that the
 // transcendental can be computed by other lanes than the ones that build the matrix:
 //   joint_sincos: (s, c) of the joint angle (revolute), or s = the displacement (prismatic)
@@ -75,33 +88,12 @@ __device__ __forceinline__ float lds_read_f32_now(const float *p) {
 
 // Serial chain of ONE point, executed by its 16-lane group without any barrier (lane 4r+c owns
 // element (r, c) of every cumulative 3x4; a lane only re-reads entries it wrote itself, the three
-// rotation entries of its row come from its DPP quad).  `local` holds the point's column-major
-// padded local transforms [L][16], `cumul` receives [L][12] row-major, `parent` = link_map.
-__device__ __forceinline__ void fk_chain_16(float *__restrict__ cumul, const float *__restrict__ local,
-                                            const int *__restrict__ parent, const float *__restrict__ fixed_transform,
-                                            int L, int lane) {
-  const int c = lane & 3;
-  const bool owner = lane < 12;
-  float cur = owner ? fixed_transform[lane] : 0.0f;  // base link: reference :467-485
-  if (owner) cumul[lane] = cur;
-  const float *my_local = local + c * 4;
-  for (int l = 1; l < L; l++) {
-    const int par = __builtin_amdgcn_readfirstlane(parent[l]);
-    float p = cur;
-    if (par != l - 1) p = lds_read_f32_now(cumul + par * 12 + lane);  // see fk_chain_16_multi
-    p = owner ? p : 0.0f;
-    const float a0 = quad_bcast<0>(p), a1 = quad_bcast<1>(p), a2 = quad_bcast<2>(p), a3 = quad_bcast<3>(p);
-    const float4 m = *reinterpret_cast<const float4 *>(my_local + l * 16);
-    cur = a0 * m.x + a1 * m.y + a2 * m.z + (c == 3 ? a3 : 0.0f);
-    if (owner) cumul[l * 12 + lane] = cur;
-  }
-}
-
-// fk_chain_16 with the cumulative transform of link l written OVER the local transform of link l (both at
-// buf + l * 16; the 3x4 takes the first 12 floats).  Every lane of the group has read its column of local[l]
-// before any lane writes cumul[l] (one wavefront, LDS operations execute in issue order), and nothing reads
-// local[l] again: the kernel needs 16 instead of 28 floats of LDS per (point, link).  No __restrict__ here: the
-// read of local[l] must stay ahead of the write to the same words.
+// rotation entries of its row come from its DPP quad; base link: reference :467-485).  `parent` = link_map.
+// The local transform of link l (column-major, padded) and its cumulative transform (3x4 row-major, the first
+// 12 floats) share buf + l * 16: every lane of the group has read its column of local[l] before any lane
+// writes cumul[l] (one wavefront, LDS operations execute in issue order), and nothing reads local[l] again,
+// so the kernel needs 16 instead of 28 floats of LDS per (point, link).  No __restrict__ here: the read of
+// local[l] must stay ahead of the write to the same words.  (fk_chain_16_multi: separate buffers, pipelined.)
 __device__ __forceinline__ void fk_chain_16_inplace(float *buf, const int *__restrict__ parent,
                                                     const float *__restrict__ fixed_transform, int L, int lane) {
   const int c = lane & 3;
@@ -248,34 +240,73 @@ __device__ __forceinline__ void fk_chain_16_multi(float *const (&cumul)[N], cons
   }
 }
 
+// The link-info word of the staged robot tables: (joint_type + 1) in the low byte (joint_type in [-1, 5]), the joint's
+// index in q above it (0 for a link without a joint).
+__device__ __forceinline__ int link_info_pack(int joint_type, int joint_index) {
+  return (joint_type + 1) | ((joint_index < 0 ? 0 : joint_index) << 8);
+}
+__device__ __forceinline__ int link_joint_type(int info) { return (info & 0xff) - 1; }
+__device__ __forceinline__ int link_joint_index(int info) { return info >> 8; }
+
+// world axis of a joint of type jt >= J_X_PRISM (a column of the rotation block) and world origin of its link, from the
+// link's cumulative 3x4 row-major transform (row stride 4: both the [12] and the [16] layouts)
+__device__ __forceinline__ f3 joint_axis(const float *C, int jt) {
+  const int ax = jt >= J_X_ROT ? jt - J_X_ROT : jt;
+  return make_f3(C[ax], C[4 + ax], C[8 + ax]);
+}
+__device__ __forceinline__ f3 link_origin(const float *C) { return make_f3(C[3], C[7], C[11]); }
+
+// geometric-Jacobian column of one link of a tool's chain (reference kinematics_forward_kernel.cuh:45-200): revolute
+// (axis x (ee - o), axis), prismatic (axis, 0), with axis = sign * world axis.  Returns whether there is an angular part.
+__device__ __forceinline__ bool jacobian_column(const float *C, int jt, float sign, f3 ee, f3 &lin, f3 &ang) {
+  const f3 axis = sign * joint_axis(C, jt);
+  if (jt >= J_X_ROT) { lin = cross(axis, ee - link_origin(C)); ang = axis; return true; }
+  lin = axis; ang = make_f3(0.f, 0.f, 0.f);
+  return false;
+}
+
+// omega = 0.5 * E(q)^T g: the angular velocity that a quaternion-rate gradient g (wxyz) at the unit quaternion q (xyzw)
+// stands for (reference quaternion_util.cuh:86-102)
+__device__ __forceinline__ f3 quat_rate_to_omega(float4 qx, float4 g_wxyz) {
+  const float dqw = g_wxyz.x, dqx = g_wxyz.y, dqy = g_wxyz.z, dqz = g_wxyz.w;
+  return make_f3(0.5f * (-qx.x * dqw + qx.w * dqx + qx.z * dqy - qx.y * dqz),
+                 0.5f * (-qx.y * dqw - qx.z * dqx + qx.w * dqy + qx.x * dqz),
+                 0.5f * (-qx.z * dqw + qx.y * dqx - qx.x * dqy + qx.w * dqz));
+}
+
 // Small robot tables staged in LDS once per workgroup (the chain walk is a pointer chase; from
 // global memory every step is a dependent L1/L2 round trip).
 struct BwdTables {
   const int *chain;      // [C]   link indices, CSR data
   const int *chain_off;  // [L+1] CSR offsets
-  const int *link_info;  // [L]   (joint_type + 1) | joint_index << 8   (joint_type in [-1,5])
+  const int *link_info;  // [L]   link_info_pack(joint type, joint index)
   const float *sign;     // [L]   joint_offset[2*l] (axis sign x mimic multiplier)
 };
 
-// gradient of one world point p with cost gradient g, pushed down the chain of link `l`
-// (reference kinematics_backward_helper.cuh:62-98, kinematics_joint_util.cuh:13-66)
-__device__ __forceinline__ void chain_point_vjp(float *__restrict__ psum, const float *__restrict__ cumul,
-                                                const BwdTables &t, int l, f3 p, f3 g) {
-  const int cs = t.chain_off[l];
-  for (int ci = t.chain_off[l + 1] - 1; ci >= cs; ci--) {
+// A lane walks chain entries first, first + STEP, ... (before `last`) of the CSR chain data and adds, for every link j with a
+// joint, project(revolute, sign, axis, C_j) to the joint's slot of `psum` (an LDS row: ds_add_f32).
+template <int STEP, typename Project>
+__device__ __forceinline__ void chain_walk_vjp(float *psum, const float *cumul, const BwdTables &t, int first, int last,
+                                               Project project) {
+  for (int ci = first; STEP > 0 ? ci < last : ci > last; ci += STEP) {
     const int j = t.chain[ci];
     const int info = t.link_info[j];
-    const int jt = (info & 0xff) - 1;
+    const int jt = link_joint_type(info);
     if (jt < J_X_PRISM) continue;
     const float sign = t.sign[j];
     const float *C = cumul + j * 12;
-    const int ax = jt >= J_X_ROT ? jt - J_X_ROT : jt;
-    const f3 axis = make_f3(C[ax], C[4 + ax], C[8 + ax]);
-    float r;
-    if (jt >= J_X_ROT) r = dot(sign * g, cross(axis, p - make_f3(C[3], C[7], C[11])));
-    else r = sign * dot(axis, g);
-    atomicAdd(&psum[info >> 8], r);  // own LDS row: ds_add_f32, never contended
+    atomicAdd(&psum[link_joint_index(info)], project(jt >= J_X_ROT, sign, joint_axis(C, jt), C));
   }
+}
+
+// gradient of one world point p with cost gradient g, pushed down the chain of link `l` from the link to the root by one
+// lane into its own row (reference kinematics_backward_helper.cuh:62-98, kinematics_joint_util.cuh:13-66)
+__device__ __forceinline__ void chain_point_vjp(float *__restrict__ psum, const float *__restrict__ cumul,
+                                                const BwdTables &t, int l, f3 p, f3 g) {
+  const auto project = [&](bool rev, float sign, f3 axis, const float *C) {
+    return rev ? dot(sign * g, cross(axis, p - link_origin(C))) : sign * dot(axis, g);
+  };
+  chain_walk_vjp<-1>(psum, cumul, t, t.chain_off[l + 1] - 1, t.chain_off[l] - 1, project);
 }
 
 // the same for a WRENCH on link `l`: force F and torque T about the world origin (the sum of g and of p x g over
@@ -283,21 +314,22 @@ __device__ __forceinline__ void chain_point_vjp(float *__restrict__ psum, const 
 // link instead of one per point.
 __device__ __forceinline__ void chain_wrench_vjp(float *__restrict__ psum, const float *__restrict__ cumul,
                                                  const BwdTables &t, int l, f3 F, f3 T) {
-  const int cs = t.chain_off[l];
-  for (int ci = t.chain_off[l + 1] - 1; ci >= cs; ci--) {
-    const int j = t.chain[ci];
-    const int info = t.link_info[j];
-    const int jt = (info & 0xff) - 1;
-    if (jt < J_X_PRISM) continue;
-    const float sign = t.sign[j];
-    const float *C = cumul + j * 12;
-    const int ax = jt >= J_X_ROT ? jt - J_X_ROT : jt;
-    const f3 axis = make_f3(C[ax], C[4 + ax], C[8 + ax]);
-    float r;
-    if (jt >= J_X_ROT) r = sign * dot(axis, T - cross(make_f3(C[3], C[7], C[11]), F));
-    else r = sign * dot(axis, F);
-    atomicAdd(&psum[info >> 8], r);
-  }
+  const auto project = [&](bool rev, float sign, f3 axis, const float *C) {
+    return rev ? sign * dot(axis, T - cross(link_origin(C), F)) : sign * dot(axis, F);
+  };
+  chain_walk_vjp<-1>(psum, cumul, t, t.chain_off[l + 1] - 1, t.chain_off[l] - 1, project);
+}
+
+// Gradient of a tool frame's pose on link `l` -- position gradient g at the frame's origin `pos` plus the free
+// angular part `om` (quat_rate_to_omega) -- with the chain entries dealt out over the 16 lanes of the point's row
+// (reference kinematics_backward_helper.cuh:102-183).  `psum`: the lane's own row in fk_backward_kernel, one shared by
+// the 16 lanes in the seed-IK kernel.
+__device__ __forceinline__ void chain_pose_vjp_lanes(float *psum, const float *cumul, const BwdTables &t, int l, f3 pos, f3 g,
+                                                     f3 om, int lane) {
+  const auto project = [&](bool rev, float sign, f3 axis, const float *C) {
+    return rev ? dot(sign * g, cross(axis, pos - link_origin(C))) + sign * dot(axis, om) : sign * dot(axis, g);
+  };
+  chain_walk_vjp<kFkLanes>(psum, cumul, t, t.chain_off[l] + lane, t.chain_off[l + 1], project);
 }
 
 }  // namespace curobo_hip

@@ -609,10 +609,10 @@ __device__ __forceinline__ void point_vjp_gather(const FusedCtx &c, int h, bool 
   for (int l = lane; l < c.L; l += kFkLanes) {
     float r = 0.0f;
     const int info = c.link_info[l];
-    const int jt = (info & 0xff) - 1;
+    const int jt = link_joint_type(info);
     if (any_grad && jt >= J_X_PRISM) {
       const float *C = cumul + l * 12;
-      const f3 o = make_f3(C[3], C[7], C[11]);
+      const f3 o = link_origin(C);
       f3 F = make_f3(0.f, 0.f, 0.f), T = make_f3(0.f, 0.f, 0.f);
       for (int wd = 0; wd < (c.L + 31) / 32; wd++) {
         uint32_t mask = c.sub[l * 4 + wd];
@@ -623,11 +623,10 @@ __device__ __forceinline__ void point_vjp_gather(const FusedCtx &c, int h, bool 
           const f3 f = make_f3(w[0], w[1], w[2]);
           const float *Cp = cumul + lp * 12;
           F = F + f;
-          T = T + make_f3(w[3], w[4], w[5]) + cross(make_f3(Cp[3], Cp[7], Cp[11]) - o, f);
+          T = T + make_f3(w[3], w[4], w[5]) + cross(link_origin(Cp) - o, f);
         }
       }
-      const int ax = jt >= J_X_ROT ? jt - J_X_ROT : jt;
-      const f3 axis = make_f3(C[ax], C[4 + ax], C[8 + ax]);
+      const f3 axis = joint_axis(C, jt);
       r = c.sign[l] * (jt >= J_X_ROT ? dot(axis, T) : dot(axis, F));
     }
     wr[l * kWrench + 6] = r;  // slot 6 of link l: its joint gradient
@@ -653,8 +652,8 @@ __device__ __forceinline__ void point_fk_locals(const FusedCtx &c, int h, int la
   float *work = c.work + (size_t)h * c.ws;
   for (int l = lane; l < c.L; l += kFkLanes) {
     const int info = c.link_info[l];
-    const int jt = (info & 0xff) - 1;
-    const float qv = jt != J_FIXED ? c.q[h * c.D + (info >> 8)] : 0.0f;
+    const int jt = link_joint_type(info);
+    const float qv = jt != J_FIXED ? c.q[h * c.D + link_joint_index(info)] : 0.0f;
     local_transform_colmajor(work + l * 16, c.fixed + l * 12, jt, qv, c.sign[l], c.off_add[l]);
   }
 }
@@ -712,15 +711,11 @@ __device__ __forceinline__ void point_tool_pose(const FusedCtx &c, const ToolPos
       l = tool_frame_map[t];
       const float *C = cumul + l * 12;
       const float4 qx = quat_from_transform(C);
-      pos = make_f3(C[3], C[7], C[11]);
+      pos = link_origin(C);
       const ToolPoseResult res = tool_pose_distance_point(tp, n, hh, t, pos, make_float4(qx.w, qx.x, qx.y, qx.z));
       cost_pt += res.position_cost + res.rotation_cost;
       gp = res.position_gradient;
-      // omega = 0.5 * E(q)^T g  (q xyzw, g wxyz)
-      const float dqw = res.quat_rate_wxyz.x, dqx = res.quat_rate_wxyz.y, dqy = res.quat_rate_wxyz.z, dqz = res.quat_rate_wxyz.w;
-      om = make_f3(0.5f * (-qx.x * dqw + qx.w * dqx + qx.z * dqy - qx.y * dqz),
-                   0.5f * (-qx.y * dqw - qx.z * dqx + qx.w * dqy + qx.x * dqz),
-                   0.5f * (-qx.z * dqw + qx.y * dqx - qx.x * dqy + qx.w * dqz));
+      om = quat_rate_to_omega(qx, res.quat_rate_wxyz);
       const size_t o = out_index0 + t;
       if (tp.out_distance) { tp.out_distance[2 * o] = res.position_cost; tp.out_distance[2 * o + 1] = res.rotation_cost; }
       if (tp.out_position_distance) tp.out_position_distance[o] = res.position_distance;
@@ -904,7 +899,7 @@ __device__ __forceinline__ void fused_stage_tables(const FusedCtx &c, const Fuse
       }
       if (i < L) {
         c.parent[i] = v_parent;
-        c.link_info[i] = (v_type + 1) | ((v_joint < 0 ? 0 : v_joint) << 8);
+        c.link_info[i] = link_info_pack(v_type, v_joint);
         c.sign[i] = v_sign;
         c.off_add[i] = v_add;
       }
@@ -950,7 +945,7 @@ __device__ __forceinline__ void fused_derive_tables(const FusedCtx &c) {
   for (int l = rotated_tid(nwaves - 1); l < c.L; l += nt) {
     for (int ci = c.chain_off[l]; ci < c.chain_off[l + 1]; ci++) atomicOr(&c.sub[c.chain[ci] * 4 + (l >> 5)], 1u << (l & 31));
     const int info = c.link_info[l];
-    if ((info & 0xff) - 1 >= J_X_PRISM) atomicOr(&c.jlinks[(info >> 8) * 4 + (l >> 5)], 1u << (l & 31));
+    if (link_joint_type(info) >= J_X_PRISM) atomicOr(&c.jlinks[link_joint_index(info) * 4 + (l >> 5)], 1u << (l & 31));
   }
   for (int sidx = rotated_tid(nwaves > 1 ? nwaves - 2 : 0); sidx < c.S; sidx += nt) {
     const float4 v = c.rs[sidx];
@@ -1248,10 +1243,10 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
   for (int e = tid; e < H * L; e += nt) {
     const int h = e / L, l = e - h * L;
     const int info = c.link_info[l];
-    const int jt = (info & 0xff) - 1;
+    const int jt = link_joint_type(info);
     if (jt != J_FIXED) {
       float sn, cs;
-      joint_sincos(jt, c.q[h * D + (info >> 8)], c.sign[l], c.off_add[l], &sn, &cs);
+      joint_sincos(jt, c.q[h * D + link_joint_index(info)], c.sign[l], c.off_add[l], &sn, &cs);
       *reinterpret_cast<float2 *>(c.cumul + ((size_t)h * L + l) * 12) = make_float2(sn, cs);
     }
   }

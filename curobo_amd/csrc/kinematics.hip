@@ -21,8 +21,6 @@
 //     contiguous segments per point.
 //   * the VJP accumulates per-lane partial joint gradients in LDS rows (ds_add_f32, no dynamic
 //     register indexing -> no scratch), then 16-lane reduces them.
-#include <cstdlib>
-
 #include "fk_device.hpp"
 
 namespace curobo_hip {
@@ -53,33 +51,57 @@ struct FkArgs {
   int n_points, horizon, nspheres, num_envs, nlinks, njoints, n_tool_frames;
 };
 
+// one set of robot spheres: the table goes to LDS with the first loads of the block, and the sphere pass of the
+// forward kernels is LDS -> registers -> HBM with no global load on its path
+__device__ __forceinline__ void stage_sphere_table(float4 *s_sph, int *s_sph_link, const FkArgs &a, int tid) {
+  for (int s = tid; s < a.nspheres; s += blockDim.x) {
+    s_sph[s] = reinterpret_cast<const float4 *>(a.robot_spheres)[s];
+    s_sph_link[s] = a.link_sphere_map[s];
+  }
+}
+
+// pose of a tool frame from its cumulative transform C (reference :270-301), quaternion wxyz; o = flat (point, frame)
+__device__ __forceinline__ void write_tool_pose(const FkArgs &a, const float *C, size_t o) {
+  const float4 qx = quat_from_transform(C);
+  reinterpret_cast<float4 *>(a.link_quat)[o] = make_float4(qx.w, qx.x, qx.y, qx.z);
+  float *p = a.link_pos + o * 3;
+  p[0] = C[3]; p[1] = C[7]; p[2] = C[11];
+}
+
 constexpr int kFkLinkStride = 16;  // floats of LDS per (point, link): the local 3x4 column-major padded, then the
                                    // cumulative 3x4 row-major over it (fk_chain_16_inplace)
 
+// dynamic LDS of fk_forward_kernel (offsets and total in floats; S = 0 without the sphere output)
+struct FkGroupedLayout { int cumul, sph, sph_link, parent, total; };
+__host__ __device__ inline FkGroupedLayout fk_grouped_layout(int pts, int L, int S) {
+  FkGroupedLayout f{};
+  LdsCarver c;
+  f.cumul = c.take(pts * L * kFkLinkStride);  // [pts][L][16]
+  f.sph = c.take(S * 4); f.sph_link = c.take(S);  // [S] float4 robot spheres (one env), [S] their links
+  f.parent = c.take(L);                       // [L]
+  f.total = c.o;
+  return f;
+}
+
+// The scalar registers are capped at what eight wavefronts per SIMD allow.  The instantiations with the Jacobian sit at
+// that edge, and two scalars spilled to the lanes of a vector register cost less than a wavefront.
 template <bool SPHERES, bool JACOBIAN, bool COM, bool WRITE_CUMUL>
-__global__ void __launch_bounds__(256) fk_forward_kernel(const FkArgs a) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(100))) fk_forward_kernel(const FkArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int L = a.nlinks;
   const int pts = blockDim.x / kFkLanes;
-  float *cumul = smem;                                                    // [pts][L][16]
-  float4 *s_sph = reinterpret_cast<float4 *>(smem + pts * L * kFkLinkStride);  // [S] robot spheres (one env)
-  int *s_sph_link = reinterpret_cast<int *>(s_sph + (SPHERES ? a.nspheres : 0));  // [S]
-  int *s_parent = s_sph_link + (SPHERES ? a.nspheres : 0);                // [L]
+  const FkGroupedLayout lay = fk_grouped_layout(pts, L, SPHERES ? a.nspheres : 0);
+  float *cumul = smem + lay.cumul;
+  float4 *s_sph = lds_at<float4>(smem, lay.sph);
+  int *s_sph_link = lds_at<int>(smem, lay.sph_link), *s_parent = lds_at<int>(smem, lay.parent);
 
   const int tid = threadIdx.x;
   const int pt0 = blockIdx.x * pts;
   const int npts = min(pts, a.n_points - pt0);
 
   for (int l = tid; l < L; l += blockDim.x) s_parent[l] = a.link_map[l];
-  // one set of robot spheres: the table goes to LDS with the first loads of the block, and the sphere pass
-  // below is LDS -> registers -> HBM with no global load on its path
   const bool spheres_staged = SPHERES && a.num_envs <= 1;
-  if (spheres_staged) {
-    for (int s = tid; s < a.nspheres; s += blockDim.x) {
-      s_sph[s] = reinterpret_cast<const float4 *>(a.robot_spheres)[s];
-      s_sph_link[s] = a.link_sphere_map[s];
-    }
-  }
+  if (spheres_staged) stage_sphere_table(s_sph, s_sph_link, a, tid);
 
   // ---- phase 1: local transforms, one (point, link) item per lane
   for (int e = tid; e < npts * L; e += blockDim.x) {
@@ -144,21 +166,16 @@ __global__ void __launch_bounds__(256) fk_forward_kernel(const FkArgs a) {
       reinterpret_cast<float4 *>(a.com_out)[n] = o;
     }
   }
-  // ---- tool-frame poses (reference :270-301), quaternion written wxyz
-  for (int t = lane; t < a.n_tool_frames; t += kFkLanes) {
-    const float *C = my_cumul + a.tool_frame_map[t] * kFkLinkStride;
-    const float4 qx = quat_from_transform(C);
-    reinterpret_cast<float4 *>(a.link_quat)[(size_t)n * a.n_tool_frames + t] = make_float4(qx.w, qx.x, qx.y, qx.z);
-    float *p = a.link_pos + ((size_t)n * a.n_tool_frames + t) * 3;
-    p[0] = C[3]; p[1] = C[7]; p[2] = C[11];
-  }
+  // ---- tool-frame poses
+  for (int t = lane; t < a.n_tool_frames; t += kFkLanes)
+    write_tool_pose(a, my_cumul + a.tool_frame_map[t] * kFkLinkStride, (size_t)n * a.n_tool_frames + t);
   // ---- geometric Jacobian (reference :45-200), one joint column per lane, no atomics
   if (JACOBIAN) {
     const int D = a.njoints, T = a.n_tool_frames;
     for (int t = 0; t < T; t++) {
       const int tl = a.tool_frame_map[t];
       const float *E = my_cumul + tl * kFkLinkStride;
-      const f3 ee = make_f3(E[3], E[7], E[11]);
+      const f3 ee = link_origin(E);
       const int cs = a.link_chain_offsets[tl], ce = a.link_chain_offsets[tl + 1];
       float *J = a.jacobian_out + ((size_t)n * T + t) * 6 * D;
       for (int j = lane; j < D; j += kFkLanes) {
@@ -170,19 +187,12 @@ __global__ void __launch_bounds__(256) fk_forward_kernel(const FkArgs a) {
             bool in_chain = false;
             for (int ci = cs; ci < ce; ci++) in_chain |= (a.link_chain_data[ci] == li);
             if (!in_chain) continue;
-            const float *C = my_cumul + li * kFkLinkStride;
             const int jt = a.joint_map_type[li];
-            const float sign = a.joint_offset[li * 2];
-            if (jt >= J_X_ROT) {
-              const int ax = jt - J_X_ROT;
-              const f3 axis = sign * make_f3(C[ax], C[4 + ax], C[8 + ax]);
-              const f3 lin = cross(axis, ee - make_f3(C[3], C[7], C[11]));
-              col[0] += lin.x; col[1] += lin.y; col[2] += lin.z;
-              col[3] += axis.x; col[4] += axis.y; col[5] += axis.z;
-            } else if (jt >= J_X_PRISM) {
-              const int ax = jt - J_X_PRISM;
-              col[0] += sign * C[ax]; col[1] += sign * C[4 + ax]; col[2] += sign * C[8 + ax];
-            }
+            if (jt < J_X_PRISM) continue;
+            f3 lin, ang;
+            const bool revolute = jacobian_column(my_cumul + li * kFkLinkStride, jt, a.joint_offset[li * 2], ee, lin, ang);
+            col[0] += lin.x; col[1] += lin.y; col[2] += lin.z;
+            if (revolute) { col[3] += ang.x; col[4] += ang.y; col[5] += ang.z; }
           }
         }
 #pragma unroll
@@ -214,6 +224,8 @@ template <bool SPHERES, bool WRITE_CUMUL>
 __global__ void __launch_bounds__(256) fk_forward_points_kernel(const FkArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int L = a.nlinks, S = SPHERES ? a.nspheres : 0, D = a.njoints, T = a.n_tool_frames;
+  // (this launch is bound by the scalar work in front of its first loads: the pointer chain below, restated by the byte sum
+  // of fk_forward_dispatch, measured 0.2 us faster at the C3 size than offsets taken from a layout function)
   float *cumul = smem;                                                 // [kFkPts][L][12]
   float2 *s_sc = reinterpret_cast<float2 *>(cumul + kFkPts * L * 12);  // [kFkPts][L] (sin, cos) | displacement
   float4 *s_col = reinterpret_cast<float4 *>(s_sc + kFkPts * L);       // [L][4][2] column tables (see above)
@@ -243,12 +255,7 @@ __global__ void __launch_bounds__(256) fk_forward_points_kernel(const FkArgs a) 
     if (jointed) s_jointed[__popcll(mask & ((1ull << tid) - 1ull))] = tid;
     if (tid == 0) s_jointed[L] = __popcll(mask);
   }
-  if (spheres_staged) {
-    for (int s = tid; s < S; s += blockDim.x) {
-      s_sph[s] = reinterpret_cast<const float4 *>(a.robot_spheres)[s];
-      s_sph_link[s] = a.link_sphere_map[s];
-    }
-  }
+  if (spheres_staged) stage_sphere_table(s_sph, s_sph_link, a, tid);
   __syncthreads();
   // ---- phase 1: sin/cos of every (point, jointed link), all lanes, LDS to LDS
   {
@@ -300,14 +307,10 @@ __global__ void __launch_bounds__(256) fk_forward_points_kernel(const FkArgs a) 
       if (sp >= S) { sp -= S; pt++; }
     }
   }
-  // tool-frame poses (reference :270-301), quaternion written wxyz
+  // tool-frame poses
   for (int e = tid; e < npts * T; e += blockDim.x) {
     const int pt = e / T, t = e - pt * T;
-    const float *Cm = cumul + ((size_t)pt * L + a.tool_frame_map[t]) * 12;
-    const float4 qx = quat_from_transform(Cm);
-    reinterpret_cast<float4 *>(a.link_quat)[(size_t)pt0 * T + e] = make_float4(qx.w, qx.x, qx.y, qx.z);
-    float *p = a.link_pos + ((size_t)pt0 * T + e) * 3;
-    p[0] = Cm[3]; p[1] = Cm[7]; p[2] = Cm[11];
+    write_tool_pose(a, cumul + ((size_t)pt * L + a.tool_frame_map[t]) * 12, (size_t)pt0 * T + e);
   }
 }
 
@@ -339,26 +342,48 @@ struct FkBwdArgs {
   int psum_rows;      // joint-gradient rows per point in LDS (16 = one per lane; fewer: lanes share rows through ds_add_f32)
 };
 
+// A work unit of the per-link sphere pass is one word: link | first sphere << kUnitLinkBits | end sphere << (kUnitLinkBits +
+// kUnitSphereBits); the launcher takes the per-link form only for robots whose link and sphere counts fit these fields.
+constexpr int kUnitLinkBits = 8, kUnitSphereBits = 12;
+constexpr int kUnitLinkMask = (1 << kUnitLinkBits) - 1, kUnitSphereMask = (1 << kUnitSphereBits) - 1;
+
+// dynamic LDS of fk_backward_kernel (offsets and total in floats); staged: with the tables and the gradient slab of the
+// per-link form of the sphere pass
+struct FkBackwardLayout { int cumul, psum, chain_off, link_info, sign, chain, start, units, meta, rs, g, sph_link, total; };
+__host__ __device__ inline FkBackwardLayout fk_backward_layout(int pts, int L, int rows, int dpad, int chain_len, int S,
+                                                               bool staged) {
+  FkBackwardLayout f{};
+  LdsCarver c;
+  f.cumul = c.take(pts * L * 12);      // [pts][L][12]
+  f.psum = c.take(pts * rows * dpad);  // [pts][rows][dpad]
+  // the small tables are packed words (their offsets stay plain sums of L and C: a rounded offset per table is one more
+  // scalar register held through the kernel, which has none to spare)
+  f.chain_off = c.words(L + 1); f.link_info = c.words(L); f.sign = c.words(L); f.chain = c.words(chain_len);  // [L+1] [L] [L] [C]
+  c.align();
+  f.start = c.words(staged ? L + 1 : 0);           // [L+1] first sphere of link l
+  f.units = c.words(staged ? kFkLanes + L : 0);    // work units: at most 12 + L (a link's run is cut every ceil(S / 12) spheres)
+  f.meta = c.words(staged ? 2 : 0);                // [0] #units  [1] unsorted flag
+  c.align();
+  f.rs = c.take(staged ? S * 4 : 0);       // [S] float4 robot spheres (one env)
+  f.g = c.take(staged ? pts * S * 4 : 0);  // [pts][S] float4 sphere gradients
+  f.sph_link = c.take(staged ? S : 0);     // [S]
+  f.total = c.o;
+  return f;
+}
+
 template <bool COM>
 __global__ void __launch_bounds__(256) fk_backward_kernel(const FkBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int L = a.nlinks, D = a.njoints;
+  const int L = a.nlinks, D = a.njoints, S = a.nspheres, R = a.psum_rows;
   const int pts = blockDim.x / kFkLanes;
-  float *cumul = smem;                          // [pts][L][12]
-  const int R = a.psum_rows;
-  float *psum_all = smem + pts * L * 12;        // [pts][R][dpad]
-  int *s_chain_off = reinterpret_cast<int *>(psum_all + pts * R * a.dpad);  // [L+1]
-  int *s_link_info = s_chain_off + (L + 1);                                        // [L]
-  float *s_sign = reinterpret_cast<float *>(s_link_info + L);                      // [L]
-  int *s_chain = reinterpret_cast<int *>(s_sign + L);                              // [C]
+  const FkBackwardLayout lay = fk_backward_layout(pts, L, R, a.dpad, a.chain_len, S, a.stage_spheres != 0);
+  float *cumul = smem + lay.cumul, *psum_all = smem + lay.psum, *s_sign = smem + lay.sign;
+  int *s_chain_off = lds_at<int>(smem, lay.chain_off), *s_link_info = lds_at<int>(smem, lay.link_info);
+  int *s_chain = lds_at<int>(smem, lay.chain);
   // per-link form of the sphere pass (see below)
-  const int S = a.nspheres;
-  int *s_start = s_chain + a.chain_len;                                            // [L+1] first sphere of link l
-  int *s_units = s_start + (L + 1);                                                // [kFkLanes + L] work units
-  int *s_meta = s_units + (kFkLanes + L);                                          // [0] #units  [1] unsorted flag
-  float4 *s_rs = reinterpret_cast<float4 *>(smem + (((s_meta + 2) - reinterpret_cast<int *>(smem) + 3) & ~3));  // [S]
-  float4 *s_g = s_rs + S;                                                          // [pts][S] sphere gradients
-  int *s_sph_link = reinterpret_cast<int *>(s_g + (size_t)pts * S);                // [S]
+  int *s_start = lds_at<int>(smem, lay.start), *s_units = lds_at<int>(smem, lay.units), *s_meta = lds_at<int>(smem, lay.meta);
+  float4 *s_rs = lds_at<float4>(smem, lay.rs), *s_g = lds_at<float4>(smem, lay.g);
+  int *s_sph_link = lds_at<int>(smem, lay.sph_link);
   const int tid = threadIdx.x;
   const int pt0 = blockIdx.x * pts;
   const int npts = min(pts, a.n_points - pt0);
@@ -387,7 +412,7 @@ __global__ void __launch_bounds__(256) fk_backward_kernel(const FkBwdArgs a) {
                     a.grad_spheres_b ? reinterpret_cast<const float4 *>(a.grad_spheres_b) + (size_t)pt0 * S : nullptr,
                     npts * S, tid, nt);
   s_chain_off[iL1] = r_off;
-  s_link_info[iL] = (r_jt + 1) | ((r_jm < 0 ? 0 : r_jm) << 8);
+  s_link_info[iL] = link_info_pack(r_jt, r_jm);
   s_sign[iL] = r_sign;
   s_chain[iC] = r_chain;
   if (staged) {
@@ -398,7 +423,7 @@ __global__ void __launch_bounds__(256) fk_backward_kernel(const FkBwdArgs a) {
   // (tables longer than the workgroup: the remaining rounds)
   for (int l = tid + nt; l <= L; l += nt) s_chain_off[l] = a.link_chain_offsets[l];
   for (int l = tid + nt; l < L; l += nt) {
-    s_link_info[l] = ((int)a.joint_map_type[l] + 1) | ((int)(a.joint_map[l] < 0 ? 0 : a.joint_map[l]) << 8);
+    s_link_info[l] = link_info_pack(a.joint_map_type[l], a.joint_map[l]);
     s_sign[l] = a.joint_offset[2 * l];
   }
   for (int c = tid + nt; c < a.chain_len; c += nt) s_chain[c] = a.link_chain_data[c];
@@ -438,7 +463,8 @@ __global__ void __launch_bounds__(256) fk_backward_kernel(const FkBwdArgs a) {
         if (tid >= off) incl += up;
       }
       const int at = carry + incl - nu;
-      for (int k = 0; k < nu; k++) s_units[at + k] = l | ((b + k * cs) << 8) | (min(b + (k + 1) * cs, e) << 20);
+      for (int k = 0; k < nu; k++)
+        s_units[at + k] = l | ((b + k * cs) << kUnitLinkBits) | (min(b + (k + 1) * cs, e) << (kUnitLinkBits + kUnitSphereBits));
       carry += __shfl(incl, kWave - 1, kWave);
     }
     if (tid == 0) s_meta[0] = carry;
@@ -463,7 +489,8 @@ __global__ void __launch_bounds__(256) fk_backward_kernel(const FkBwdArgs a) {
     const int U = s_meta[0];
     for (int u = lane; u < U; u += kFkLanes) {
       const int unit = s_units[u];
-      const int l = unit & 0xff, sb = (unit >> 8) & 0xfff, se = (unit >> 20) & 0xfff;
+      const int l = unit & kUnitLinkMask, sb = (unit >> kUnitLinkBits) & kUnitSphereMask;
+      const int se = (unit >> (kUnitLinkBits + kUnitSphereBits)) & kUnitSphereMask;
       const float *C = my_cumul + l * 12;
       f3 F = make_f3(0.f, 0.f, 0.f), T = make_f3(0.f, 0.f, 0.f);
       for (int sp = sb; sp < se; sp++) {
@@ -513,30 +540,7 @@ __global__ void __launch_bounds__(256) fk_backward_kernel(const FkBwdArgs a) {
     if (g.x == 0.f && g.y == 0.f && g.z == 0.f && gq.x == 0.f && gq.y == 0.f && gq.z == 0.f && gq.w == 0.f) continue;
     const int l = a.tool_frame_map[t];
     const float *C = my_cumul + l * 12;
-    const float4 qx = quat_from_transform(C);
-    const f3 pos = make_f3(C[3], C[7], C[11]);
-    // omega = 0.5 * E(q)^T g  (reference quaternion_util.cuh:86-102; q xyzw, g wxyz)
-    const float dqw = gq.x, dqx = gq.y, dqy = gq.z, dqz = gq.w;
-    const f3 om = make_f3(0.5f * (-qx.x * dqw + qx.w * dqx + qx.z * dqy - qx.y * dqz),
-                          0.5f * (-qx.y * dqw - qx.z * dqx + qx.w * dqy + qx.x * dqz),
-                          0.5f * (-qx.z * dqw + qx.y * dqx - qx.x * dqy + qx.w * dqz));
-    const int cs = s_chain_off[l], ce = s_chain_off[l + 1];
-    for (int ci = cs + lane; ci < ce; ci += kFkLanes) {
-      const int j = s_chain[ci];
-      const int info = s_link_info[j];
-      const int jt = (info & 0xff) - 1;
-      if (jt < J_X_PRISM) continue;
-      const float sign = s_sign[j];
-      const float *Cj = my_cumul + j * 12;
-      const int ax = jt >= J_X_ROT ? jt - J_X_ROT : jt;
-      const f3 axis = make_f3(Cj[ax], Cj[4 + ax], Cj[8 + ax]);
-      float r;
-      if (jt >= J_X_ROT)
-        r = dot(sign * g, cross(axis, pos - make_f3(Cj[3], Cj[7], Cj[11]))) + sign * dot(axis, om);
-      else
-        r = sign * dot(axis, g);
-      atomicAdd(&psum[info >> 8], r);
-    }
+    chain_pose_vjp_lanes(psum, my_cumul, tb, l, link_origin(C), g, quat_rate_to_omega(quat_from_transform(C), gq), lane);
   }
   // ---- geometric-Jacobian output: grad_q[i] += sum_k <grad_J[:, k], dJ[:, k] / dq_i> (reference JAC_GRAD,
   // kinematics_jacobian_backward_helper.cuh:19-300).  Column k of tool frame t is (a_k x (p_ee - p_k), a_k) for a
@@ -551,34 +555,32 @@ __global__ void __launch_bounds__(256) fk_backward_kernel(const FkBwdArgs a) {
     for (int t = 0; t < a.n_tool_frames; t++) {
       const int tl = a.tool_frame_map[t];
       const float *E = my_cumul + tl * 12;
-      const f3 pe = make_f3(E[3], E[7], E[11]);
+      const f3 pe = link_origin(E);
       const int cs = s_chain_off[tl], ce = s_chain_off[tl + 1];
       const float *gJ = a.grad_jacobian + ((size_t)n * a.n_tool_frames + t) * 6 * D;
       for (int pi = cs + lane; pi < ce; pi += kFkLanes) {
         const int li = s_chain[pi];
         const int info_i = s_link_info[li];
-        const int jt_i = (info_i & 0xff) - 1;
+        const int jt_i = link_joint_type(info_i);
         if (jt_i < J_X_PRISM || li == 0) continue;
         const float *Ci = my_cumul + li * 12;
-        const int ax_i = jt_i >= J_X_ROT ? jt_i - J_X_ROT : jt_i;
-        const f3 a_i = s_sign[li] * make_f3(Ci[ax_i], Ci[4 + ax_i], Ci[8 + ax_i]);
-        const f3 p_i = make_f3(Ci[3], Ci[7], Ci[11]);
+        const f3 a_i = s_sign[li] * joint_axis(Ci, jt_i);
+        const f3 p_i = link_origin(Ci);
         float r = 0.0f;
         for (int pk = cs; pk < ce; pk++) {
           const int lk = s_chain[pk];
           const int info_k = s_link_info[lk];
-          const int jt_k = (info_k & 0xff) - 1;
+          const int jt_k = link_joint_type(info_k);
           if (jt_k < J_X_PRISM || lk == 0) continue;
-          const int k = info_k >> 8;
+          const int k = link_joint_index(info_k);
           const f3 gv = make_f3(gJ[0 * D + k], gJ[1 * D + k], gJ[2 * D + k]);
           const f3 gw = make_f3(gJ[3 * D + k], gJ[4 * D + k], gJ[5 * D + k]);
           if (gv.x == 0.f && gv.y == 0.f && gv.z == 0.f && gw.x == 0.f && gw.y == 0.f && gw.z == 0.f) continue;
           const float *Ck = my_cumul + lk * 12;
-          const int ax_k = jt_k >= J_X_ROT ? jt_k - J_X_ROT : jt_k;
-          const f3 a_k = s_sign[lk] * make_f3(Ck[ax_k], Ck[4 + ax_k], Ck[8 + ax_k]);
+          const f3 a_k = s_sign[lk] * joint_axis(Ck, jt_k);
           const bool before = pi < pk;
           if (jt_k >= J_X_ROT) {
-            const f3 p_k = make_f3(Ck[3], Ck[7], Ck[11]);
+            const f3 p_k = link_origin(Ck);
             if (jt_i >= J_X_ROT) {
               if (before) {
                 const f3 dw = cross(a_i, a_k), ek = pe - p_k;
@@ -593,7 +595,7 @@ __global__ void __launch_bounds__(256) fk_backward_kernel(const FkBwdArgs a) {
             r += dot(gv, cross(a_i, a_k));
           }
         }
-        if (r != 0.0f) atomicAdd(&psum[info_i >> 8], r);
+        if (r != 0.0f) atomicAdd(&psum[link_joint_index(info_i)], r);
       }
     }
   }
@@ -644,12 +646,12 @@ static int fk_forward_dispatch(const FkArgs &a, bool spheres, bool jac, bool com
   CUROBO_REQUIRE(a.n_points >= 0 && a.horizon >= 1, "%s: bad batch_size/horizon", what);
   CUROBO_REQUIRE(a.njoints >= 1, "%s: n_joints must be >= 1", what);
   if (a.n_points == 0) return CUROBO_HIP_OK;
-  static const bool grouped_only = getenv("CUROBO_HIP_FK_GROUPED") != nullptr;
+  const int S = spheres ? a.nspheres : 0;
   const size_t lds_pts = (size_t)kFkPts * a.nlinks * (12 * sizeof(float) + sizeof(float2)) +
                          (size_t)a.nlinks * (8 * sizeof(float4) + sizeof(int4) + sizeof(float2) + sizeof(int)) + 16 +
                          (size_t)kFkPts * a.njoints * sizeof(float) +
                          (spheres ? (size_t)(a.nspheres + 4) * (sizeof(float4) + sizeof(int)) : 0);
-  if (!jac && !com && !grouped_only && lds_pts <= 80 * 1024 && a.nlinks <= kWave) {  // (two workgroups per CU)
+  if (!jac && !com && lds_pts <= 80 * 1024 && a.nlinks <= kWave) {  // (two workgroups per CU)
     const int nblk = ceil_div(a.n_points, kFkPts);
     if (spheres && write_cumul) hipLaunchKernelGGL((fk_forward_points_kernel<true, true>), dim3(nblk), dim3(256), lds_pts, st, a);
     else if (spheres) hipLaunchKernelGGL((fk_forward_points_kernel<true, false>), dim3(nblk), dim3(256), lds_pts, st, a);
@@ -657,16 +659,11 @@ static int fk_forward_dispatch(const FkArgs &a, bool spheres, bool jac, bool com
     else hipLaunchKernelGGL((fk_forward_points_kernel<false, false>), dim3(nblk), dim3(256), lds_pts, st, a);
     return check_launch(what, st);
   }
-  static const int env_pts = getenv("CUROBO_FK_FWD_PTS") ? atoi(getenv("CUROBO_FK_FWD_PTS")) : 0;
-  auto lds_for = [&](int p) {
-    return (size_t)p * a.nlinks * kFkLinkStride * sizeof(float) + (size_t)a.nlinks * sizeof(int) +
-           (spheres ? (size_t)a.nspheres * (sizeof(float4) + sizeof(int)) : 0);
-  };
+  auto lds_for = [&](int p) { return (size_t)fk_grouped_layout(p, a.nlinks, S).total * sizeof(float); };
   int pts = fk_points_per_block(a.nlinks);
   // every workgroup stages the sphere table: with many spheres (G1: 13.5 KB) twice the points per workgroup hold more
   // wavefronts per CU in the same LDS (two workgroups of 16 points instead of three of 8: 151 -> 145 us at the C4 size)
   if (spheres && pts == 8 && lds_for(16) <= 80 * 1024) pts = 16;
-  if (env_pts > 0) pts = env_pts;
   const int threads = pts * kFkLanes;
   const int blocks = ceil_div(a.n_points, pts);
   const size_t lds = lds_for(pts);
@@ -789,31 +786,21 @@ CUROBO_EXPORT int curobo_hip_launch_kinematics_backward(
   // 8 points per workgroup where 16 would fit: twice the workgroups, whose load and arithmetic phases then overlap
   // a little more (24.6 -> 23.5 us at 32 k points)
   int pts = max(4, fk_points_per_block(num_links) / 2);
-  static const int env_rows = getenv("CUROBO_FK_BWD_ROWS") ? atoi(getenv("CUROBO_FK_BWD_ROWS")) : 0;
-  static const int env_pts = getenv("CUROBO_FK_BWD_PTS") ? atoi(getenv("CUROBO_FK_BWD_PTS")) : 0;
   // One gradient row per lane costs 16 * dof floats of LDS per point: with many joints that, not the wavefront slots, is what
   // limits the points a CU holds (Unitree G1, 49 joints: 6.1 KB per point = 6.5 wavefronts per CU).  Four rows shared by the
   // lanes through ds_add_f32 make it 3.5 KB (G1 at the C4 size, sparse sphere gradient + four tool frames: 314 -> 194 us);
   // robots with few joints keep a private row per lane (no LDS pressure, no shared-address adds).
-  a.psum_rows = env_rows > 0 ? env_rows : (a.dpad > 16 ? 4 : kFkLanes);
+  a.psum_rows = a.dpad > 16 ? 4 : kFkLanes;
   if (a.psum_rows < kFkLanes) pts = fk_points_per_block(num_links);
-  if (env_pts > 0) pts = env_pts;
-  size_t lds = 0;
-  for (;;) {
-    lds = ((size_t)pts * num_links * 12 + (size_t)pts * a.psum_rows * a.dpad + 3 * (size_t)num_links + 1 +
-           (size_t)a.chain_len) * sizeof(float);
-    if (lds <= 60 * 1024 || pts == 4) break;
-    pts /= 2;
-  }
-  {  // + the tables and the gradient slab of the per-link sphere pass, when they leave >= 3 workgroups per CU
-    const size_t S = (size_t)a.nspheres;
-    const size_t extra = ((size_t)2 * num_links + kFkLanes + 8) * sizeof(int) + (S + 4) * (sizeof(int) + sizeof(float4)) +
-                         (size_t)pts * S * sizeof(float4) + 16;
-    a.stage_spheres = S > 0 && S < 4096 && num_links < 256 && lds + extra <= 48 * 1024;
-    if (a.stage_spheres) lds += extra;
-  }
-  static const bool per_sphere_only = getenv("CUROBO_HIP_FK_BWD_PER_SPHERE") != nullptr;
-  if (per_sphere_only) a.stage_spheres = 0;
+  auto lds_for = [&](int p, bool staged) {
+    return (size_t)fk_backward_layout(p, num_links, a.psum_rows, a.dpad, a.chain_len, a.nspheres, staged).total * sizeof(float);
+  };
+  while (pts > 4 && lds_for(pts, false) > 60 * 1024) pts /= 2;
+  // + the tables and the gradient slab of the per-link sphere pass, when they leave >= 3 workgroups per CU and the work-unit
+  // word holds the robot's link and sphere counts
+  a.stage_spheres = a.nspheres > 0 && a.nspheres < (1 << kUnitSphereBits) && num_links < (1 << kUnitLinkBits) &&
+                    lds_for(pts, true) <= 48 * 1024;
+  const size_t lds = lds_for(pts, a.stage_spheres != 0);
   CUROBO_REQUIRE(lds <= 64 * 1024, "%s: robot too large for the LDS tiling (%zu bytes)", what, lds);
   const int threads = pts * kFkLanes;
   const int blocks = ceil_div(batch_size, threads / kFkLanes);

@@ -214,8 +214,9 @@ __global__ void __launch_bounds__(256) seed_ik_update_kernel(const SeedIkUpdateA
 // accepted Jacobian [6T + D][D], the normal matrix, q, J^T e, the 13 link transforms of the candidate -- and
 // the row runs `iterations` iterations back to back; global memory sees the state once on the way in and once
 // on the way out.  Same arithmetic per stage as the stand-alone kernels (shared device functions:
-// fk_chain_16, tool_pose_distance_point, seed_ik_update_row); J^T J is contracted on the matrix cores here too
-// (a wavefront takes the Jacobians of its four rows in turn), the D x D system is then solved in registers.
+// fk_chain_16_multi, joint_axis, tool_pose_distance_point, chain_pose_vjp_lanes, seed_ik_update_row); J^T J is
+// contracted on the matrix cores here too (a wavefront takes the Jacobians of its four rows in turn), the D x D
+// system is then solved in registers.
 struct SeedIkSolveArgs {
   SeedIkUpdateArgs u;  // state pointers and parameters (u.cand_q = the seeds when u.initial; other u.cand_* unused)
   ToolPoseArgs tp;     // goal set, weights (current_* / out_* unused)
@@ -230,18 +231,63 @@ struct SeedIkSolveArgs {
   int32_t *blocks_run;
 };
 
-__host__ __device__ inline int seed_ik_row_floats(int D, int T, int L) {
-  const int R = 6 * T + D;
-  // J | A [D][D+1] | q | q_cand | jTe | cand jTe | cand J | cumul | locals | pose (2T + T + T + 3T + 4T) | scalars + flags (8) | bcast (16)
-  return R * D + D * (D + 1) + 4 * D + 6 * T * D + L * 12 + L * 16 + 11 * T + 8 + 16;
+// dynamic LDS of one 256-thread workgroup of seed_ik_solve_kernel (offsets and sizes in floats): the robot tables shared
+// by the workgroup, then from `rows` on 16 rows of per-problem state of `row` floats each; the fields from J to bc are
+// offsets INTO a row
+constexpr int kSeedIkLdsLimit = 64 * 1024;
+constexpr int kSeedIkRows = 256 / kRow;
+static_assert(kRow == kFkLanes, "the seed-IK row runs fk_device.hpp's 16-lane walks");
+struct SeedIkLayout {
+  int parent, info, sign, choff, chain, rows, total;
+  int J, A, q, qc, jte, cjte, cJ, cumul, locals, pose_cost, pos_dist, rot_dist, gpos, gquat, scal, bc, row;
+};
+__host__ __device__ constexpr SeedIkLayout seed_ik_layout(int D, int T, int L, int chain_len) {
+  SeedIkLayout f{};
+  LdsCarver c;
+  // the robot tables are packed words: offsets that are plain sums of L stay cheap to recompute, where a rounded offset
+  // per table is a scalar register held through the whole iteration loop, and that kernel spills already
+  f.parent = c.words(L); f.info = c.words(L); f.sign = c.words(L);  // link_map, link-info words, axis sign x mimic multiplier
+  f.choff = c.words(L + 1); f.chain = c.words(chain_len);           // chain offsets [L+1], chain links [C]
+  c.align();
+  f.rows = c.o;
+  LdsCarver r;
+  // the two regions whose size depends on L come last: every other offset is a compile-time constant in the
+  // instantiations with fixed D and T
+  f.J = r.take((6 * T + D) * D);  // accepted Jacobian [6T + D][D]
+  f.A = r.take(D * (D + 1));      // normal matrix [D][D+1]
+  f.q = r.take(D); f.qc = r.take(D);       // q and the candidate's
+  f.jte = r.take(D); f.cjte = r.take(D);   // J^T e and the candidate's
+  f.cJ = r.take(6 * T * D);       // candidate pose Jacobian
+  f.pose_cost = r.words(2 * T); f.pos_dist = r.words(T); f.rot_dist = r.words(T);  // pose cost, position / rotation distance
+  f.gpos = r.words(3 * T); f.gquat = r.words(4 * T);                               // position / quaternion-rate gradient
+  r.align();
+  f.scal = r.take(8);             // [0] error_norm [1] pos_err [2] ori_err [3] lambda [4] pred; the two flag bytes at [6]
+  f.bc = r.take(16);              // row broadcast scratch
+  f.cumul = r.take(L * 12);       // the candidate's link transforms
+  f.locals = r.take(L * 16);      // its local transforms, float4 columns: written and read as 16-byte words
+  f.row = r.o;
+  f.total = f.rows + kSeedIkRows * f.row;
+  return f;
 }
 
-// dynamic LDS of one 256-thread workgroup of seed_ik_solve_kernel: the shared robot tables + 16 rows of per-problem state
-constexpr int kSeedIkLdsLimit = 64 * 1024;
-__host__ inline size_t seed_ik_iterate_lds(int D, int T, int L, int chain_len) {
-  const int rows = 256 / kRow;
-  return ((size_t)((4 * L + 1 + chain_len + 3) & ~3) + (size_t)rows * ((seed_ik_row_floats(D, T, L) + 3) & ~3)) * sizeof(float);
+// `locals` is accessed through float4 (local_transform_from_sincos, fk_chain_16_multi): it starts on a multiple of 4 floats
+// in every row, whatever the sizes in front of it
+constexpr bool seed_ik_locals_aligned() {
+  const int Ls[] = {1, 2, 7, 10, 13, 31, 64};
+  for (int D = 1; D <= kRow; D++)
+    for (int T = 1; T <= 4; T++)
+      for (int L : Ls)
+        for (int C = L; C <= L + 3; C++) {
+          const SeedIkLayout f = seed_ik_layout(D, T, L, C);
+          if ((f.rows | f.row | f.locals) & 3) return false;
+        }
+  return true;
 }
+static_assert(seed_ik_locals_aligned(), "seed_ik_layout: locals is not 16-byte aligned");
+// the four workgroups per CU (160 KiB of LDS) that the solve kernel's launch bounds are written for, at the packaged
+// franka (D 7, T 1, 13 links, chain data of 88) and ur10e (D 6, T 1, 10 links, 55)
+static_assert(4 * seed_ik_layout(7, 1, 13, 88).total * sizeof(float) <= 160 * 1024, "seed_ik_layout: franka, < 4 workgroups per CU");
+static_assert(4 * seed_ik_layout(6, 1, 10, 55).total * sizeof(float) <= 160 * 1024, "seed_ik_layout: ur10e, < 4 workgroups per CU");
 
 #define SEED_ROW_SYNC()                                         \
   do {                                                          \
@@ -263,22 +309,20 @@ __global__ void __launch_bounds__(256, 4) seed_ik_solve_kernel(const SeedIkSolve
   const int row = blockIdx.x * (blockDim.x / kRow) + rowi;
   const bool live = row < u.n;
   const int p = live ? row : u.n - 1;
-  // robot tables shared by the rows: parent, (joint type + 1) | joint << 8, axis sign, chain offsets, chain links
-  int *s_parent = reinterpret_cast<int *>(smem);
-  int *s_info = s_parent + L;
-  float *s_sign = reinterpret_cast<float *>(s_info + L);
-  int *s_choff = reinterpret_cast<int *>(s_sign + L);
-  int *s_chain = s_choff + (L + 1);
-  float *base = smem + ((4 * L + 1 + a.chain_len + 3) & ~3) + (size_t)rowi * ((seed_ik_row_floats(D, T, L) + 3) & ~3);
-  float *sJ = base, *sA = sJ + R * D, *sq = sA + D * LD, *sqc = sq + D, *sjte = sqc + D, *scjte = sjte + D;
-  float *scJ = scjte + D, *cumul = scJ + 6 * T * D, *locals = cumul + L * 12, *pose = locals + L * 16;
-  float *pose_cost = pose, *pos_dist = pose + 2 * T, *rot_dist = pos_dist + T, *gpos = rot_dist + T, *gquat = gpos + 3 * T;
-  float *scal = gquat + 4 * T;  // [0] error_norm [1] pos_err [2] ori_err [3] lambda [4] pred; flags behind
+  const SeedIkLayout lay = seed_ik_layout(D, T, L, a.chain_len);
+  int *s_parent = lds_at<int>(smem, lay.parent), *s_info = lds_at<int>(smem, lay.info), *s_choff = lds_at<int>(smem, lay.choff);
+  int *s_chain = lds_at<int>(smem, lay.chain);
+  float *s_sign = smem + lay.sign;
+  const BwdTables tb{s_chain, s_choff, s_info, s_sign};
+  float *base = smem + lay.rows + (size_t)rowi * lay.row;
+  float *sJ = base + lay.J, *sA = base + lay.A, *sq = base + lay.q, *sqc = base + lay.qc, *sjte = base + lay.jte;
+  float *scjte = base + lay.cjte, *scJ = base + lay.cJ, *cumul = base + lay.cumul, *locals = base + lay.locals;
+  float *pose_cost = base + lay.pose_cost, *pos_dist = base + lay.pos_dist, *rot_dist = base + lay.rot_dist;
+  float *gpos = base + lay.gpos, *gquat = base + lay.gquat, *scal = base + lay.scal, *bc = base + lay.bc;
   uint8_t *flags = reinterpret_cast<uint8_t *>(scal + 6);
-  float *bc = scal + 8;  // [16] row broadcast scratch
   for (int l = tid; l < L; l += blockDim.x) {
     s_parent[l] = a.link_map[l];
-    s_info[l] = ((int)a.joint_map_type[l] + 1) | ((int)(a.joint_map[l] < 0 ? 0 : a.joint_map[l]) << 8);
+    s_info[l] = link_info_pack(a.joint_map_type[l], a.joint_map[l]);
     s_sign[l] = a.joint_offset[2 * l];
   }
   for (int l = tid; l <= L; l += blockDim.x) s_choff[l] = a.link_chain_offsets[l];
@@ -310,12 +354,12 @@ __global__ void __launch_bounds__(256, 4) seed_ik_solve_kernel(const SeedIkSolve
       // row's normal matrix.  Same accumulation order as the stand-alone kernel: identical J^T J.
       {
         const int lane64 = tid & 63, kk = lane64 >> 4, col = lane64 & 15;
-        const size_t row_stride = (size_t)((seed_ik_row_floats(D, T, L) + 3) & ~3);
+        const size_t row_stride = (size_t)lay.row;
         float *wave_base = base - (size_t)(rowi & 3) * row_stride;  // row 0 of this wavefront
 #pragma unroll
         for (int rr = 0; rr < 4; rr++) {
-          const float *Jr = wave_base + rr * row_stride;
-          float *Ar = wave_base + rr * row_stride + R * D;
+          const float *Jr = wave_base + rr * row_stride + lay.J;
+          float *Ar = wave_base + rr * row_stride + lay.A;
           f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
           for (int k0 = 0; k0 < R; k0 += 4) {
             const int r = k0 + kk;
@@ -416,8 +460,8 @@ __global__ void __launch_bounds__(256, 4) seed_ik_solve_kernel(const SeedIkSolve
     // ---- FK of the candidate on the row (kinematics_forward_helper.cuh:316-512)
     for (int l = lane; l < L; l += kRow) {
       const int info = s_info[l];
-      const int jt = (info & 0xff) - 1;
-      const float qv = jt != J_FIXED ? sqc[info >> 8] : 0.0f;
+      const int jt = link_joint_type(info);
+      const float qv = jt != J_FIXED ? sqc[link_joint_index(info)] : 0.0f;
       local_transform_colmajor(locals + l * 16, a.fixed_transform + l * 12, jt, qv, s_sign[l], a.joint_offset[2 * l + 1]);
     }
     for (int d = lane; d < D; d += kRow) scjte[d] = 0.0f;
@@ -435,26 +479,24 @@ __global__ void __launch_bounds__(256, 4) seed_ik_solve_kernel(const SeedIkSolve
     for (int t = 0; t < T; t++) {
       const int tl = a.tool_frame_map[t];
       const float *E = cumul + tl * 12;
-      const f3 ee = make_f3(E[3], E[7], E[11]);
+      const f3 ee = link_origin(E);
       const int cs = s_choff[tl], ce = s_choff[tl + 1];
       for (int ci = cs + lane; ci < ce; ci += kRow) {
         const int li = s_chain[ci];
         const int info = s_info[li];
-        const int jt = (info & 0xff) - 1;
+        const int jt = link_joint_type(info);
         if (li == 0 || jt < J_X_PRISM) continue;
-        const int j = info >> 8;
+        float *col = scJ + (t * 6) * D + link_joint_index(info);
         const float *C = cumul + li * 12;
         const float sign = s_sign[li];
-        float *col = scJ + (t * 6) * D + j;
         if (jt >= J_X_ROT) {
-          const int ax = jt - J_X_ROT;
-          const f3 axis = sign * make_f3(C[ax], C[4 + ax], C[8 + ax]);
-          const f3 lin = cross(axis, ee - make_f3(C[3], C[7], C[11]));
+          const f3 axis = sign * joint_axis(C, jt);
+          const f3 lin = cross(axis, ee - link_origin(C));
           atomicAdd(col, lin.x); atomicAdd(col + D, lin.y); atomicAdd(col + 2 * D, lin.z);
           atomicAdd(col + 3 * D, axis.x); atomicAdd(col + 4 * D, axis.y); atomicAdd(col + 5 * D, axis.z);
         } else {
-          const int ax = jt - J_X_PRISM;
-          atomicAdd(col, sign * C[ax]); atomicAdd(col + D, sign * C[4 + ax]); atomicAdd(col + 2 * D, sign * C[8 + ax]);
+          const f3 axis = sign * joint_axis(C, jt);
+          atomicAdd(col, axis.x); atomicAdd(col + D, axis.y); atomicAdd(col + 2 * D, axis.z);
         }
       }
     }
@@ -462,7 +504,7 @@ __global__ void __launch_bounds__(256, 4) seed_ik_solve_kernel(const SeedIkSolve
     for (int t = lane; t < T; t += kRow) {
       const float *C = cumul + a.tool_frame_map[t] * 12;
       const float4 qx = quat_from_transform(C);
-      const ToolPoseResult r = tool_pose_distance_point(a.tp, p, 0, t, make_f3(C[3], C[7], C[11]), make_float4(qx.w, qx.x, qx.y, qx.z));
+      const ToolPoseResult r = tool_pose_distance_point(a.tp, p, 0, t, link_origin(C), make_float4(qx.w, qx.x, qx.y, qx.z));
       pose_cost[2 * t] = r.position_cost; pose_cost[2 * t + 1] = r.rotation_cost;
       pos_dist[t] = r.position_distance; rot_dist[t] = r.rotation_distance;
       gpos[3 * t] = r.position_gradient.x; gpos[3 * t + 1] = r.position_gradient.y; gpos[3 * t + 2] = r.position_gradient.z;
@@ -473,30 +515,11 @@ __global__ void __launch_bounds__(256, 4) seed_ik_solve_kernel(const SeedIkSolve
     // ---- J^T e of the pose error through the chain (kinematics_backward_helper.cuh:102-183)
     for (int t = 0; t < T; t++) {
       const f3 g = make_f3(gpos[3 * t], gpos[3 * t + 1], gpos[3 * t + 2]);
-      const float dqw = gquat[4 * t], dqx = gquat[4 * t + 1], dqy = gquat[4 * t + 2], dqz = gquat[4 * t + 3];
-      if (g.x == 0.f && g.y == 0.f && g.z == 0.f && dqw == 0.f && dqx == 0.f && dqy == 0.f && dqz == 0.f) continue;
+      const float4 gq = make_float4(gquat[4 * t], gquat[4 * t + 1], gquat[4 * t + 2], gquat[4 * t + 3]);
+      if (g.x == 0.f && g.y == 0.f && g.z == 0.f && gq.x == 0.f && gq.y == 0.f && gq.z == 0.f && gq.w == 0.f) continue;
       const int l = a.tool_frame_map[t];
       const float *C = cumul + l * 12;
-      const float4 qx = quat_from_transform(C);
-      const f3 pos = make_f3(C[3], C[7], C[11]);
-      const f3 om = make_f3(0.5f * (-qx.x * dqw + qx.w * dqx + qx.z * dqy - qx.y * dqz),
-                            0.5f * (-qx.y * dqw - qx.z * dqx + qx.w * dqy + qx.x * dqz),
-                            0.5f * (-qx.z * dqw + qx.y * dqx - qx.x * dqy + qx.w * dqz));
-      const int cs = s_choff[l], ce = s_choff[l + 1];
-      for (int ci = cs + lane; ci < ce; ci += kRow) {
-        const int j = s_chain[ci];
-        const int info = s_info[j];
-        const int jt = (info & 0xff) - 1;
-        if (jt < J_X_PRISM) continue;
-        const float sign = s_sign[j];
-        const float *Cj = cumul + j * 12;
-        const int ax = jt >= J_X_ROT ? jt - J_X_ROT : jt;
-        const f3 axis = make_f3(Cj[ax], Cj[4 + ax], Cj[8 + ax]);
-        float r;
-        if (jt >= J_X_ROT) r = dot(sign * g, cross(axis, pos - make_f3(Cj[3], Cj[7], Cj[11]))) + sign * dot(axis, om);
-        else r = sign * dot(axis, g);
-        atomicAdd(&scjte[info >> 8], r);
-      }
+      chain_pose_vjp_lanes(scjte, cumul, tb, l, link_origin(C), g, quat_rate_to_omega(quat_from_transform(C), gq), lane);
     }
     SEED_ROW_SYNC();
     // ---- trust ratio, acceptance, damping, state selection, convergence (seed_iteration_state_manager.py:74-260)
@@ -767,11 +790,10 @@ CUROBO_EXPORT int curobo_hip_seed_ik_iterate(
   a.link_chain_offsets = link_chain_offsets; a.joint_links_data = joint_links_data; a.joint_links_offsets = joint_links_offsets;
   a.joint_affects_endeffector = joint_affects_endeffector; a.L = num_links; a.iterations = iterations;
   a.chain_len = link_chain_len; a.stop_flag = stop_flag; a.blocks_run = blocks_run;
-  const int rows = 256 / kRow;
-  const size_t lds = seed_ik_iterate_lds(dof, num_tool_frames, num_links, link_chain_len);
+  const size_t lds = (size_t)seed_ik_layout(dof, num_tool_frames, num_links, link_chain_len).total * sizeof(float);
   CUROBO_REQUIRE(lds <= (size_t)kSeedIkLdsLimit, "%s: the per-problem state does not fit in LDS (%zu bytes); use the launch sequence", what, lds);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(ceil_div(num_problems, rows)), block(256);
+  const dim3 grid(ceil_div(num_problems, kSeedIkRows)), block(256);
   if (dof == 7 && num_tool_frames == 1) hipLaunchKernelGGL((seed_ik_solve_kernel<7, 1>), grid, block, lds, st, a);
   else if (dof == 6 && num_tool_frames == 1) hipLaunchKernelGGL((seed_ik_solve_kernel<6, 1>), grid, block, lds, st, a);
   else hipLaunchKernelGGL((seed_ik_solve_kernel<0, 0>), grid, block, lds, st, a);
@@ -780,7 +802,7 @@ CUROBO_EXPORT int curobo_hip_seed_ik_iterate(
 
 CUROBO_EXPORT int curobo_hip_seed_ik_iterate_fits(int dof, int num_links, int num_tool_frames, int link_chain_len) {
   if (dof < 1 || dof > 16 || num_links < 1 || num_tool_frames < 1 || link_chain_len < 0) return 0;
-  return seed_ik_iterate_lds(dof, num_tool_frames, num_links, link_chain_len) <= (size_t)kSeedIkLdsLimit ? 1 : 0;
+  return (size_t)seed_ik_layout(dof, num_tool_frames, num_links, link_chain_len).total * sizeof(float) <= (size_t)kSeedIkLdsLimit ? 1 : 0;
 }
 
 CUROBO_EXPORT int curobo_hip_seed_ik_batch_status(const uint8_t *success, int num_problems, int num_seeds, int needed,

@@ -8,10 +8,10 @@ reach only the first two, so the variants below are derived from them with ``dat
 fewer dofs, land in ``<0,0>``.
 
     case  model                                    D, T   instantiation   fused LDS
-    A     franka                                   7, 1   <7,1>           40 000 B
-    B     ur10e                                    6, 1   <6,1>           31 872 B
-    C     franka + panda_link6                     7, 2   <0,0>           46 144 B
-    D     ur10e + wrist_1_link, wrist_3_link       6, 3   <0,0>           42 368 B
+    A     franka                                   7, 1   <7,1>           40 512 B
+    B     ur10e                                    6, 1   <6,1>           32 384 B
+    C     franka + panda_link6                     7, 2   <0,0>           46 656 B
+    D     ur10e + wrist_1_link, wrist_3_link       6, 3   <0,0>           43 136 B
     E     franka, panda_joint5 / _joint7 locked    5, 1   <0,0>, D < 6    smaller than A
 """
 

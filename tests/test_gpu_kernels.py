@@ -119,6 +119,58 @@ def test_fk_backward(robot, oracle, device):
     np.testing.assert_allclose(got, ref, atol=1e-5 * max(scale, 1.0), rtol=1e-4)
 
 
+def test_fk_backward_spheres_not_grouped_by_link(oracle, device):
+    """the per-sphere form of the sphere VJP: a sphere table that is NOT grouped by link (a seeded permutation of franka's)
+    against the oracle on the same permuted table, and against the launch on the unpermuted table (which takes the
+    per-link form) with the gradient un-permuted.  17 points: three workgroups, the last with one live point."""
+    import dataclasses
+
+    from curobo_amd.backends import kinematics as K
+
+    model = load_model("franka")
+    kp = _kp(model, device)
+    n = 17
+    q = sample_q(model, n, seed=3)
+    md = dict(model.as_dict())
+    fwd = oracle.kinematics_forward(q, md, compute_com=True)
+    rng = np.random.default_rng(7)
+    S, T, d = model.num_spheres, len(model.tool_frames), model.num_dof
+    perm = rng.permutation(S)
+    link_of = np.asarray(md["link_sphere_idx_map"])
+    assert np.all(np.diff(link_of) >= 0) and np.any(np.diff(link_of[perm]) < 0)
+    spheres = np.asarray(md["link_spheres"], np.float32).reshape(1, S, 4)
+    md_p = dict(md)
+    md_p["link_spheres"] = np.ascontiguousarray(spheres[:, perm])
+    md_p["link_sphere_idx_map"] = np.ascontiguousarray(link_of[perm])
+    kp_p = dataclasses.replace(kp, link_spheres=torch.as_tensor(md_p["link_spheres"], device=device),
+                               link_sphere_idx_map=torch.as_tensor(md_p["link_sphere_idx_map"], device=device).to(torch.int16))
+    g_s = rng.normal(size=(n, S, 4)).astype(np.float32)  # gradient of the PERMUTED spheres
+    g_s[rng.uniform(size=(n, S)) < 0.6] = 0.0  # sparse, like collision gradients
+    g_p, g_q, g_c = np.zeros((n, T, 3), np.float32), np.zeros((n, T, 4), np.float32), np.zeros((n, 4), np.float32)
+    ref = oracle.kinematics_backward(md_p, fwd["cumul_mat"], g_s, g_p, g_q, g_c, fwd["com"])
+    env = torch.zeros(n, dtype=torch.int32, device=device)
+    t = lambda a: torch.as_tensor(a, device=device)  # noqa: E731
+
+    def run(p, g):
+        out = torch.zeros(n, d, device=device)
+        K.launch_kinematics_backward(
+            out, t(g_p), t(g_q), t(g), t(g_c), t(fwd["com"]), t(g_p), t(fwd["cumul_mat"]), p.link_spheres,
+            p.link_masses_com, p.link_map, p.joint_map, p.joint_map_type, p.tool_frame_map,
+            p.link_sphere_idx_map, p.link_chain_data, p.link_chain_offsets, p.joint_links_data,
+            p.joint_links_offsets, p.joint_affects_endeffector, p.joint_offset_map, env, p.num_envs, n, 1,
+            d, S, True, False)
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
+    got = run(kp_p, g_s)
+    g_unpermuted = np.zeros_like(g_s)
+    g_unpermuted[:, perm] = g_s
+    grouped = run(kp, g_unpermuted)
+    tol = dict(atol=1e-5 * max(np.abs(ref).max(), 1.0), rtol=1e-4)
+    np.testing.assert_allclose(got, ref, **tol)
+    np.testing.assert_allclose(got, grouped, **tol)
+
+
 @pytest.mark.parametrize("robot", ["franka", "unitree_g1"])
 def test_fk_sphere_sets_per_environment(robot, oracle, device):
     """two sets of robot spheres selected per batch row through env_query_idx (reference

@@ -1,5 +1,5 @@
 """FK forward (spheres + cumulative transforms) and FK VJP at the C4 size (Unitree G1, 33 792 points; argv: robot, points): us per
-launch (hipGraph replay) and checksums.  Knobs under test: CUROBO_FK_BWD_ROWS / CUROBO_FK_BWD_PTS."""
+launch (hipGraph replay) and checksums."""
 import os
 import sys
 
@@ -39,5 +39,4 @@ out = {}
 for name, fn in (("forward", fwd), ("backward", bwd)):
     gr = B_.graphed(fn, 3, torch)
     out[name] = round(B_.time_kernel(gr.replay, 3, torch, min_s=0.05) / 3, 1)
-print(os.environ.get("CUROBO_FK_BWD_ROWS", "-"), os.environ.get("CUROBO_FK_BWD_PTS", "-"), robot, n, out,
-      "checksums", f"{float(sph.abs().sum()):.6e}", f"{float(gq.abs().sum()):.6e}")
+print(robot, n, out, "checksums", f"{float(sph.abs().sum()):.6e}", f"{float(gq.abs().sum()):.6e}")
