@@ -207,14 +207,26 @@ def rollout_ik_fused(
     fixed_transform, robot_spheres, joint_map_type, joint_map, link_map, tool_frame_map, link_sphere_map,
     link_chain_data, link_chain_offsets, joint_offset_map, sphere_padding, self_collision_weight, pair_locations,
     scene: Optional[Scene], scene_collision_weight, activation_distance, batch_size: int, dof: int,
-    env_query_idx=None, num_envs: int = 1, use_multi_env: bool = False,
+    env_query_idx=None, num_envs: int = 1, use_multi_env: bool = False, squared_l2_reg_weight=None, current_position=None,
+    current_velocity=None, idxs_current_state=None, velocity_limits=None, state_dt=None,
+    acceleration_regularization: bool = False,
 ):
     """cost[b], d cost / d q [b, dof] of ``batch_size`` joint configurations against per-row goal
     poses in one launch (see ``curobo_hip_rollout_ik_fused`` in the header); optional outputs may be None.
     ``env_query_idx`` [b] (scene environment with ``use_multi_env``, sphere set with ``num_envs`` > 1) must be constant
-    over aligned runs of 16 configurations."""
+    over aligned runs of 16 configurations.
+
+    With any of the current-state arguments (``squared_l2_reg_weight`` [2], ``current_position`` / ``current_velocity``
+    [n_states, dof], ``idxs_current_state`` [b], ``velocity_limits`` [2, dof], ``state_dt`` [n_states]) the launch is
+    ``curobo_hip_rollout_ik_fused_state``: limits tightened to one time step from the row's current state and the implied
+    velocity / acceleration regularisation; ``acceleration_regularization`` says the second weight may be positive
+    (``current_velocity`` is then required)."""
     num_pairs = 0 if pair_locations is None else int(pair_locations.shape[0])
-    check(load().curobo_hip_rollout_ik_fused(
+    state = (squared_l2_reg_weight, current_position, current_velocity, idxs_current_state, velocity_limits, state_dt)
+    with_state = any(t is not None for t in state)
+    fn = load().curobo_hip_rollout_ik_fused_state if with_state else load().curobo_hip_rollout_ik_fused
+    extra = (*(ptr(t) for t in state), int(acceleration_regularization)) if with_state else ()
+    check(fn(
         ptr(out_cost), ptr(out_grad_q), ptr(out_pose_distance), ptr(out_position_distance), ptr(out_rotation_distance),
         ptr(out_goalset_idx), ptr(out_link_pos), ptr(out_link_quat), ptr(out_robot_spheres), ptr(out_cspace_cost),
         ptr(q), ptr(goal_position), ptr(goal_quat), ptr(idxs_goal), ptr(position_orientation_weight),
@@ -225,7 +237,7 @@ def rollout_ik_fused(
         ptr(self_collision_weight), ptr(pair_locations), None if scene is None else C.addressof(scene),
         ptr(scene_collision_weight), ptr(activation_distance), batch_size, dof, int(fixed_transform.shape[0]),
         int(tool_frame_map.shape[0]), int(link_sphere_map.shape[0]), num_pairs, int(link_chain_data.shape[0]),
-        ptr(env_query_idx), int(num_envs), int(use_multi_env), current_stream(out_cost),
+        ptr(env_query_idx), int(num_envs), int(use_multi_env), *extra, current_stream(out_cost),
     ))
 
 

@@ -169,6 +169,28 @@ __device__ __forceinline__ float cspace_bound_term(float cp, float pl, float pu,
   return 0.0f;
 }
 
+// joint limits tightened to what the joint can reach in dt from cur_p (wp_cspace_position.py:299-312); the caller checks dt > 0
+__device__ __forceinline__ void cspace_velocity_bounds(float &pl, float &pu, float cur_p, float v_lo, float v_hi, float dt) {
+  pl = fmaxf(pl, cur_p + v_lo * dt);
+  pu = fminf(pu, cur_p + v_hi * dt);
+}
+
+// implied velocity / acceleration regularisation w.r.t. a current state (wp_cspace_position.py:330-356): added to c and gp.
+// reg = squared_l2_reg_weight [2]; cur_v = the joint's current velocity, read only when the acceleration weight is positive
+__device__ __forceinline__ void cspace_state_regularisation(float cp, float cur_p, const float *cur_v, float dt, const float *reg,
+                                                            float &c, float &gp) {
+  const float vw = reg[0] * dt, aw = reg[1] * dt * dt;
+  if (dt > 0.0f && (vw > 0.0f || aw > 0.0f)) {
+    const float vi = (cp - cur_p) / dt;
+    if (vw > 0.0f) { c += 0.5f * vw * vi * vi; gp += vw * vi / dt; }
+    if (aw > 0.0f) {
+      const float ai = (vi - *cur_v) / dt;
+      c += 0.5f * aw * ai * ai;
+      gp += aw * ai / (dt * dt);
+    }
+  }
+}
+
 // one (batch, horizon, dof) entry, wp_cspace_position.py:232-362
 __device__ __forceinline__ float cspace_position_point(const CspacePosArgs &a, int b, int d, float cp, float ctau,
                                                        float &gp, float &gt) {
@@ -184,8 +206,7 @@ __device__ __forceinline__ float cspace_position_point(const CspacePosArgs &a, i
   float cur_p = 0.0f;
   if (dt > 0.0f) {
     cur_p = a.current_position[(size_t)cur * dof + d];
-    pl = fmaxf(pl, cur_p + a.v_b[d] * dt);
-    pu = fminf(pu, cur_p + a.v_b[dof + d] * dt);
+    cspace_velocity_bounds(pl, pu, cur_p, a.v_b[d], a.v_b[dof + d], dt);
   }
   float c = 0.0f;
   gt = 0.0f;
@@ -202,16 +223,7 @@ __device__ __forceinline__ float cspace_position_point(const CspacePosArgs &a, i
     c += tw * e * e;
     gp += 2.0f * tw * e;
   }
-  const float vw = a.squared_l2_reg_weight[0] * dt, aw = a.squared_l2_reg_weight[1] * dt * dt;
-  if (dt > 0.0f && (vw > 0.0f || aw > 0.0f)) {
-    const float vi = (cp - cur_p) / dt;
-    if (vw > 0.0f) { c += 0.5f * vw * vi * vi; gp += vw * vi / dt; }
-    if (aw > 0.0f) {
-      const float ai = (vi - a.current_velocity[(size_t)cur * dof + d]) / dt;
-      c += 0.5f * aw * ai * ai;
-      gp += aw * ai / (dt * dt);
-    }
-  }
+  cspace_state_regularisation(cp, cur_p, a.current_velocity + (size_t)cur * dof + d, dt, a.squared_l2_reg_weight, c, gp);
   return c;
 }
 

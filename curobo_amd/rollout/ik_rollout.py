@@ -35,13 +35,21 @@ class IKRolloutCfg:
     #: one fused launch (csrc/rollout_ik_fused.hip, rollout_ik_fused_kernel) for cost + gradient when 16
     #: configurations fit in LDS; False = the seven drop-in launches
     use_fused: bool = True
+    #: weights of the implied velocity / acceleration regularisation w.r.t. the current state (reference
+    #: ``squared_l2_regularization_weight`` of the c-space position cost, cost_cspace_cfg.py); read by a rollout built with
+    #: ``use_current_state=True``
+    squared_l2_regularization_weight: List[float] = field(default_factory=lambda: [0.0, 0.0])
 
 
 class IKRollout(PoseTerms, RobotRolloutBase):
     """cost[B] and d cost / d q [B, D] for B joint configurations against per-row goal poses."""
 
     def __init__(self, kin: KinematicsParams, scene: Optional[SceneData], batch_size: int,
-                 cfg: Optional[IKRolloutCfg] = None, num_goalset: int = 1):
+                 cfg: Optional[IKRolloutCfg] = None, num_goalset: int = 1, use_current_state: bool = False):
+        """``use_current_state``: the c-space term is taken w.r.t. a current state (``update_current_state``): joint limits
+        tightened to one time step from it + ``cfg.squared_l2_regularization_weight``.  Such a rollout always launches the
+        state variant of the fused launch / passes the state to the c-space kernel; ``dt`` = 0 (the initial state) gives the
+        plain term from the same launches."""
         c = cfg or IKRolloutCfg()
         super().__init__(kin, scene, c, c.self_collision_weight, c.scene_collision_weight, c.scene_activation_distance)
         self.action_horizon = 1
@@ -57,6 +65,11 @@ class IKRollout(PoseTerms, RobotRolloutBase):
         self._zeroD = torch.zeros(1, D, device=d)
         self._onesD = torch.ones(D, device=d)
         self._reg = torch.zeros(2, device=d)
+        self.use_current_state = bool(use_current_state)
+        if self.use_current_state:
+            self._reg = f(c.squared_l2_regularization_weight)
+            self._acc_reg = float(c.squared_l2_regularization_weight[1]) > 0.0
+            self._cur_pos, self._cur_vel, self._state_dt = torch.zeros(1, D, device=d), torch.zeros(1, D, device=d), torch.zeros(1, device=d)
         self._env_runs_ok = True  # env_query_idx constant over aligned runs of 16 rows (update_env_query_idx)
         self.update_batch_size(batch_size)
 
@@ -65,6 +78,7 @@ class IKRollout(PoseTerms, RobotRolloutBase):
         self._alloc_pose_buffers(B, 1, self.num_goalset)
         self.cspace_cost, self.cspace_grad = self._zeros(B, 1, self.action_dim), self._zeros(B, 1, self.action_dim)
         self._idxs_src = None  # (the row -> goal map was reallocated: the next update_goals must copy, whatever tensor it is handed)
+        self._idxs_cur, self._idxs_cur_src = self._zeros(B, dt=torch.int32), None  # row -> current state
 
     def update_env_query_idx(self, env_query_idx: Optional[torch.Tensor]) -> None:
         """Scene environment of every configuration (see the base).  The fused IK launch serves 16 configurations per
@@ -88,16 +102,55 @@ class IKRollout(PoseTerms, RobotRolloutBase):
             self.idxs_goal.copy_(idxs_goal.to(torch.int32))
             self._idxs_src = key
 
+    def update_current_state(self, position: torch.Tensor, velocity: Optional[torch.Tensor] = None, dt=None,
+                             idxs: Optional[torch.Tensor] = None) -> None:
+        """position [P, D], velocity [P, D] or None (= at rest), dt [P] / float / None, idxs [B]: row b is taken w.r.t. state
+        idxs[b] (kept when None).  Copied into fixed buffers, so captured graphs stay valid as long as P does not change (a new
+        P allocates: re-capture).  ``dt`` None or 0 writes zeros: the terms are off, the launches are the same."""
+        if not self.use_current_state:
+            raise ValueError("update_current_state: the rollout was built without use_current_state=True")
+        d, D = self.device, self.action_dim
+        p = position.to(d, torch.float32).reshape(-1, D)
+        if p.shape != self._cur_pos.shape:
+            self._cur_pos, self._cur_vel, self._state_dt = torch.zeros_like(p), torch.zeros_like(p), torch.zeros(p.shape[0], device=d)
+            self._idxs_cur.zero_()  # (indices into the old states may be out of range now)
+            self._idxs_cur_src = None
+        P = self._cur_pos.shape[0]
+        if idxs is not None:
+            key = (idxs, idxs._version)  # (solvers pass the same, unmodified row -> problem map every solve: no copy, no check then)
+            last = self._idxs_cur_src
+            if last is None or last[0] is not key[0] or last[1] != key[1]:
+                if idxs.numel() != self.batch_size or int(idxs.min()) < 0 or int(idxs.max()) >= P:
+                    raise ValueError(f"update_current_state: idxs must hold {self.batch_size} state indices in [0, {P})")
+                self._idxs_cur.copy_(idxs.to(device=d, dtype=torch.int32).reshape(-1))
+                self._idxs_cur_src = key
+        self._cur_pos.copy_(p)
+        self._cur_vel.copy_(velocity.to(d, torch.float32).reshape(P, D)) if velocity is not None else self._cur_vel.zero_()
+        if dt is None:
+            self._state_dt.zero_()
+        elif torch.is_tensor(dt):
+            self._state_dt.copy_(dt.to(d, torch.float32).reshape(-1).expand(P))
+        else:
+            self._state_dt.fill_(float(dt))
+
+    def _state_args(self):
+        """(regularisation weights, current position, current velocity, row -> state, dt per state) of the c-space term; without
+        a current state: the zeros that switch the terms off"""
+        if self.use_current_state:
+            return self._reg, self._cur_pos, self._cur_vel, self._idxs_cur, self._state_dt
+        return self._reg, self._zeroD, self._zeroD, self._idx0, self._zero1
+
     # ------------------------------------------------------------------ forward + backward
     def evaluate(self, q: torch.Tensor, with_gradient: bool = True) -> torch.Tensor:
         k, B = self.kin, self.batch_size
         T, S, D = k.num_pose_links, k.num_spheres, k.num_dof
         self._fk_forward(q)
         self._pose_term()
+        reg, cur_pos, cur_vel, idxs_cur, state_dt = self._state_args()
         cost_hip.cspace_position_cost(
             self.cspace_cost, self.cspace_grad, None, q, None, self._zeroD, self._idx0, self._p_b, self._effort_b,
-            self._cs_w, self._cs_eta, self._zero1, self._onesD, self._reg, self._zeroD, self._zeroD, self._idx0,
-            self._v_b, self._zero1, True, B, 1, D)
+            self._cs_w, self._cs_eta, self._zero1, self._onesD, reg, cur_pos, cur_vel, idxs_cur,
+            self._v_b, state_dt, True, B, 1, D)
         self._self_collision()
         use_scene = self.scene is not None
         if use_scene:
@@ -123,6 +176,11 @@ class IKRollout(PoseTerms, RobotRolloutBase):
         k, B, c = self.kin, self.batch_size, self.cfg
         sc = k.self_collision
         m = with_metrics
+        state = {}
+        if self.use_current_state:  # curobo_hip_rollout_ik_fused_state
+            state = dict(squared_l2_reg_weight=self._reg, current_position=self._cur_pos, current_velocity=self._cur_vel,
+                         idxs_current_state=self._idxs_cur, velocity_limits=self._v_b, state_dt=self._state_dt,
+                         acceleration_regularization=self._acc_reg)
         rollout_hip.rollout_ik_fused(
             self.cost, self.grad_q, self.pose_cost if m else None, self.pose_pos_dist if m else None,
             self.pose_rot_dist if m else None, self.goalset_idx if m else None, self.link_pos if m else None,
@@ -132,7 +190,7 @@ class IKRollout(PoseTerms, RobotRolloutBase):
             k.joint_map_type, k.joint_map, k.link_map, k.tool_frame_map, k.link_sphere_idx_map, k.link_chain_data,
             k.link_chain_offsets, k.joint_offset_map, sc.sphere_padding, self._w_self, sc.collision_pairs,
             self.scene.struct if self.scene is not None else None, self._w_scene, self._eta_scene, B, k.num_dof,
-            self.env_query_idx, k.num_envs, self.use_multi_env)
+            self.env_query_idx, k.num_envs, self.use_multi_env, **state)
         return self.cost, self.grad_q.view(B, -1)
 
     def cost_and_gradient(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -59,6 +59,12 @@ class IKSolverCfg:
     #: convergence metric, metrics_base.yml:27-30: weight 0.001), so that among the solutions that succeed the ones near the robot's
     #: configuration come first unless they are millimetres less accurate.  Without a current position: the rollout's cost, as before.
     start_cspace_dist_weight: float = 0.001
+    #: reference IKSolverCfg.optimization_dt (solver_ik_cfg.py:159-162): the time step [s] in which a solution has to be reachable
+    #: from ``solve_pose(current_position=)``.  Set: every rollout -- the metrics rollout too, as the reference hands one goal with
+    #: ``current_js`` / ``current_state_dt`` to all of them (cost_manager_robot.py:250-256) -- carries the current state: the joint
+    #: limits are tightened to ``current +- velocity_limits * dt``, ``rollout.squared_l2_regularization_weight`` regularises the
+    #: implied velocity / acceleration, and ``success`` requires a solution within one step.  None: no current state anywhere.
+    optimization_dt: Optional[float] = None
 
 
 @dataclass
@@ -99,9 +105,12 @@ class IKSolver:
         # the metrics rollout decides feasibility as the reference's does (content/configs/task/metrics_base.yml:8-19): joint limits
         # and scene collision at ZERO activation distance -- a solution inside the optimiser's 0.01 rad / 2.5 mm activation shells
         # is inside the limits and clear of the world (with 49 joints a quarter of the G1's solutions sit within 0.01 rad of a limit)
+        # with a current state: the same position term at zero activation and zero regularisation (cost_cspace_cfg.py:84-119)
+        self._with_state = self.cfg.optimization_dt is not None
         self.metrics_rollout = IKRollout(kin, scene, self.P * self.S, dataclasses.replace(
             self.cfg.rollout, cspace_activation_distance=[0.0] * len(self.cfg.rollout.cspace_activation_distance),
-            scene_activation_distance=0.0), num_goalset=self.G)
+            scene_activation_distance=0.0, squared_l2_regularization_weight=[0.0, 0.0]), num_goalset=self.G,
+            use_current_state=self._with_state)
         bounds = (kin.joint_limits_position[0], kin.joint_limits_position[1])
         K = self.cfg.stream_shards
         if K > 1 and self.P % K != 0:
@@ -110,7 +119,7 @@ class IKSolver:
         self.rollouts = []
 
         def make_rollout(batch, k=0):
-            ro = IKRollout(kin, scene, batch, self.cfg.rollout, num_goalset=self.G)
+            ro = IKRollout(kin, scene, batch, self.cfg.rollout, num_goalset=self.G, use_current_state=self._with_state)
             ro._first_problem = k * (self.P // K)  # rows of shard k belong to problems [first, first + P/K)
             self.rollouts.append(ro)
             return ro.cost_and_gradient
@@ -163,6 +172,7 @@ class IKSolver:
         # the robot's configuration and the weight of its distance term in the ranking: fixed buffers (the ranking is a captured graph)
         self._cur_buf = torch.zeros(self.P, kin.num_dof, device=self.device)
         self._cur_w = torch.zeros(1, device=self.device)
+        self._set_current_state(None, None, None)  # (the state buffers get their size before anything is captured)
 
     @classmethod
     def sharded(cls, kin: KinematicsParams, scene: Optional[SceneData], num_problems: int, cfg: Optional[IKSolverCfg] = None,
@@ -179,6 +189,16 @@ class IKSolver:
             raise ValueError(f"{cfg.num_seeds} seeds cannot be sharded over {dist.get_world_size()} ranks")
         return cls(kin, scene, num_problems, dataclasses.replace(cfg, num_seeds=hi - lo), seed_offset=lo,
                    use_cuda_graph=use_cuda_graph, global_num_seeds=cfg.num_seeds)
+
+    def _set_current_state(self, position: Optional[torch.Tensor], velocity: Optional[torch.Tensor], dt) -> None:
+        """the current state of every problem into the fixed buffers of every rollout (row -> problem: the map the goals use);
+        no position = dt 0: the terms are off"""
+        if not self._with_state:
+            return
+        if position is None:
+            position, velocity, dt = self._cur_buf, None, None
+        for ro, rows in zip(self.rollouts + [self.metrics_rollout], self._row_goals + [self._mrow_goal]):
+            ro.update_current_state(position, velocity, dt, rows)
 
     def reset_seed(self) -> None:
         """reference ``reset_seed``: rewind the Halton index stream of the LM seed stage, so that the next solve starts from
@@ -205,7 +225,8 @@ class IKSolver:
     def solve_pose(self, goal_position: torch.Tensor, goal_quat: torch.Tensor,
                    seeds: Optional[torch.Tensor] = None, return_seeds: int = 1,
                    exit_early: Optional[bool] = None, env_idx: Optional[torch.Tensor] = None,
-                   current_position: Optional[torch.Tensor] = None) -> IKResult:
+                   current_position: Optional[torch.Tensor] = None, current_velocity: Optional[torch.Tensor] = None,
+                   dt=None) -> IKResult:
         """Goals of EVERY tool frame (reference IKSolver.solve_pose over a GoalToolPose, solver_ik.py:631-700): goal_position
         [P, T, G, 3], goal_quat [P, T, G, 4] (wxyz) with T = the robot's tool frames (``kin.tool_frames`` order) and G =
         ``cfg.num_goalset`` alternatives per problem (one member index per frame is chosen: the closest).  A robot with ONE
@@ -213,15 +234,24 @@ class IKSolver:
         thresholds; the reported errors are the largest over the frames.  ``return_seeds`` k > 1 returns the k best seeds
         per problem, best first (solver_ik.py:503-530: top-k over the ranked cost), with a [P, k, ...] result.
         ``current_position`` [P, D]: the robot's configuration -- the first seed of every problem, and the seed stage prefers
-        solutions close to it (reference: ``current_state`` / ``seed_config`` of solve_pose, as the MPC's goal IK passes them)."""
+        solutions close to it (reference: ``current_state`` / ``seed_config`` of solve_pose, as the MPC's goal IK passes them).
+        With ``cfg.optimization_dt`` set it is also the state the solution has to be reachable from in ``dt`` (float or [P];
+        default ``cfg.optimization_dt``), ``current_velocity`` [P, D] the velocity the acceleration regularisation refers to
+        (None: at rest); without ``current_position`` the step is written as 0 and the solve is the plain one."""
         P, S, D, T, G = self.P, self.S, self.kin.num_dof, self.kin.num_pose_links, self.G
         if goal_position.numel() != P * T * G * 3 or goal_quat.numel() != P * T * G * 4:
             raise ValueError(f"solve_pose: expected goals for {P} problems x {T} tool frames {tuple(self.kin.tool_frames)} x {G} "
                              f"goal-set members, got position {tuple(goal_position.shape)}, quaternion {tuple(goal_quat.shape)}")
         gp = goal_position.to(self.device, torch.float32).reshape(P, T, G, 3).contiguous()
         gq = goal_quat.to(self.device, torch.float32).reshape(P, T, G, 4).contiguous()
+        if dt is not None and not self._with_state:
+            raise ValueError("solve_pose: dt needs a solver built with IKSolverCfg.optimization_dt")
+        step = None
+        if self._with_state and current_position is not None:
+            step = self.cfg.optimization_dt if dt is None else dt
         self._set_envs(env_idx)
         self.metrics_rollout.update_goals(gp, gq, self._mrow_goal)
+        self._set_current_state(current_position, current_velocity, step)
         if current_position is not None:
             self._cur_buf.copy_(current_position.to(self.device, torch.float32).reshape(P, D))
             self._cur_w.fill_(float(self.cfg.start_cspace_dist_weight))
@@ -243,7 +273,8 @@ class IKSolver:
                 shared = self.seed_solver.goal_position is m.goal_position
                 cur = None if current_position is None else current_position.to(self.device, torch.float32).reshape(P, D)
                 seeds = self.seed_solver.solve_batch(m.goal_position if shared else gp, m.goal_quat if shared else gq,
-                                                     return_seeds=self.S_global, current_position=cur).solution
+                                                     return_seeds=self.S_global, current_position=cur, dt=step,
+                                                     current_velocity=current_velocity if step is not None else None).solution
                 if self.S_global != S:
                     seeds = seeds[:, self.seed_offset:self.seed_offset + S].contiguous()
             else:

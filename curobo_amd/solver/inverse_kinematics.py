@@ -107,6 +107,18 @@ class InverseKinematicsCfg:
     stream_shards: int = 1
     #: reference ``override_iters_for_multi_link_ik``: L-BFGS iterations raised to this when lower
     override_iters_for_multi_link_ik: Optional[int] = None
+    #: reference ``optimization_dt`` (solver_ik_cfg.py:159-162, 249-257): with ``solve_pose(current_state=)`` a solution has to be
+    #: reachable from the current state in this time step [s]; None = the current state only ranks the solutions
+    optimization_dt: Optional[float] = None
+    #: weights of the implied velocity / acceleration regularisation w.r.t. the current state; None = the task value (0)
+    velocity_regularization_weight: Optional[float] = None
+    acceleration_regularization_weight: Optional[float] = None
+    #: reference ``override_optimizer_num_iters``: ``{"lbfgs": n}`` sets the L-BFGS iteration count (rounded up to whole inner loops)
+    override_optimizer_num_iters: Optional[Dict[str, Optional[int]]] = None
+    #: built-in cost and optimiser values the solvers start from, for a front end with a task set of its own (the motion
+    #: retargeter's ``lbfgs_retarget_ik.yml`` values); None = ``lbfgs_ik.yml``'s, the defaults of ``IKSolverCfg``.  The fields
+    #: above are applied on top of a copy
+    task_cfg: Optional[IKSolverCfg] = None
 
     @staticmethod
     def create(robot: Union[str, Dict], scene_model: Union[str, Dict, List, None] = None, num_seeds: int = 32,
@@ -114,11 +126,16 @@ class InverseKinematicsCfg:
                self_collision_check: bool = True, optimizer_collision_activation_distance: float = 0.0025,
                device_cfg: Optional[DeviceCfg] = None, seed_solver_num_seeds: Optional[int] = None, max_batch_size: int = 0,
                max_goalset: int = 1, use_lm_seed: bool = True, exit_early: bool = True, assets_root: str = "",
-               override_iters_for_multi_link_ik: Optional[int] = None, **unused) -> "InverseKinematicsCfg":
+               override_iters_for_multi_link_ik: Optional[int] = None, optimization_dt: Optional[float] = None,
+               velocity_regularization_weight: Optional[float] = None,
+               acceleration_regularization_weight: Optional[float] = None,
+               override_optimizer_num_iters: Optional[Dict[str, Optional[int]]] = None, **unused) -> "InverseKinematicsCfg":
         """``robot``: packaged name (``"franka.yml"``), a robot yaml path or its dictionary.  ``scene_model``: the
         reference's scene format (see ``curobo_amd.scene.config``).  Keyword arguments of the reference this backend has
         no use for (``optimizer_configs``, ``metrics_rollout``, ``transition_model``, ...) are accepted and ignored: the
-        cost set and optimiser settings of ``content/configs/task/ik/lbfgs_ik.yml`` are built in."""
+        cost set and optimiser settings of ``content/configs/task/ik/lbfgs_ik.yml`` are built in.  ``optimization_dt``,
+        ``velocity_regularization_weight``, ``acceleration_regularization_weight`` and ``override_optimizer_num_iters`` are the
+        reference's (solver_ik_cfg.py:159-162, 249-257): see the fields."""
         import os
 
         device_cfg = device_cfg or DeviceCfg()
@@ -135,7 +152,10 @@ class InverseKinematicsCfg:
             orientation_tolerance=orientation_tolerance, use_cuda_graph=use_cuda_graph, self_collision_check=self_collision_check,
             optimizer_collision_activation_distance=optimizer_collision_activation_distance, exit_early=exit_early,
             seed_solver_num_seeds=seed_solver_num_seeds or max(32, 2 * num_seeds), use_lm_seed=use_lm_seed,
-            max_batch_size=max_batch_size, max_goalset=max_goalset, override_iters_for_multi_link_ik=override_iters_for_multi_link_ik)
+            max_batch_size=max_batch_size, max_goalset=max_goalset, override_iters_for_multi_link_ik=override_iters_for_multi_link_ik,
+            optimization_dt=optimization_dt, velocity_regularization_weight=velocity_regularization_weight,
+            acceleration_regularization_weight=acceleration_regularization_weight,
+            override_optimizer_num_iters=override_optimizer_num_iters)
 
 
 class InverseKinematics(ToolPoseTrackingMixin):
@@ -248,10 +268,22 @@ class InverseKinematics(ToolPoseTrackingMixin):
     def _solver(self, batch: int) -> IKSolver:
         if batch not in self._solvers:
             c = self.config
-            cfg = IKSolverCfg(num_seeds=c.num_seeds, position_threshold=c.position_tolerance, rotation_threshold=c.orientation_tolerance,
-                              use_lm_seed=c.use_lm_seed, seed_solver_num_seeds=c.seed_solver_num_seeds, num_goalset=c.max_goalset,
-                              stream_shards=c.stream_shards if batch % max(c.stream_shards, 1) == 0 else 1,
-                              override_iters_for_multi_link_ik=c.override_iters_for_multi_link_ik)
+            import copy
+            import dataclasses
+
+            cfg = dataclasses.replace(
+                copy.deepcopy(c.task_cfg) if c.task_cfg is not None else IKSolverCfg(), num_seeds=c.num_seeds,
+                position_threshold=c.position_tolerance, rotation_threshold=c.orientation_tolerance, use_lm_seed=c.use_lm_seed,
+                seed_solver_num_seeds=c.seed_solver_num_seeds, num_goalset=c.max_goalset,
+                stream_shards=c.stream_shards if batch % max(c.stream_shards, 1) == 0 else 1,
+                override_iters_for_multi_link_ik=c.override_iters_for_multi_link_ik, optimization_dt=c.optimization_dt)
+            for i, w in enumerate((c.velocity_regularization_weight, c.acceleration_regularization_weight)):
+                if w is not None:  # (None keeps the task value)
+                    cfg.rollout.squared_l2_regularization_weight[i] = float(w)
+            n = (c.override_optimizer_num_iters or {}).get("lbfgs")
+            if n is not None:
+                inner = max(int(cfg.optimizer.inner_iters), 1)
+                cfg.optimizer.num_iters = -(-int(n) // inner) * inner
             cfg.rollout.scene_activation_distance = c.optimizer_collision_activation_distance
             if not c.self_collision_check:
                 cfg.rollout.self_collision_weight = 0.0
@@ -266,7 +298,10 @@ class InverseKinematics(ToolPoseTrackingMixin):
         (``tool_frames`` order), as the reference's solve_pose takes it (solver_ik.py:631-700); a goal set smaller than
         ``config.max_goalset`` is padded with its last pose, a larger one rebuilds the solvers; ``seed_config``
         [batch, num_seeds, dof] optional warm starts; ``current_state`` [batch, dof]: the robot's configuration -- first seed of
-        the seed stage, which then prefers solutions near it (reference ``solve_pose(current_state=)``, solver_ik.py:631-700)."""
+        the seed stage, which then prefers solutions near it (reference ``solve_pose(current_state=)``, solver_ik.py:631-700).
+        With ``config.optimization_dt`` set the solution also has to be reachable from it in ``current_state.dt`` (else
+        ``optimization_dt``, solver_ik.py:344-360), ``current_state.velocity`` is what the acceleration regularisation refers to,
+        and ``js_solution.velocity`` = (solution - current) / dt (solver_ik.py:588-624)."""
         t0 = time.perf_counter()
         gp, gq = goal_tool_poses.static_goals(self.tool_frames)  # [batch, T, G, 3 | 4], the robot's frame order
         B, T, G = int(gp.shape[0]), int(gp.shape[1]), int(gp.shape[2])
@@ -280,13 +315,23 @@ class InverseKinematics(ToolPoseTrackingMixin):
             pos = torch.cat([pos, pos[:, :, -1:].expand(B, T, M - G, 3)], 2)
             quat = torch.cat([quat, quat[:, :, -1:].expand(B, T, M - G, 4)], 2)
         cur = None if current_state is None else current_state.position.to(pos.device, torch.float32).reshape(-1, self.dof).expand(B, self.dof)
-        r = slv.solve_pose(pos, quat, seeds=seed_config, return_seeds=return_seeds, exit_early=self.config.exit_early, current_position=cur)
+        vel = step = None
+        if cur is not None and self.config.optimization_dt is not None:
+            step = torch.as_tensor(self.config.optimization_dt if current_state.dt is None else current_state.dt, dtype=torch.float32,
+                                   device=pos.device).reshape(-1)
+            if current_state.velocity is not None:
+                vel = current_state.velocity.to(pos.device, torch.float32).reshape(-1, self.dof).expand(B, self.dof)
+        r = slv.solve_pose(pos, quat, seeds=seed_config, return_seeds=return_seeds, exit_early=self.config.exit_early, current_position=cur,
+                           current_velocity=vel, dt=step)
         torch.cuda.synchronize(pos.device) if pos.is_cuda else None
         self.solve_time = time.perf_counter() - t0
         k = return_seeds
         sol = r.solution.reshape(B, k, -1)
+        js = JointState.from_position(sol, joint_names=self.joint_names)
+        if step is not None:
+            js.velocity = (sol - cur.reshape(B, 1, -1)) / step.reshape(-1, 1, 1)
         return InverseKinematicsResult(
-            success=r.success.reshape(B, k), solution=sol, js_solution=JointState.from_position(sol, joint_names=self.joint_names),
+            success=r.success.reshape(B, k), solution=sol, js_solution=js,
             position_error=r.position_error.reshape(B, k), rotation_error=r.rotation_error.reshape(B, k),
             goalset_index=None if r.goalset_index is None else r.goalset_index.reshape(B, k, T), solve_time=self.solve_time,
             debug_info={"optimizer_ran": bool(getattr(slv, "optimizer_ran", True))}, total_time=self.solve_time,

@@ -838,6 +838,51 @@ class GoalToolPose(_FramePoseMembers):
 
 
 @dataclass
+class SequenceGoalToolPose:
+    """a clip of goal poses per tool frame, time first (reference SequenceGoalToolPose, _src/types/sequence_tool_pose.py:24-98):
+    position [num_frames, num_envs, num_links, num_goalset, 3], quaternion [..., 4] (wxyz); frame ``t`` is a contiguous slice"""
+
+    tool_frames: List[str]
+    position: torch.Tensor
+    quaternion: torch.Tensor
+
+    def __post_init__(self):
+        if self.position.ndim != 5:
+            raise ValueError(f"SequenceGoalToolPose position must be 5D [F,E,L,G,3], got {tuple(self.position.shape)}")
+        if self.quaternion.ndim != 5:
+            raise ValueError(f"SequenceGoalToolPose quaternion must be 5D [F,E,L,G,4], got {tuple(self.quaternion.shape)}")
+        if self.position.shape[2] != len(self.tool_frames):
+            raise ValueError(f"num_links dim ({self.position.shape[2]}) != len(tool_frames) ({len(self.tool_frames)})")
+
+    @property
+    def num_frames(self) -> int:
+        return int(self.position.shape[0])
+
+    @property
+    def num_envs(self) -> int:
+        return int(self.position.shape[1])
+
+    @property
+    def num_links(self) -> int:
+        return int(self.position.shape[2])
+
+    @property
+    def num_goalset(self) -> int:
+        return int(self.position.shape[3])
+
+    @property
+    def device(self):
+        return self.position.device
+
+    def get_frame(self, t: int) -> GoalToolPose:
+        """frame ``t`` as a GoalToolPose [num_envs, 1, num_links, num_goalset, 3 | 4]: a view, no copy"""
+        return GoalToolPose(self.tool_frames, self.position[t].unsqueeze(1), self.quaternion[t].unsqueeze(1))
+
+    def clone(self) -> "SequenceGoalToolPose":
+        return SequenceGoalToolPose(list(self.tool_frames), self.position.clone(), self.quaternion.clone())
+
+
+@dataclass
 class ToolPoseCriteria:
     """how the pose cost of one tool frame is weighted (reference _src/cost/tool_pose_criteria.py:17-200): factors on the
     (x, y, z, roll, pitch, yaw) terms at the last point of a trajectory and at the points before it, convergence tolerances

@@ -760,6 +760,38 @@ int curobo_hip_rollout_ik_fused(
     int num_spheres, int num_collision_pairs, int link_chain_len, const int32_t *env_query_idx, int num_envs,
     int use_multi_env, curobo_hip_stream_t stream);
 
+/* curobo_hip_rollout_ik_fused with a current state: the arguments of that entry point in its order, then the current state, the
+ * stream last.  The c-space term becomes the reference's with a state (cost/wp_cspace_position.py:299-356,
+ * curobo_hip_cspace_position_cost semantics): row b reads state cur = idxs_current_state[b] (rows of one workgroup may differ)
+ * and dt = state_dt[cur]; with dt > 0 the activation-shrunk limits are tightened to [current_position + velocity_limits[0] * dt,
+ * current_position + velocity_limits[1] * dt] and 0.5 * (squared_l2_reg_weight[0] * dt) * v^2 + 0.5 * (squared_l2_reg_weight[1] *
+ * dt^2) * a^2 is added, v = (q - current_position) / dt, a = (v - current_velocity) / dt; dt == 0 is the term of
+ * curobo_hip_rollout_ik_fused, bit for bit.  out_cspace_cost [b, dof] carries the whole term.  current_position /
+ * current_velocity [n_states, dof], idxs_current_state [b], velocity_limits [2, dof], state_dt [n_states],
+ * squared_l2_reg_weight [2] (device).  current_velocity may be NULL when the acceleration weight is 0 (the acceleration term is
+ * then skipped whatever the device-side weight says); acceleration_regularization != 0 states that the weight may be positive:
+ * current_velocity is then required.  Same LDS layout as curobo_hip_rollout_ik_fused (curobo_hip_rollout_ik_fused_lds_bytes). */
+int curobo_hip_rollout_ik_fused_state(
+    float *out_cost, float *out_grad_q, float *out_pose_distance, float *out_position_distance,
+    float *out_rotation_distance, int32_t *out_goalset_idx, float *out_link_pos,
+    float *out_link_quat, float *out_robot_spheres, float *out_cspace_cost, const float *q,
+    const float *goal_position, const float *goal_quat, const int32_t *idxs_goal,
+    const float *position_orientation_weight, const float *terminal_pose_axes_weight_factor,
+    const float *terminal_pose_convergence_tolerance, const uint8_t *project_distance_to_goal,
+    int num_goalset, int rotation_method, const float *p_b, const float *cspace_weight,
+    const float *cspace_activation_distance, const float *fixed_transform,
+    const float *robot_spheres, const int8_t *joint_map_type, const int16_t *joint_map,
+    const int16_t *link_map, const int16_t *tool_frame_map, const int16_t *link_sphere_map,
+    const int16_t *link_chain_data, const int16_t *link_chain_offsets,
+    const float *joint_offset_map, const float *sphere_padding,
+    const float *self_collision_weight, const int16_t *pair_locations,
+    const curobo_hip_scene *scene, const float *scene_collision_weight,
+    const float *activation_distance, int batch_size, int dof, int num_links, int n_tool_frames,
+    int num_spheres, int num_collision_pairs, int link_chain_len, const int32_t *env_query_idx, int num_envs,
+    int use_multi_env, const float *squared_l2_reg_weight, const float *current_position,
+    const float *current_velocity, const int32_t *idxs_current_state, const float *velocity_limits,
+    const float *state_dt, int acceleration_regularization, curobo_hip_stream_t stream);
+
 /* LDS bytes of one 16-configuration workgroup of curobo_hip_rollout_ik_fused (usable when <= 163840) */
 int curobo_hip_rollout_ik_fused_lds_bytes(int dof, int num_links, int num_spheres,
                                           int num_collision_pairs, int link_chain_len,
