@@ -118,38 +118,88 @@ __device__ __forceinline__ float bspline_sample_at(const BsFwdArgs &a, int b, in
   return bspline_sample_pre<DEG>(a, b, h, d, ph, interpolated_dt, bo, go, a.use_implicit_goal[go] != 0, o);
 }
 
+// Which knot interval a sample lies in: what the loads of a sample and its arithmetic both start from.  It depends on the
+// trajectory's shape alone (h, padded horizon, knot count), on nothing that is loaded.
+template <int DEG>
+struct BsSampleSpan {
+  int interp, knot_idx;
+  bool past_end;
+  __device__ __forceinline__ BsSampleSpan(int h, int ph, int n_knots) {
+    constexpr int SUP = DEG + 1;
+    const int padded_n_knots = n_knots + SUP;
+    interp = (ph - 1) / padded_n_knots;
+    knot_idx = interp > 0 ? h / interp : 0;
+    past_end = false;
+    if (knot_idx >= padded_n_knots) { knot_idx = padded_n_knots - 1; past_end = true; }
+  }
+};
+
+// the SUP knot values of sample (b, h, d), zero outside the knot vector: needs b, h and d only, so a caller can request them
+// before anything else of the trajectory is known (clamped, unpredicated: all SUP loads in flight)
+template <int DEG>
+__device__ __forceinline__ void bspline_sample_knots(const BsFwdArgs &a, int b, int h, int d, int ph, float *knots) {
+  constexpr int SUP = DEG + 1;
+  const BsSampleSpan<DEG> sp(h, ph, a.n_knots);
+  const int start_knot = sp.knot_idx - SUP;
+#pragma unroll
+  for (int i = 0; i < SUP; i++) {
+    const int src = start_knot + i;
+    const int sc = src < 0 ? 0 : (src < a.n_knots ? src : a.n_knots - 1);
+    const float kv = a.u[((size_t)b * a.n_knots + sc) * a.dof + d];
+    knots[i] = (src < a.n_knots && src >= 0) ? kv : 0.0f;
+  }
+}
+// which boundary state row sample h reads IF it reads one: the start row (knot_idx < SUP), else the goal row.  Whether it does
+// read one depends on the goal mode, a loaded value (implicit: knot_idx > n_knots - 1, explicit: knot_idx > n_knots); a caller
+// that requests the row before it knows the mode requests it for every sample (a sample between the boundaries fetches a goal
+// row it does not use: the address is valid for all of them).
+template <int DEG>
+__device__ __forceinline__ bool bspline_sample_state_from_start(int h, int ph, int n_knots) {
+  return BsSampleSpan<DEG>(h, ph, n_knots).knot_idx < DEG + 1;
+}
+// position / velocity / acceleration / jerk component d of start row bo or goal row go -> st[4]: needs the indices only
+__device__ __forceinline__ void bspline_sample_state(const BsFwdArgs &a, bool from_start, int bo, int go, int d, float *st) {
+  const int ci = (from_start ? bo : go) * a.dof + d;
+  const float *const *src = from_start ? a.start : a.goal;
+  st[0] = src[0][ci]; st[1] = src[1][ci]; st[2] = src[2][ci]; st[3] = src[3][ci];
+}
+
+template <int DEG>
+__device__ __forceinline__ float bspline_sample_values(const BsFwdArgs &a, int h, int ph, float interpolated_dt, bool implicit_goal,
+                                                       float *knots, const float *state, float *o);
+
 // the same with the trajectory's indices and goal mode already in registers (a caller that samples many points of ONE
 // trajectory loads them once, ahead of its other memory traffic, instead of at the head of every sample's chain)
 template <int DEG>
 __device__ __forceinline__ float bspline_sample_pre(const BsFwdArgs &a, int b, int h, int d, int ph, float interpolated_dt,
                                                     int bo, int go, bool implicit_goal, float *o) {
   constexpr int SUP = DEG + 1;
-  const int dof = a.dof;
-  const int horizon = ph - 1;
-  const int padded_n_knots = a.n_knots + SUP;
-  const int interp = horizon / padded_n_knots;
+  float knots[SUP], state[4] = {0.f, 0.f, 0.f, 0.f};
+  bspline_sample_knots<DEG>(a, b, h, d, ph, knots);
+  const BsSampleSpan<DEG> sp(h, ph, a.n_knots);
+  const bool req_start = sp.knot_idx < SUP;
+  const bool req_goal = implicit_goal ? (sp.knot_idx > a.n_knots - 1) : (sp.knot_idx > a.n_knots);
+  if (req_start || req_goal) bspline_sample_state(a, req_start, bo, go, d, state);
+  return bspline_sample_values<DEG>(a, h, ph, interpolated_dt, implicit_goal, knots, state, o);
+}
+
+// ... and with every loaded value in registers: knots[SUP] from bspline_sample_knots (overwritten), state[4] from
+// bspline_sample_state (read only by a sample that needs a boundary row).  The arithmetic of a sample lives here, once.
+template <int DEG>
+__device__ __forceinline__ float bspline_sample_values(const BsFwdArgs &a, int h, int ph, float interpolated_dt, bool implicit_goal,
+                                                       float *knots, const float *state, float *o) {
+  constexpr int SUP = DEG + 1;
+  const BsSampleSpan<DEG> sp(h, ph, a.n_knots);
+  const int interp = sp.interp, knot_idx = sp.knot_idx;
+  const bool past_end = sp.past_end;
   const float knot_dt = fmaxf(interpolated_dt, 1e-6f) * (float)interp;
-  float knots[SUP];
-  int knot_idx = interp > 0 ? h / interp : 0;
-  bool past_end = false;
-  if (knot_idx >= padded_n_knots) { knot_idx = padded_n_knots - 1; past_end = true; }
-  const int start_knot = knot_idx - SUP;
-#pragma unroll
-  for (int i = 0; i < SUP; i++) {
-    const int src = start_knot + i;
-    const int sc = src < 0 ? 0 : (src < a.n_knots ? src : a.n_knots - 1);  // (clamped, unpredicated: all SUP loads in flight)
-    const float kv = a.u[((size_t)b * a.n_knots + sc) * dof + d];
-    knots[i] = (src < a.n_knots && src >= 0) ? kv : 0.0f;
-  }
   const bool req_start = knot_idx < SUP;
   const bool req_goal = implicit_goal ? (knot_idx > a.n_knots - 1) : (knot_idx > a.n_knots);
   float t_mod = interp > 0 ? exact_ratio(h, interp) - (float)(int)(h / interp) : 0.0f;
   if (past_end) t_mod = 1.0f;
   const float dt2 = knot_dt * knot_dt, dt3 = knot_dt * knot_dt * knot_dt;
   if (req_start || req_goal) {
-    const int ci = (req_start ? bo : go) * dof + d;
-    const float *const *src = req_start ? a.start : a.goal;
-    const float cpos = src[0][ci], cvel = src[1][ci], cacc = src[2][ci], cjerk = src[3][ci];
+    const float cpos = state[0], cvel = state[1], cacc = state[2], cjerk = state[3];
     float fixed[SUP];
 #pragma unroll
     for (int i = 0; i < SUP; i++)

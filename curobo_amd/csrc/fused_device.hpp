@@ -96,13 +96,14 @@ struct FusedTrajArgs {
 //   offset_add[L] fixed_transform[L][12] sphere_link[S] sphere_rad[S] (raw radius) sphere_pad[S]
 //   link-frame spheres [S][4] | link bounding boxes [L][8] (ordered-int keys) | subtree masks [L][4] | joint-link masks [D][4]
 //   | leftover-point sphere gradients [S][4] + arg-max key | pairs [P] | obstacle records
+//   | the trajectory's dt and goal mode (trajectory kernel: kept from P0 for the B-spline VJP of P3)
 constexpr int kWrench = 7;  // per link: force xyz, torque xyz about the link origin, joint gradient
 constexpr int kSceneListEntries = 128;  // ring of active (row, sphere) entries per wave: < 64 pending + <= 64 appended
 constexpr int kIkPoints = 16;  // configurations per workgroup of the IK and the steering launches (one 16-lane row each)
 
 struct FusedLayout {
   int q, cumul, work, ws, wrench, wl, cost, parent, chain_off, link_info, sign, lists, off_add, fixed, chain, sph_link, sph_rad,
-      sph_pad, rs, lbound, sub, jlinks, left, key, flag, dyn, cstab, pairs, lanel, recs, total;
+      sph_pad, rs, lbound, sub, jlinks, left, key, flag, dyn, cstab, pairs, lanel, recs, bsv, total;
 };
 // n_lane > 0: the lane = sphere form of the pair list (n_lane words) is staged INSTEAD of the (i, j) offsets
 __host__ __device__ inline FusedLayout fused_layout(int H, int D, int L, int S, int C, int P, int n_rec, int n_dyn = 0,
@@ -144,6 +145,7 @@ __host__ __device__ inline FusedLayout fused_layout(int H, int D, int L, int S, 
   f.pairs = take(n_lane > 0 ? 0 : (P + 63) & ~63);  // padded with (NaN sphere, NaN sphere) pairs: loops need no bounds checks
   f.lanel = take(n_lane);
   f.recs = take(n_rec * kObsRecFloats);
+  f.bsv = take(with_left ? 2 : 0);  // (behind everything else: no other offset moves; like `left`, the trajectory kernel's alone)
   f.total = o;
   return f;
 }
@@ -180,6 +182,7 @@ struct FusedCtx {
   int *flag;   // [H] point has gradients (set by the cost pass, read by the VJP pass)
   float *dyn;  // [3][H][D] velocity / acceleration / jerk, later their cost gradients
   float *cstab;  // c-space STATE constants staged once per workgroup: limits [8][D], weights [10], dt
+  float *bsv;    // trajectory kernel: the trajectory's dt and goal mode (1.0f = implicit), written in P0, read by P3
   unsigned long long *key;
   ObsRec *recs;
   int H, D, L, S, P, ws, wl, env;
@@ -855,6 +858,7 @@ __device__ __forceinline__ void fused_ctx_carve(FusedCtx &c, float *smem, const 
   c.flag = reinterpret_cast<int *>(smem + lay.flag);
   c.dyn = smem + lay.dyn;
   c.cstab = smem + lay.cstab;
+  c.bsv = smem + lay.bsv;
   c.pairs = reinterpret_cast<uint32_t *>(smem + lay.pairs);
   c.lanel = reinterpret_cast<const uint32_t *>(smem + lay.lanel);
   c.g_pairs = nullptr; c.lane_len0 = 0; c.lane_len1 = 0;
@@ -867,6 +871,16 @@ __device__ __forceinline__ int rotated_tid(int first_wave) {  // jobs start on d
   return t < 0 ? t + nt : t;
 }
 
+// body(i) for i = first, first + nt, ... below n, the FIRST pass outside the loop.  A loop header waits for every load in flight
+// (the loads its own back edge leaves pending cannot be told from the ones requested before the loop), so a staging loop that
+// stands behind earlier requests opened a round trip of its own; its first pass -- the only one at the built-in shapes -- now
+// requests its values in the trip that is already under way.
+template <class Body>
+__device__ __forceinline__ void staged_passes(int first, int n, int nt, Body body) {
+  if (first < n) body(first);
+  for (int i = first + nt; i < n; i += nt) body(i);
+}
+
 // Every global read of the robot / scene constants happens here (before the first barrier).  Loads
 // are clamped instead of predicated so each loop body is one basic block (all loads issued back to
 // back, one wait), and the independent jobs start on different waves so their latencies overlap.
@@ -874,6 +888,15 @@ __device__ __forceinline__ void fused_stage_tables(const FusedCtx &c, const Fuse
                                                    const float4 *rs, int n_rec) {
   const int tid = threadIdx.x, nt = blockDim.x, nwaves = nt >> 6;
   const int H = c.H, D = c.D, L = c.L, S = c.S, P = c.P;
+  // lane = sphere form of the pair list, a straight copy: a thread's first two words are requested here, ahead of the table
+  // loads and in flight with them, and stored where the copy stands below (a wavefront that stages tables made the copy's
+  // round trips after the tables', one per word)
+  const int n_lane = (a.use_self && a.lane_lists) ? (a.lane_len0 + a.lane_len1) * 64 : 0;
+  uint32_t lane_w0 = 0u, lane_w1 = 0u;
+  if (n_lane > 0) {
+    lane_w0 = a.lane_lists[tid < n_lane ? tid : n_lane - 1];
+    lane_w1 = a.lane_lists[tid + nt < n_lane ? tid + nt : n_lane - 1];
+  }
   for (int i = tid; i < L * 4 + D * 4; i += nt) c.sub[i] = 0u;  // sub and jlinks are adjacent
   for (int i = tid; i < H * lay.wl; i += nt) c.wrench[i] = 0.0f;
   for (int i = tid; i < L * 8; i += nt) c.lbound[i] = (i & 4) ? float_key(-3.0e38f) : float_key(3.0e38f);  // empty boxes
@@ -882,7 +905,7 @@ __device__ __forceinline__ void fused_stage_tables(const FusedCtx &c, const Fuse
     int n_tab = L * 12;
     n_tab = n_tab > C ? n_tab : C;
     n_tab = n_tab > S ? n_tab : S;
-    for (int i = rotated_tid(0); i < n_tab; i += nt) {
+    staged_passes(rotated_tid(0), n_tab, nt, [&](int i) {
       const int il = i < L ? i : L - 1, ic = i < C ? i : C - 1, is = i < S ? i : (S > 0 ? S - 1 : 0);
       const int io = i <= L ? i : L, ix = i < L * 12 ? i : L * 12 - 1;
       const int v_parent = a.link_map[il], v_type = a.joint_map_type[il], v_joint = a.joint_map[il];
@@ -912,15 +935,16 @@ __device__ __forceinline__ void fused_stage_tables(const FusedCtx &c, const Fuse
         c.sph_pad[i] = v_pad;
         c.rs[i] = v_rs;
       }
-    }
+    });
   }
   // column table of the quad chain of P1 (fk_chain_quad), in the work area (dead until P1 writes the spheres)
-  for (int i = rotated_tid(nwaves > 2 ? 2 : 0); i < L * 4; i += nt)
-    fk_column_table_entry(reinterpret_cast<float4 *>(c.work), i, a.joint_map_type, a.fixed_transform);
-  if (a.use_self && a.lane_lists) {  // lane = sphere form: a straight copy
-    const int n = (a.lane_len0 + a.lane_len1) * 64;
+  staged_passes(rotated_tid(nwaves > 2 ? 2 : 0), L * 4, nt,
+                [&](int i) { fk_column_table_entry(reinterpret_cast<float4 *>(c.work), i, a.joint_map_type, a.fixed_transform); });
+  if (a.use_self && a.lane_lists) {  // lane = sphere form: the two words requested above, then the rest of a longer list
     uint32_t *dst = const_cast<uint32_t *>(c.lanel);
-    for (int k = tid; k < n; k += nt) dst[k] = a.lane_lists[k];
+    if (tid < n_lane) dst[tid] = lane_w0;
+    if (tid + nt < n_lane) dst[tid + nt] = lane_w1;
+    for (int k = tid + 2 * nt; k < n_lane; k += nt) dst[k] = a.lane_lists[k];
   } else if (a.use_self) {  // (i, j) -> byte offsets of the float4 spheres; two loads in flight per thread
     const uint32_t *g_pairs = reinterpret_cast<const uint32_t *>(a.pairs);
     for (int k = tid; k < P; k += 2 * nt) {
@@ -932,9 +956,10 @@ __device__ __forceinline__ void fused_stage_tables(const FusedCtx &c, const Fuse
     for (int k = P + tid; k < ((P + 63) & ~63); k += nt) c.pairs[k] = (uint32_t)(S * 16) | ((uint32_t)(S * 16) << 16);
   }
   if (a.use_scene)
-    for (int o = rotated_tid(nwaves - 1); o < n_rec; o += nt)
+    staged_passes(rotated_tid(nwaves - 1), n_rec, nt, [&](int o) {
       c.recs[o] = (o < a.sc.max_cuboids) ? load_rec_global<false>(a.sc, c.env, o)
                                          : load_rec_global<true>(a.sc, c.env, o - a.sc.max_cuboids);
+    });
 }
 
 // Derived tables (after the first barrier), on the last waves (the first one carries leftover
@@ -1177,6 +1202,18 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
   const bool reorder = a.dispatch_ws != nullptr;
   const int b = reorder ? a.dispatch_ws[(size_t)a.dispatch_phase * a.batch + blockIdx.x] : (int)blockIdx.x;
   const long long t_begin = reorder ? wall_clock64() : 0ll;
+  // The trajectory's load chain starts here, as soon as b is known.  First trip: its state indices, beside them the knot values
+  // of this thread's first B-spline sample, whose addresses need b, h and d only (threads without a sample request the last
+  // one's: unpredicated), and the launch-wide weights, which need nothing.  They travel while the reuse check below makes its
+  // own round trip; a copied row requested them for nothing.
+  const int nwaves = nt >> 6;
+  const int bs_e0 = rotated_tid(nwaves / 2);
+  const int bs_e0c = bs_e0 < H * D ? bs_e0 : H * D - 1, bs_h0 = bs_e0c / D, bs_d0 = bs_e0c - bs_h0 * D;
+  const int bs_bo = a.bs.start_idx[b], bs_go = a.bs.goal_idx[b];
+  float bs_knots[DEG + 1];
+  bspline_sample_knots<DEG>(a.bs, b, bs_h0, bs_d0, H, bs_knots);
+  const float ld_w_self = a.use_self ? a.w_self[0] : 0.0f, ld_w_scene = a.use_scene ? a.w_scene[0] : 0.0f;
+  const float ld_eta = a.use_scene ? a.eta[0] : 0.0f, ld_speed_dt = a.enable_speed_metric != 0 ? a.speed_dt[0] : 0.0f;
   // a trajectory the caller already holds the result of (keyed by b, never by blockIdx) ends here, its dispatch duties done
   const bool stamp_rows = (!TERMS || kStampTerms) && a.prof != nullptr;
   const long long t_known = stamp_rows ? wall_clock64() : 0ll;
@@ -1199,31 +1236,46 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
 #define CUROBO_STAMP(i) do { if ((!TERMS || kStampTerms) && a.prof && tid == 0) a.prof[(size_t)b * 16 + (i)] = wall_clock64(); } while (0)
 #endif
   CUROBO_STAMP(0);
+  // Second (and last) dependent trip, the indices having arrived: dt, the goal mode and the start / goal state components of
+  // this thread's first sample (the row a sample at its place may need: unpredicated, a sample between the boundaries reads a
+  // goal row it does not use), all requested together and ahead of the table loads, which travel with them.  Nothing that
+  // waits stands between these requests and those of fused_stage_tables; the samples below wait for nothing of their own.
+  const float ld_dt = a.bs.traj_dt[bs_go];
+  const int ld_implicit = a.bs.use_implicit_goal[bs_go];
+  float bs_state[4];
+  bspline_sample_state(a.bs, bspline_sample_state_from_start<DEG>(bs_h0, H, a.bs.n_knots), bs_bo, bs_go, bs_d0, bs_state);
   const int sph_env = a.num_envs > 1 ? a.env_query_idx[b] : 0;
   const float4 *rs = reinterpret_cast<const float4 *>(a.robot_spheres) + (size_t)sph_env * S;
-  // launch-wide scalars: loaded through the vector path, moved to SGPRs (else each occupies a VGPR
-  // for the whole kernel)
-  c.w_self = uniform_f(a.use_self ? a.w_self[0] : 0.0f);
-  c.w_scene = uniform_f(a.use_scene ? a.w_scene[0] : 0.0f);
-  c.eta = uniform_f(a.use_scene ? a.eta[0] : 0.0f);
+  // launch-wide scalars: loaded through the vector path (with the first trip, above), moved to SGPRs (else each occupies a
+  // VGPR for the whole kernel)
+  c.w_self = uniform_f(ld_w_self);
+  c.w_scene = uniform_f(ld_w_scene);
+  c.eta = uniform_f(ld_eta);
   c.speed_metric = a.enable_speed_metric != 0;
-  c.speed_dt = uniform_f(c.speed_metric ? a.speed_dt[0] : 0.0f);
+  c.speed_dt = uniform_f(ld_speed_dt);
 
   // ---------------- P0: tables + B-spline samples
-  const int nwaves = nt >> 6;
-  // (the trajectory's state indices, dt and goal mode: requested here, ahead of the table loads, used by the samples)
-  const int bs_bo = a.bs.start_idx[b], bs_go = a.bs.goal_idx[b];
-  const float bs_dt = a.bs.traj_dt[bs_go];
-  const bool bs_implicit = a.bs.use_implicit_goal[bs_go] != 0;
   fused_stage_tables(c, a, lay, rs, n_rec);
+  // (made uniform HERE, behind the staging: as scalars at their request, the wait for them stood in front of the table loads)
+  const float bs_dt = uniform_f(ld_dt);
+  const bool bs_implicit = __builtin_amdgcn_readfirstlane(ld_implicit) != 0;
   if (use_cspace) stage_cspace_tables(c, kernarg_block<CspaceStateArgs>(offsetof(FusedTrajArgs, cs)), b);
-  for (int e = rotated_tid(nwaves / 2); e < H * D; e += nt) {
-    const int h = e / D, d = e - h * D;
-    float o4[4];
-    bspline_sample_pre<DEG>(a.bs, b, h, d, a.bs.padded_horizon, bs_dt, bs_bo, bs_go, bs_implicit, o4);
+  if (tid == 0) { c.bsv[0] = bs_dt; c.bsv[1] = bs_implicit ? 1.0f : 0.0f; }  // kept for P3 (read there behind several barriers)
+  auto sample_out = [&](int e, const float *o4) {
     c.q[e] = o4[0];
     if (use_cspace) { c.dyn[e] = o4[1]; c.dyn[H * D + e] = o4[2]; c.dyn[2 * H * D + e] = o4[3]; }
     if (a.out_position) a.out_position[(size_t)b * H * D + e] = o4[0];
+  };
+  if (bs_e0 < H * D) {  // the first sample of a thread: from the values requested above
+    float o4[4];
+    bspline_sample_values<DEG>(a.bs, bs_h0, H, bs_dt, bs_implicit, bs_knots, bs_state, o4);
+    sample_out(bs_e0, o4);
+  }
+  for (int e = bs_e0 + nt; e < H * D; e += nt) {  // further samples (H D > threads) load their own
+    const int h = e / D, d = e - h * D;
+    float o4[4];
+    bspline_sample_pre<DEG>(a.bs, b, h, d, H, bs_dt, bs_bo, bs_go, bs_implicit, o4);
+    sample_out(e, o4);
   }
   __syncthreads();
   CUROBO_STAMP(1);
@@ -1600,10 +1652,9 @@ __global__ void __launch_bounds__(1024, 4) rollout_trajectory_fused_kernel(const
   // (its pointers come from the argument segment here, kernarg_block: read through `a` they are loaded at entry and stay in
   // scalar registers across the collision pass)
   const int nk = a.bs.n_knots;
-  constexpr size_t kBs = offsetof(FusedTrajArgs, bs);
-  const int go = kernarg_block<const int32_t *>(kBs + offsetof(BsFwdArgs, goal_idx))[b];
-  const float traj_dt = kernarg_block<const float *>(kBs + offsetof(BsFwdArgs, traj_dt))[go];
-  const bool use_goal = kernarg_block<const uint8_t *>(kBs + offsetof(BsFwdArgs, use_implicit_goal))[go] != 0;
+  // dt and the goal mode are the values P0 loaded (c.bsv): no global load stands in front of the VJP
+  const float traj_dt = uniform_f(c.bsv[0]);
+  const bool use_goal = uniform_f(c.bsv[1]) != 0.0f;
   float *const out_grad_knots = kernarg_block<float *>(offsetof(FusedTrajArgs, out_grad_knots));
   float *const out_cost = kernarg_block<float *>(offsetof(FusedTrajArgs, out_cost));
   const float *gin[4] = {c.q, use_cspace ? c.dyn : nullptr, use_cspace ? c.dyn + H * D : nullptr,
