@@ -1,4 +1,5 @@
-"""HIP backend for the tool-pose and c-space POSITION cost kernels.
+"""HIP backend for the tool-pose and c-space POSITION cost kernels, and for the support-polygon cost (torch code in the
+reference: ``geom/convex_polygon_helper.py``, ``cost/cost_support_polygon.py``).
 
 The reference runs these through NVIDIA Warp without a backend hook
 (``curobo/_src/cost/wp_tool_pose.py:698-914``, ``cost/wp_cspace_position.py:232-362``); the
@@ -102,6 +103,72 @@ def rollout_point_aggregate(
         ptr(out_cost), ptr(grad_q), ptr(pose_cost), ptr(cspace_cost), ptr(cspace_grad), ptr(self_cost),
         ptr(scene_cost), rows, num_links, dof, num_spheres, current_stream(out_cost),
     ))
+
+
+def rollout_point_aggregate_terms(out_cost, grad_q, pose_cost, cspace_cost, cspace_grad, self_cost, scene_cost, extra_cost,
+                                  rows: int, num_links: int, dof: int, num_spheres: int):
+    """``rollout_point_aggregate`` with one more per-row term: out_cost[r] also takes extra_cost[r] (None = none)."""
+    check(load().curobo_hip_rollout_point_aggregate_terms(
+        ptr(out_cost), ptr(grad_q), ptr(pose_cost), ptr(cspace_cost), ptr(cspace_grad), ptr(self_cost),
+        ptr(scene_cost), ptr(extra_cost), rows, num_links, dof, num_spheres, current_stream(out_cost),
+    ))
+
+
+def _f32(name: str, t: torch.Tensor, *shape) -> None:
+    """a contiguous float32 tensor of ``shape`` (None = any extent)"""
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous torch.float32 tensor, got {t.dtype}")
+    if t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
+        want = "(" + ", ".join("*" if s is None else str(s) for s in shape) + ")"
+        raise ValueError(f"{name} must have shape {want}, got {tuple(t.shape)}")
+
+
+def _i32(name: str, t: torch.Tensor, n: int) -> None:
+    if t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != (n,):
+        raise ValueError(f"{name} must be a contiguous torch.int32 tensor of shape ({n},), got {t.dtype} {tuple(t.shape)}")
+
+
+def convex_hull_2d(out_hulls: torch.Tensor, out_counts: torch.Tensor, points: torch.Tensor, padding: float = 0.0):
+    """points [N, n_pts, 2] -> out_hulls [N, n_pts, 2], out_counts [N] int32 (reference ``_compute_convex_hull_single`` per set,
+    ``geom/convex_polygon_helper.py:106-216``): counter-clockwise from the lowest vertex, padded, rows past the count repeat
+    the last vertex.  ``3 <= n_pts <= 64``."""
+    _f32("points", points, None, None, 2)
+    N, n_pts = int(points.shape[0]), int(points.shape[1])
+    if not 3 <= n_pts <= 64:  # (the launcher's own check, made before the stream is asked for)
+        raise ValueError(f"convex_hull_2d: n_pts must be in 3..64, got {n_pts}")
+    _f32("out_hulls", out_hulls, N, n_pts, 2)
+    _i32("out_counts", out_counts, N)
+    check(load().curobo_hip_convex_hull_2d(ptr(out_hulls), ptr(out_counts), ptr(points), float(padding), N, n_pts,
+                                           current_stream(out_hulls)))
+
+
+def support_polygon_cost(out_cost: torch.Tensor, out_grad_com: torch.Tensor, out_signed_distance: Optional[torch.Tensor],
+                         com: torch.Tensor, hulls: torch.Tensor, counts: Optional[torch.Tensor], idxs_hull: torch.Tensor,
+                         weight: torch.Tensor, inside_cost_weight: float, margin_target: float = 0.1,
+                         smoothing: float = 0.01, cost_mode: int = 0):
+    """com [B, H, 4] against hull ``idxs_hull[b]`` of hulls [N, M, 2] -> out_cost [B, H], out_grad_com [B, H, 4] (weight
+    applied, xy only) and out_signed_distance [B, H] or None (reference ``compute_point_hull_distance`` +
+    ``_compute_support_polygon_cost_vectorized``).  ``counts`` None: every row of a hull forms an edge (the reference's
+    padded tensor); else hull i has ``counts[i]`` vertices.  ``cost_mode`` 1: the cost is ``weight * signed distance`` itself.
+    ``M <= 32``."""
+    _f32("com", com, None, None, 4)
+    B, H = int(com.shape[0]), int(com.shape[1])
+    _f32("hulls", hulls, None, None, 2)
+    N, M = int(hulls.shape[0]), int(hulls.shape[1])
+    if not 1 <= M <= 32:
+        raise ValueError(f"support_polygon_cost: max_vertices must be in 1..32, got {M}")
+    _f32("out_cost", out_cost, B, H)
+    _f32("out_grad_com", out_grad_com, B, H, 4)
+    if out_signed_distance is not None:
+        _f32("out_signed_distance", out_signed_distance, B, H)
+    if counts is not None:
+        _i32("counts", counts, N)
+    _i32("idxs_hull", idxs_hull, B)
+    _f32("weight", weight, 1)
+    check(load().curobo_hip_support_polygon_cost(
+        ptr(out_cost), ptr(out_grad_com), ptr(out_signed_distance), ptr(com), ptr(hulls), ptr(counts), ptr(idxs_hull),
+        ptr(weight), float(inside_cost_weight), float(margin_target), float(smoothing), B, H, N, M, int(cost_mode),
+        current_stream(out_cost)))
 
 
 def cspace_state_cost(

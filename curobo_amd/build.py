@@ -40,6 +40,7 @@ SOURCES = [
     "pose_detect.hip",
     "pose_icp.hip",
     "mapper.hip",
+    "support_polygon.hip",
 ]
 
 
@@ -86,7 +87,10 @@ def _flags() -> List[str]:
 # SWEEP x voxel instantiations spill 54-60 registers with it, 2-4 without).  Off for every source.
 # self_collision.hip: the matrix-core narrow phase compares the tile results on the vector ALU, so they must land in VGPRs -- the
 # AGPR form costs a v_accvgpr_write per accumulator input and a v_accvgpr_read per output, twelve moves per 16 x 16 tile
-PER_SOURCE_FLAGS: dict = {"self_collision.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+# support_polygon.hip: the soft-min gradient divides differences of edge distances by the smoothing length (x 100), so the
+# distances are taken with the correctly rounded sqrt / divide; the kernel is a few hundred instructions per point either way
+PER_SOURCE_FLAGS: dict = {"self_collision.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+                          "support_polygon.hip": ["-fhip-fp32-correctly-rounded-divide-sqrt"]}
 NO_SLP = ["-fno-slp-vectorize"]
 
 

@@ -71,6 +71,30 @@ __global__ void __launch_bounds__(256) rollout_point_aggregate_kernel(
   if (valid && lane == 0) out_cost[grp] = acc;
 }
 
+// The same aggregation with one more per-row term (`extra_cost[r]`, e.g. the support-polygon cost of a horizon-1 rollout, whose
+// gradient has already gone through the FK VJP): a second entry so that the launch above stays what it is.
+__global__ void __launch_bounds__(256) rollout_point_aggregate_terms_kernel(
+    float *out_cost, float *grad_q, const float *pose_cost, const float *cspace_cost, const float *cspace_grad,
+    const float *self_cost, const float *scene_cost, const float *extra_cost, int rows, int num_links, int dof, int nspheres) {
+  const int grp = (blockIdx.x * blockDim.x + threadIdx.x) / 16, lane = threadIdx.x % 16;
+  const bool valid = grp < rows;
+  float acc = 0.0f;
+  if (valid) {
+    if (pose_cost)
+      for (int i = lane; i < 2 * num_links; i += 16) acc += pose_cost[(size_t)grp * 2 * num_links + i];
+    if (cspace_cost)
+      for (int i = lane; i < dof; i += 16) acc += cspace_cost[(size_t)grp * dof + i];
+    if (scene_cost)
+      for (int i = lane; i < nspheres; i += 16) acc += scene_cost[(size_t)grp * nspheres + i];
+    if (self_cost && lane == 0) acc += self_cost[grp];
+    if (extra_cost && lane == 1) acc += extra_cost[grp];
+    if (cspace_grad && grad_q)
+      for (int i = lane; i < dof; i += 16) grad_q[(size_t)grp * dof + i] += cspace_grad[(size_t)grp * dof + i];
+  }
+  acc = row16_sum(acc);
+  if (valid && lane == 0) out_cost[grp] = acc;
+}
+
 __global__ void __launch_bounds__(256) cspace_state_kernel(const CspaceStateArgs a) {
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long total = (long)a.batch * a.horizon * a.dof;
@@ -174,6 +198,22 @@ CUROBO_EXPORT int curobo_hip_rollout_point_aggregate(float *out_cost, float *gra
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(rollout_point_aggregate_kernel, dim3((unsigned)ceil_div(rows, 16)), dim3(256), 0, st, out_cost,
                      grad_q, pose_cost, cspace_cost, cspace_grad, self_cost, scene_cost, rows, num_links, dof,
+                     num_spheres);
+  return check_launch(what, st);
+}
+
+CUROBO_EXPORT int curobo_hip_rollout_point_aggregate_terms(float *out_cost, float *grad_q, const float *pose_cost,
+                                                           const float *cspace_cost, const float *cspace_grad,
+                                                           const float *self_cost, const float *scene_cost,
+                                                           const float *extra_cost, int rows, int num_links, int dof,
+                                                           int num_spheres, curobo_hip_stream_t stream) {
+  const char *what = "rollout_point_aggregate_terms";
+  CUROBO_REQUIRE(rows >= 0 && num_links >= 0 && dof >= 1 && num_spheres >= 0, "%s: bad dimensions", what);
+  CUROBO_REQUIRE(out_cost, "%s: out_cost must not be null", what);
+  if (rows == 0) return CUROBO_HIP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(rollout_point_aggregate_terms_kernel, dim3((unsigned)ceil_div(rows, 16)), dim3(256), 0, st, out_cost,
+                     grad_q, pose_cost, cspace_cost, cspace_grad, self_cost, scene_cost, extra_cost, rows, num_links, dof,
                      num_spheres);
   return check_launch(what, st);
 }

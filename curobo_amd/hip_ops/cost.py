@@ -103,3 +103,36 @@ class StateCSpaceFunction(torch.autograd.Function):
                 if ctx.needs_input_grad[i] and (i < 4 or ctx.has_effort):
                     grads[i] = g * grad_out_cost if ctx.use_grad_input else g
         return tuple(grads) + (None,) * 23
+
+
+class SupportPolygonCostFunction(torch.autograd.Function):
+    """The support-polygon balance cost (reference ``CostSupportPolygon._compute_support_polygon_cost_vectorized`` on
+    ``ConvexPolygon2DHelper.compute_point_hull_distance``, ``cost/cost_support_polygon.py:63-109``, where autograd runs through
+    ~25 elementwise launches): ``com [B, H, 4]`` (or ``[B, H, 3]``: padded) against hull ``idxs_hull[b]`` -> ``cost [B, H]`` in one
+    launch; the backward scales the ``out_grad_com`` the forward wrote.  ``counts`` None = the reference's padded hull rows."""
+
+    @staticmethod
+    def forward(ctx, com, hulls, counts, idxs_hull, weight, inside_cost_weight: float, margin_target: float, smoothing: float,
+                out_cost, out_grad_com, out_signed_distance, use_grad_input: bool = True, cost_mode: int = 0):
+        c = com.detach()
+        ctx.com_width = int(c.shape[-1])
+        if ctx.com_width != 4:
+            c = torch.nn.functional.pad(c[..., :3], (0, 4 - min(ctx.com_width, 3)))
+        c = c.contiguous()
+        check_float32_tensors(c.device, com=c, hulls=hulls, weight=weight)
+        cost_hip.support_polygon_cost(out_cost, out_grad_com, out_signed_distance, c, hulls, counts, idxs_hull, weight,
+                                      inside_cost_weight, margin_target, smoothing, cost_mode)
+        ctx.use_grad_input = use_grad_input
+        ctx.save_for_backward(out_grad_com)
+        return out_cost
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out_cost):
+        g = None
+        if grad_out_cost is not None and ctx.needs_input_grad[0]:
+            (gc,) = ctx.saved_tensors
+            g = gc * grad_out_cost.unsqueeze(-1) if ctx.use_grad_input else gc
+            if ctx.com_width != 4:
+                g = g[..., :ctx.com_width]
+        return (g,) + (None,) * 12

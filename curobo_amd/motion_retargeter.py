@@ -72,6 +72,11 @@ class MotionRetargeterCfg:
     local_ik_num_iters: Optional[int] = None
     mpc_warm_start_num_iters: int = 100
     mpc_cold_start_num_iters: int = 300
+    #: the support-polygon (balance) term of both IK solvers (``InverseKinematicsCfg``): None = off.  Fields of this dataclass
+    #: only (``dataclasses.replace(MotionRetargeterCfg.create(...), support_polygon_weight=..., foot_link_names=[...])``):
+    #: ``create`` keeps the reference's argument list
+    support_polygon_weight: Optional[float] = None
+    foot_link_names: Optional[List[str]] = None
 
     @property
     def tool_frames(self) -> List[str]:
@@ -157,7 +162,8 @@ class MotionRetargeter:
             robot=c.robot, position_tolerance=c.position_tolerance, orientation_tolerance=c.orientation_tolerance,
             self_collision_check=c.self_collision_check, scene_model=c.scene_model, override_iters_for_multi_link_ik=None,
             optimizer_configs=c.ik_optimizer_configs, device_cfg=c.device_cfg, load_collision_spheres=c.load_collision_spheres,
-            optimizer_collision_activation_distance=c.collision_activation_distance, max_batch_size=c.num_envs, **kw)
+            optimizer_collision_activation_distance=c.collision_activation_distance, max_batch_size=c.num_envs,
+            support_polygon_weight=c.support_polygon_weight, foot_link_names=c.foot_link_names, **kw)
         ik_cfg.task_cfg = retarget_ik_task_cfg()
         solver = InverseKinematics(ik_cfg)
         solver.update_tool_pose_criteria(self._tool_pose_criteria)

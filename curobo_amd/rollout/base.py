@@ -34,13 +34,14 @@ def scene_has_meshes(scene: Optional[SceneData]) -> bool:
 
 
 def fk_forward_spheres(kin: KinematicsParams, link_pos, link_quat, robot_spheres, com, cumul_mat, q, env_query_idx,
-                       n_points: int, horizon: int) -> None:
-    """q [n_points, D] -> tool-frame poses, spheres, centre of mass and the cumulative link transforms"""
+                       n_points: int, horizon: int, compute_com: bool = False) -> None:
+    """q [n_points, D] -> tool-frame poses, spheres and the cumulative link transforms; ``compute_com``: also the centre of
+    mass (xyz + total mass) into ``com``, which the launch leaves untouched otherwise"""
     k = kin
     kinematics_hip.launch_kinematics_forward_spheres(
         link_pos, link_quat, robot_spheres, com, cumul_mat, q, k.fixed_transforms, k.link_spheres, k.link_masses_com,
         k.joint_map_type, k.joint_map, k.link_map, k.tool_frame_map, k.link_sphere_idx_map, k.joint_offset_map, env_query_idx,
-        k.num_envs, n_points, horizon, k.num_dof, k.num_spheres, 32, True, False)
+        k.num_envs, n_points, horizon, k.num_dof, k.num_spheres, 32, True, compute_com)
 
 
 class BSplineHorizon:
@@ -110,19 +111,21 @@ class RobotRolloutBase:
             self.env_query_idx.copy_(env_query_idx.to(device=self.device, dtype=torch.int32).reshape(-1))
 
     # ------------------------------------------------------------------ launches
-    def _fk_forward(self, q: torch.Tensor) -> None:
+    def _fk_forward(self, q: torch.Tensor, compute_com: bool = False) -> None:
         fk_forward_spheres(self.kin, self.link_pos, self.link_quat, self.robot_spheres, self.com, self.cumul_mat, q,
-                           self.env_query_idx, self.batch_size * self._H, self._H)
+                           self.env_query_idx, self.batch_size * self._H, self._H, compute_com=compute_com)
 
-    def _fk_backward(self, grad_pos, grad_quat, sphere_grad_a, sphere_grad_b) -> None:
-        """grad_q <- the VJP of the tool-frame pose gradients and of the sum of the two sphere gradients (either may be None)"""
+    def _fk_backward(self, grad_pos, grad_quat, sphere_grad_a, sphere_grad_b, grad_com: Optional[torch.Tensor] = None) -> None:
+        """grad_q <- the VJP of the tool-frame pose gradients and of the sum of the two sphere gradients (either may be None);
+        ``grad_com`` [B, H, 4]: also of a centre-of-mass gradient (the forward must have run with ``compute_com``)"""
         k = self.kin
         kinematics_hip.launch_kinematics_backward(
-            self.grad_q, grad_pos, grad_quat, sphere_grad_a, self.com, self.com, grad_pos, self.cumul_mat, k.link_spheres,
+            self.grad_q, grad_pos, grad_quat, sphere_grad_a, self.com if grad_com is None else grad_com, self.com, grad_pos,
+            self.cumul_mat, k.link_spheres,
             k.link_masses_com, k.link_map, k.joint_map, k.joint_map_type, k.tool_frame_map, k.link_sphere_idx_map,
             k.link_chain_data, k.link_chain_offsets, k.joint_links_data, k.joint_links_offsets, k.joint_affects_endeffector,
             k.joint_offset_map, self.env_query_idx, k.num_envs, self.batch_size * self._H, self._H, self.action_dim,
-            k.num_spheres if sphere_grad_a is not None else 0, False, False, grad_spheres_b=sphere_grad_b)
+            k.num_spheres if sphere_grad_a is not None else 0, grad_com is not None, False, grad_spheres_b=sphere_grad_b)
 
     def _self_collision(self, num_blocks_per_batch: int = 1, max_threads_per_block: int = 256) -> None:
         sc = self.kin.self_collision

@@ -15,6 +15,7 @@ import torch
 
 from ..backends import cost as cost_hip
 from ..backends import rollout as rollout_hip
+from ..cost import support_polygon
 from ..robot.kinematics_params import KinematicsParams
 from ..scene.data import SceneData
 from .base import PoseTerms, RobotRolloutBase
@@ -35,10 +36,20 @@ class IKRolloutCfg:
     #: one fused launch (csrc/rollout_ik_fused.hip, rollout_ik_fused_kernel) for cost + gradient when 16
     #: configurations fit in LDS; False = the seven drop-in launches
     use_fused: bool = True
+    #: weight of the support-polygon (balance) term: the centre of mass' xy against the polygon of ``update_support_polygon``
+    #: (reference CostSupportPolygon); 0 = off, the launches are then exactly those without it.  Positive: the kernel sequence
+    #: runs (FK with the centre of mass, csrc/support_polygon.hip, the FK VJP with its gradient), not the fused launch.
+    support_polygon_weight: float = 0.0
+    #: the reference's ``inside_cost_weight``: a small pull towards the middle of the polygon while inside (0: no cost inside)
+    support_polygon_inside_cost_weight: float = 0.001
     #: weights of the implied velocity / acceleration regularisation w.r.t. the current state (reference
     #: ``squared_l2_regularization_weight`` of the c-space position cost, cost_cspace_cfg.py); read by a rollout built with
     #: ``use_current_state=True``
     squared_l2_regularization_weight: List[float] = field(default_factory=lambda: [0.0, 0.0])
+
+
+#: rows of a support polygon's fixed buffer (the cost launch's limit)
+SUPPORT_POLYGON_CAPACITY = support_polygon.MAX_HULL_VERTICES
 
 
 class IKRollout(PoseTerms, RobotRolloutBase):
@@ -71,12 +82,19 @@ class IKRollout(PoseTerms, RobotRolloutBase):
             self._acc_reg = float(c.squared_l2_regularization_weight[1]) > 0.0
             self._cur_pos, self._cur_vel, self._state_dt = torch.zeros(1, D, device=d), torch.zeros(1, D, device=d), torch.zeros(1, device=d)
         self._env_runs_ok = True  # env_query_idx constant over aligned runs of 16 rows (update_env_query_idx)
+        self._use_support_polygon = float(c.support_polygon_weight) > 0.0
+        if self._use_support_polygon:
+            self._w_sp = f([c.support_polygon_weight])
+            self._sp_hulls, self._sp_counts, self._sp_set = None, None, False
         self.update_batch_size(batch_size)
 
     def _alloc(self, B: int) -> None:
         self._alloc_robot_buffers(B, 1)
         self._alloc_pose_buffers(B, 1, self.num_goalset)
         self.cspace_cost, self.cspace_grad = self._zeros(B, 1, self.action_dim), self._zeros(B, 1, self.action_dim)
+        if self._use_support_polygon:
+            self.sp_cost, self.sp_grad, self.sp_distance = self._zeros(B, 1), self._zeros(B, 1, 4), self._zeros(B, 1)
+            self._sp_idxs = self._zeros(B, dt=torch.int32)
         self._idxs_src = None  # (the row -> goal map was reallocated: the next update_goals must copy, whatever tensor it is handed)
         self._idxs_cur, self._idxs_cur_src = self._zeros(B, dt=torch.int32), None  # row -> current state
 
@@ -133,6 +151,40 @@ class IKRollout(PoseTerms, RobotRolloutBase):
         else:
             self._state_dt.fill_(float(dt))
 
+    def update_support_polygon(self, vertices_xy: torch.Tensor, idxs: Optional[torch.Tensor] = None,
+                               padding: float = support_polygon.DEFAULT_PADDING) -> None:
+        """vertices_xy [P, n, 2] (3 <= n <= 64: e.g. the xy of the foot spheres of P stances), idxs [B]: row b is held over
+        polygon idxs[b] (kept when None; all rows over polygon 0 at first).  One launch builds the P hulls (padded by ``padding``)
+        into a buffer of SUPPORT_POLYGON_CAPACITY rows per polygon plus their vertex counts, so a captured graph stays valid
+        when the polygon changes, as long as P does not (a new P allocates: re-capture).  Never call it inside a capture."""
+        if not self._use_support_polygon:
+            raise ValueError("update_support_polygon: the rollout was built with support_polygon_weight = 0")
+        v = torch.as_tensor(vertices_xy).to(self.device, torch.float32)
+        if v.dim() != 3 or v.shape[-1] != 2:
+            raise ValueError(f"update_support_polygon: vertices_xy must be (P, n, 2), got {tuple(v.shape)}")
+        P, n, cap = int(v.shape[0]), int(v.shape[1]), SUPPORT_POLYGON_CAPACITY
+        hulls, counts = support_polygon.convex_hulls(v, padding)
+        if n > cap and int(counts.max()) > cap:
+            raise ValueError(f"update_support_polygon: a hull has {int(counts.max())} vertices, at most {cap} fit")
+        if self._sp_hulls is None or self._sp_hulls.shape[0] != P:
+            self._sp_hulls, self._sp_counts = self._zeros(P, cap, 2), self._zeros(P, dt=torch.int32)
+            self._sp_idxs.zero_()  # (indices into the old polygons may be out of range now)
+        self._sp_hulls[:, :min(n, cap)].copy_(hulls[:, :cap])
+        self._sp_counts.copy_(counts)
+        if idxs is not None:
+            if idxs.numel() != self.batch_size or int(idxs.min()) < 0 or int(idxs.max()) >= P:
+                raise ValueError(f"update_support_polygon: idxs must hold {self.batch_size} polygon indices in [0, {P})")
+            self._sp_idxs.copy_(idxs.to(device=self.device, dtype=torch.int32).reshape(-1))
+        self._sp_set = True
+
+    def _support_polygon_term(self) -> None:
+        """com -> sp_cost [B, 1], sp_grad [B, 1, 4] (weighted, what the FK VJP takes) and sp_distance [B, 1]"""
+        if not self._sp_set:
+            raise ValueError("support_polygon_weight > 0 but no polygon is set: call update_support_polygon first")
+        cost_hip.support_polygon_cost(self.sp_cost, self.sp_grad, self.sp_distance, self.com, self._sp_hulls, self._sp_counts,
+                                      self._sp_idxs, self._w_sp, self.cfg.support_polygon_inside_cost_weight,
+                                      support_polygon.MARGIN_TARGET, support_polygon.SMOOTHING)
+
     def _state_args(self):
         """(regularisation weights, current position, current velocity, row -> state, dt per state) of the c-space term; without
         a current state: the zeros that switch the terms off"""
@@ -144,7 +196,8 @@ class IKRollout(PoseTerms, RobotRolloutBase):
     def evaluate(self, q: torch.Tensor, with_gradient: bool = True) -> torch.Tensor:
         k, B = self.kin, self.batch_size
         T, S, D = k.num_pose_links, k.num_spheres, k.num_dof
-        self._fk_forward(q)
+        sp = self._use_support_polygon
+        self._fk_forward(q, compute_com=sp)
         self._pose_term()
         reg, cur_pos, cur_vel, idxs_cur, state_dt = self._state_args()
         cost_hip.cspace_position_cost(
@@ -155,6 +208,16 @@ class IKRollout(PoseTerms, RobotRolloutBase):
         use_scene = self.scene is not None
         if use_scene:
             self._scene_collision()
+        if sp:
+            self._support_polygon_term()
+            if with_gradient:
+                self._fk_backward(self.pose_grad_pos, self.pose_grad_quat, self.self_grad, self.scene_grad if use_scene else None,
+                                  grad_com=self.sp_grad)
+            cost_hip.rollout_point_aggregate_terms(
+                self.cost, self.grad_q if with_gradient else None, self.pose_cost, self.cspace_cost,
+                self.cspace_grad if with_gradient else None, self.self_dist, self.scene_dist if use_scene else None,
+                self.sp_cost, B, T, D, S)
+            return self.cost
         if with_gradient:
             self._fk_backward(self.pose_grad_pos, self.pose_grad_quat, self.self_grad, self.scene_grad if use_scene else None)
         cost_hip.rollout_point_aggregate(
@@ -195,7 +258,7 @@ class IKRollout(PoseTerms, RobotRolloutBase):
 
     def cost_and_gradient(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """x[B, D] -> (cost[B], grad[B, D]) in static buffers (graph friendly)."""
-        if (self.cfg.use_fused and (self._env_runs_ok or not (self.use_multi_env or self.kin.num_envs > 1))
+        if (self.cfg.use_fused and not self._use_support_polygon and (self._env_runs_ok or not (self.use_multi_env or self.kin.num_envs > 1))
                 and self._fused_chosen()):
             return self.cost_and_gradient_fused(x.view(self.batch_size, self.action_dim).contiguous())
         cost = self.evaluate(x.view(self.batch_size, 1, self.action_dim), with_gradient=True)

@@ -76,6 +76,9 @@ class IKResult:
     cost: torch.Tensor  # [P]
     seed_index: torch.Tensor  # [P] global seed index of the winner
     goalset_index: Optional[torch.Tensor] = None  # [P, T] member of the goal set the solution reaches, per tool frame
+    #: [P] signed distance [m] of the solution's centre of mass (xy) to its support polygon, negative inside; None when the
+    #: support-polygon term is off (``rollout.support_polygon_weight`` = 0)
+    support_polygon_distance: Optional[torch.Tensor] = None
 
 
 class IKSolver:
@@ -199,6 +202,26 @@ class IKSolver:
             position, velocity, dt = self._cur_buf, None, None
         for ro, rows in zip(self.rollouts + [self.metrics_rollout], self._row_goals + [self._mrow_goal]):
             ro.update_current_state(position, velocity, dt, rows)
+
+    @property
+    def _sp_on(self) -> bool:
+        return float(self.cfg.rollout.support_polygon_weight) > 0.0
+
+    def update_support_polygon(self, vertices_xy: torch.Tensor, padding: float = 0.05) -> None:
+        """vertices_xy [1 | P, n, 2]: the points (e.g. the xy of the stance feet's spheres) whose padded convex hull the centre
+        of mass is held over, one set for all problems or one per problem; written into the fixed buffers of every rollout
+        (``IKRollout.update_support_polygon``), so the captured graphs stay valid unless the number of sets changes"""
+        if not self._sp_on:
+            raise ValueError("update_support_polygon: the solver was built with rollout.support_polygon_weight = 0")
+        v = torch.as_tensor(vertices_xy).to(self.device, torch.float32)
+        if v.dim() != 3 or int(v.shape[0]) not in (1, self.P):
+            raise ValueError(f"update_support_polygon: vertices_xy must be (1 | {self.P}, n, 2), got {tuple(v.shape)}")
+        n_sets = int(v.shape[0])
+        if getattr(self, "_sp_sets", n_sets) != n_sets:
+            self._drop_captures()  # (the rollouts allocate buffers for the new number of polygons)
+        self._sp_sets = n_sets
+        for ro, rows in zip(self.rollouts + [self.metrics_rollout], self._row_goals + [self._mrow_goal]):
+            ro.update_support_polygon(v, None if n_sets == 1 else rows, padding)  # (rows: the global problem of every row)
 
     def reset_seed(self) -> None:
         """reference ``reset_seed``: rewind the Halton index stream of the LM seed stage, so that the next solve starts from
@@ -334,7 +357,9 @@ class IKSolver:
 
             views = _unpack_like(out._pack_views, pack.clone())
             sq = (lambda x: x) if return_seeds > 1 else (lambda x: x[:, 0])  # noqa: E731
-            return IKResult(**{f: sq(v) for f, v in zip(fields, views)})
+            spd = out.support_polygon_distance
+            return IKResult(**{f: sq(v) for f, v in zip(fields, views)}, support_polygon_distance=None if spd is None else spd.clone())
+        fields += ("support_polygon_distance",)
         return IKResult(**{f: (getattr(out, f).clone() if getattr(out, f) is not None else None) for f in fields})
 
     def _get_result_eager(self, q: torch.Tensor, return_seeds: int) -> IKResult:
@@ -350,6 +375,10 @@ class IKSolver:
             cost = m.pose_pos_dist.view(P * S, T).sum(-1) + m.pose_rot_dist.view(P * S, T).sum(-1) + 0.5 * self._cur_w * near
         import torch.distributed as dist
 
+        # the support-polygon term on: a seed whose centre of mass is outside its polygon (signed distance > 0) is infeasible,
+        # next to the self, scene and c-space checks; folded into the self-collision row the ranking reads (both are >= 0)
+        sp_dist = m.sp_distance.view(P, S) if self._sp_on else None
+        self_dist = m.self_dist.view(P * S) if sp_dist is None else m.self_dist.view(P * S) + sp_dist.reshape(P * S).clamp_min(0.0)
         if not (dist.is_available() and dist.is_initialized()) and S <= 1024 and return_seeds <= S:
             # alone in the process: feasibility, success and the ranked winners in one launch (the winner exchange
             # below is only needed across ranks)
@@ -363,7 +392,7 @@ class IKSolver:
                 dev, [((P, k), torch.uint8), ((P, k, D), torch.float32), ((P, k), torch.float32), ((P, k), torch.float32),
                       ((P, k), torch.float32), ((P, k), torch.int64), ((P, k, T), torch.int64)])
             linalg_hip.ik_rank(ok_o, sol_o, pe_o, re_o, c_o, si_o, gi_o, q.view(P * S, D), cost.view(P * S), m.pose_pos_dist.view(P * S, T),
-                               m.pose_rot_dist.view(P * S, T), m.self_dist.view(P * S), m.cspace_cost.view(P * S, D),
+                               m.pose_rot_dist.view(P * S, T), self_dist, m.cspace_cost.view(P * S, D),
                                m.scene_dist if self.scene is not None else None, m.goalset_idx.view(P * S, T),
                                self.cfg.position_threshold, self.cfg.rotation_threshold, P, S, k, self.seed_offset)
             sq = (lambda x: x) if k > 1 else (lambda x: x[:, 0])  # noqa: E731
@@ -371,10 +400,12 @@ class IKSolver:
             res = IKResult(success=sq(ok_b), solution=sq(sol_o), position_error=sq(pe_o), rotation_error=sq(re_o),
                            cost=sq(c_o), seed_index=sq(si_o), goalset_index=sq(gi_o))
             res._packed, res._pack_views = True, [ok_b, sol_o, pe_o, re_o, c_o, si_o, gi_o]
+            if sp_dist is not None:
+                res.support_polygon_distance = sq(sp_dist.gather(1, (si_o - self.seed_offset).clamp(0, S - 1)))
             return res
         pos_all, rot_all = m.pose_pos_dist.view(P, S, T), m.pose_rot_dist.view(P, S, T)
         pos_err, rot_err = pos_all.max(-1).values, rot_all.max(-1).values  # the largest error over the tool frames
-        feasible = (m.self_dist.view(P, S) <= 0.0) & (m.cspace_cost.view(P, S, D).sum(-1) <= 0.0)
+        feasible = (self_dist.view(P, S) <= 0.0) & (m.cspace_cost.view(P, S, D).sum(-1) <= 0.0)
         if self.scene is not None:
             feasible &= m.scene_dist.view(P, S, -1).sum(-1) <= 0.0
         # converged on every tool frame (reference: torch.all over the per-link convergence list, solver_ik.py:463-476)
@@ -382,13 +413,12 @@ class IKSolver:
         ranked = cost.view(P, S) + 1e16 * (~ok).float()  # reference solver_ik.py:503-509
         gidx = m.goalset_idx.view(P, S, T).float()
         payload = torch.cat([q.view(P, S, D), pos_err.unsqueeze(-1), rot_err.unsqueeze(-1), ok.float().unsqueeze(-1),
-                             cost.view(P, S, 1), gidx], dim=-1)
+                             cost.view(P, S, 1), gidx] + ([sp_dist.unsqueeze(-1)] if sp_dist is not None else []), dim=-1)
         if return_seeds > 1:
             _, idx, win = global_topk(ranked, payload, self.seed_offset, return_seeds)
-            return IKResult(success=win[..., D + 2] > 0.5, solution=win[..., :D], position_error=win[..., D],
-                            rotation_error=win[..., D + 1], cost=win[..., D + 3], seed_index=idx,
-                            goalset_index=win[..., D + 4:D + 4 + T].long())
-        _, idx, win = global_argmin(ranked, payload, self.seed_offset)
-        return IKResult(success=win[:, D + 2] > 0.5, solution=win[:, :D], position_error=win[:, D],
-                        rotation_error=win[:, D + 1], cost=win[:, D + 3], seed_index=idx,
-                        goalset_index=win[:, D + 4:D + 4 + T].long())
+        else:
+            _, idx, win = global_argmin(ranked, payload, self.seed_offset)
+        return IKResult(success=win[..., D + 2] > 0.5, solution=win[..., :D], position_error=win[..., D],
+                        rotation_error=win[..., D + 1], cost=win[..., D + 3], seed_index=idx,
+                        goalset_index=win[..., D + 4:D + 4 + T].long(),
+                        support_polygon_distance=win[..., D + 4 + T] if sp_dist is not None else None)

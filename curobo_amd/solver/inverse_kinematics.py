@@ -38,8 +38,10 @@ class InverseKinematicsResult:
     orientation_tolerance: float = 0.0
     batch_size: int = 0
     num_seeds: int = 0
+    #: [batch, return_seeds] signed distance [m] of the centre of mass to the support polygon (negative inside); None = term off
+    support_polygon_distance: Optional[torch.Tensor] = None
 
-    _TENSORS = ("success", "solution", "position_error", "rotation_error", "goalset_index")
+    _TENSORS = ("success", "solution", "position_error", "rotation_error", "goalset_index", "support_polygon_distance")
 
     def clone(self) -> "InverseKinematicsResult":
         """deep copy (reference BaseSolverResult.clone, solver_base_result.py:81-131)"""
@@ -119,6 +121,10 @@ class InverseKinematicsCfg:
     #: retargeter's ``lbfgs_retarget_ik.yml`` values); None = ``lbfgs_ik.yml``'s, the defaults of ``IKSolverCfg``.  The fields
     #: above are applied on top of a copy
     task_cfg: Optional[IKSolverCfg] = None
+    #: weight of the support-polygon (balance) term, reference CostSupportPolygon: the centre of mass' xy is held over the padded
+    #: hull of the spheres of ``foot_link_names`` in a stance (``InverseKinematics.update_support_polygon``); None / 0 = off
+    support_polygon_weight: Optional[float] = None
+    foot_link_names: Optional[List[str]] = None
 
     @staticmethod
     def create(robot: Union[str, Dict], scene_model: Union[str, Dict, List, None] = None, num_seeds: int = 32,
@@ -129,7 +135,9 @@ class InverseKinematicsCfg:
                override_iters_for_multi_link_ik: Optional[int] = None, optimization_dt: Optional[float] = None,
                velocity_regularization_weight: Optional[float] = None,
                acceleration_regularization_weight: Optional[float] = None,
-               override_optimizer_num_iters: Optional[Dict[str, Optional[int]]] = None, **unused) -> "InverseKinematicsCfg":
+               override_optimizer_num_iters: Optional[Dict[str, Optional[int]]] = None,
+               support_polygon_weight: Optional[float] = None, foot_link_names: Optional[List[str]] = None,
+               **unused) -> "InverseKinematicsCfg":
         """``robot``: packaged name (``"franka.yml"``), a robot yaml path or its dictionary.  ``scene_model``: the
         reference's scene format (see ``curobo_amd.scene.config``).  Keyword arguments of the reference this backend has
         no use for (``optimizer_configs``, ``metrics_rollout``, ``transition_model``, ...) are accepted and ignored: the
@@ -155,7 +163,8 @@ class InverseKinematicsCfg:
             max_batch_size=max_batch_size, max_goalset=max_goalset, override_iters_for_multi_link_ik=override_iters_for_multi_link_ik,
             optimization_dt=optimization_dt, velocity_regularization_weight=velocity_regularization_weight,
             acceleration_regularization_weight=acceleration_regularization_weight,
-            override_optimizer_num_iters=override_optimizer_num_iters)
+            override_optimizer_num_iters=override_optimizer_num_iters, support_polygon_weight=support_polygon_weight,
+            foot_link_names=None if foot_link_names is None else list(foot_link_names))
 
 
 class InverseKinematics(ToolPoseTrackingMixin):
@@ -261,6 +270,45 @@ class InverseKinematics(ToolPoseTrackingMixin):
         for s in self._solvers.values():
             s.update_tool_pose_criteria(tool_pose_criteria)
 
+    def update_support_polygon(self, joint_state: Optional[Union[JointState, torch.Tensor]] = None,
+                               vertices: Optional[torch.Tensor] = None, padding: float = 0.05) -> None:
+        """The polygon the centre of mass is held over (``config.support_polygon_weight`` > 0): the padded convex hull of
+        ``vertices`` [1 | batch, n, 2], else of the xy of the spheres (radius > 0) of ``config.foot_link_names`` in the stance
+        ``joint_state`` [1 | batch, dof] (default: the robot's default joint position, which is also what a solver uses when this
+        was never called).  In place on the solvers that exist, and kept for the ones built later."""
+        w = self.config.support_polygon_weight
+        if w is None and self.config.task_cfg is not None:
+            w = self.config.task_cfg.rollout.support_polygon_weight
+        if not (w and w > 0):
+            raise ValueError("update_support_polygon: the configuration has no support_polygon_weight")
+        if vertices is None:
+            kc = self.config.kinematics.kinematics_config
+            names, feet = list(kc.link_names), list(self.config.foot_link_names or [])
+            missing = [n for n in feet if n not in names]
+            if not feet or missing:
+                raise ValueError(f"update_support_polygon: foot_link_names {feet} must name links of the robot (missing: {missing})")
+            q = self.default_joint_position if joint_state is None else (
+                joint_state.position if hasattr(joint_state, "position") else joint_state)
+            q = q.to(kc.device, torch.float32).reshape(-1, self.dof)
+            spheres = self.compute_kinematics(q).robot_spheres[:, 0]  # [n, S, 4]
+            link_of = kc.link_sphere_idx_map.to(torch.long)
+            on_foot = torch.zeros_like(link_of, dtype=torch.bool)
+            for n in feet:
+                on_foot |= link_of == names.index(n)
+            on_foot &= spheres[0, :, 3] > 0
+            if not 3 <= int(on_foot.sum()) <= 64:
+                raise ValueError(f"update_support_polygon: {int(on_foot.sum())} foot spheres; the hull takes 3 to 64 points")
+            vertices = spheres[:, on_foot, :2]
+        self._support_vertices = (torch.as_tensor(vertices).detach().clone(), float(padding))
+        for s in self._solvers.values():
+            self._apply_support_polygon(s)
+
+    def _apply_support_polygon(self, solver: IKSolver) -> None:
+        v, padding = self._support_vertices
+        if int(v.shape[0]) not in (1, solver.P):
+            raise ValueError(f"update_support_polygon: {int(v.shape[0])} stances for a batch of {solver.P} (one, or one per problem)")
+        solver.update_support_polygon(v, padding)
+
     def destroy(self) -> None:
         self._solvers.clear()
         self._checker = None
@@ -287,7 +335,13 @@ class InverseKinematics(ToolPoseTrackingMixin):
             cfg.rollout.scene_activation_distance = c.optimizer_collision_activation_distance
             if not c.self_collision_check:
                 cfg.rollout.self_collision_weight = 0.0
+            if c.support_polygon_weight is not None:  # (None keeps the task value: off)
+                cfg.rollout.support_polygon_weight = float(c.support_polygon_weight)
             self._solvers[batch] = IKSolver(c.kinematics.kinematics_config, c.scene, batch, cfg, use_cuda_graph=c.use_cuda_graph)
+            if cfg.rollout.support_polygon_weight > 0:
+                if getattr(self, "_support_vertices", None) is None:
+                    self.update_support_polygon()  # the stance of the default joint position
+                self._apply_support_polygon(self._solvers[batch])
             if getattr(self, "_criteria", None):
                 self._solvers[batch].update_tool_pose_criteria(self._criteria)
         return self._solvers[batch]
@@ -336,4 +390,5 @@ class InverseKinematics(ToolPoseTrackingMixin):
             goalset_index=None if r.goalset_index is None else r.goalset_index.reshape(B, k, T), solve_time=self.solve_time,
             debug_info={"optimizer_ran": bool(getattr(slv, "optimizer_ran", True))}, total_time=self.solve_time,
             position_tolerance=self.config.position_tolerance, orientation_tolerance=self.config.orientation_tolerance, batch_size=B,
-            num_seeds=self.config.num_seeds)
+            num_seeds=self.config.num_seeds,
+            support_polygon_distance=None if r.support_polygon_distance is None else r.support_polygon_distance.reshape(B, k))

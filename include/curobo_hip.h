@@ -372,6 +372,38 @@ int curobo_hip_rollout_point_aggregate(
     const float *cspace_grad, const float *self_cost, const float *scene_cost, int rows,
     int num_links, int dof, int num_spheres, curobo_hip_stream_t stream);
 
+/* The same with one more per-row term: out_cost[r] += extra_cost[r] (NULL = none), e.g. the support-polygon cost below. */
+int curobo_hip_rollout_point_aggregate_terms(
+    float *out_cost, float *grad_q, const float *pose_cost, const float *cspace_cost,
+    const float *cspace_grad, const float *self_cost, const float *scene_cost, const float *extra_cost,
+    int rows, int num_links, int dof, int num_spheres, curobo_hip_stream_t stream);
+
+/* ---------------------------------------------------------------- support polygon (balance) cost
+ * reference (torch ops, no backend hook): geom/convex_polygon_helper.py:63-336, cost/cost_support_polygon.py:35-109.
+ *
+ * convex_hull_2d: points [n_hulls, n_pts, 2] -> hulls [n_hulls, n_pts, 2], counts [n_hulls].  The strictly convex vertices
+ * counter-clockwise from the lowest one (leftmost on a tie); a vertex whose turn is <= 1e-10 is dropped; every vertex then
+ * moves by `padding` (> 0) along the unit vector from the vertex mean; rows past counts[i] repeat the last vertex.
+ * 3 <= n_pts <= 64.
+ *
+ * support_polygon_cost: com [batch, horizon, 4] (xyz + total mass: the FK launches' centre-of-mass buffer), hulls
+ * [n_hulls, max_vertices, 2], idxs_hull [batch] (row b -> hull), weight [1] -> cost [batch, horizon], grad_com
+ * [batch, horizon, 4] (d cost / d com: xy filled, z and w zero, weight applied: what launch_kinematics_backward takes as
+ * grad_center_of_mass) and, unless NULL, signed_distance [batch, horizon] (negative inside).  The distance is the
+ * soft-min (softmax(-d / smoothing)) of the distances to the hull's edges.  counts NULL: all max_vertices rows form edges,
+ * repeated rows included (the reference's padded tensor); else hull i uses its first counts[i] rows.
+ * inside_cost_weight > 0: inside costs inside_cost_weight * max(margin_target + sd, 0), outside sd; else max(sd, 0).
+ * cost_mode 1: cost = weight * sd and grad_com its gradient (the distance query of the reference's helper); 0: the cost.
+ * max_vertices <= 32. */
+int curobo_hip_convex_hull_2d(float *hulls, int32_t *counts, const float *points, float padding, int n_hulls,
+                              int n_pts, curobo_hip_stream_t stream);
+
+int curobo_hip_support_polygon_cost(float *cost, float *grad_com, float *signed_distance, const float *com,
+                                    const float *hulls, const int32_t *counts, const int32_t *idxs_hull,
+                                    const float *weight, float inside_cost_weight, float margin_target,
+                                    float smoothing, int batch_size, int horizon, int n_hulls,
+                                    int max_vertices, int cost_mode, curobo_hip_stream_t stream);
+
 /* ---------------------------------------------------------------- dynamics: RNEA
  * reference: cuda_core_backend/dynamics.py:24-131,134-260
  * kernels:   kernels/dynamics/rnea_forward_kernel.cuh:53-292, rnea_backward_kernel.cuh:65-468
