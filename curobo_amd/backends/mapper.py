@@ -249,3 +249,58 @@ def mapper_mesh_compact(triangles: torch.Tensor, raw_triangles: torch.Tensor, ke
                   keep=(keep, torch.uint8, n_raw, 1), keep_offset=(keep_offset, torch.int32, n_raw, 1))
     check(load().curobo_hip_mapper_mesh_compact(ptr(triangles), n, ptr(raw_triangles), ptr(keep), ptr(keep_offset), n_raw,
                                                 current_stream(triangles)))
+
+
+# ---------------------------------------------------------------------------------------------------- raycast (csrc/mapper_raycast.hip)
+def _require_camera(intrinsics: torch.Tensor, position: torch.Tensor, quaternion: torch.Tensor, what: str, like: torch.Tensor) -> None:
+    for name, t, n in (("intrinsics", intrinsics, 9), ("position", position, 3), ("quaternion", quaternion, 4)):
+        _require(t, name, torch.float32, like)
+        if t.numel() != n:
+            raise ValueError(f"{what}: {name} must hold {n} values, got {tuple(t.shape)}")
+
+
+def mapper_raycast(hit_points: torch.Tensor, hit_normals: torch.Tensor, hit_depths: torch.Tensor, hit_mask: torch.Tensor,
+                   intrinsics: torch.Tensor, position: torch.Tensor, quaternion: torch.Tensor, block_data: torch.Tensor,
+                   block_mask: torch.Tensor, params: MapperParams, minimum_tsdf_weight: float, depth_minimum_distance: float,
+                   depth_maximum_distance: float, image_shape: Sequence[int], accelerated: bool, z_depth: bool = False) -> None:
+    """``curobo_hip_mapper_raycast``: one ray per pixel of an ``(H, W)`` image from the camera ``intrinsics`` [3, 3], ``position`` [3],
+    ``quaternion`` [4] wxyz (device tensors) -> hit_points, hit_normals float32 [H W, 3], hit_depths float32 [H W] (range along the
+    ray; ``z_depth``: along the camera's axis), hit_mask uint8 [H W], all zero on a miss"""
+    what = "mapper_raycast"
+    h, w = (int(v) for v in image_shape)
+    _require_map(params, what, block_data, block_mask=block_mask)
+    _require_camera(intrinsics, position, quaternion, what, block_data)
+    _require_rows(what, block_data, hit_points=(hit_points, torch.float32, h * w, 3), hit_normals=(hit_normals, torch.float32, h * w, 3),
+                  hit_depths=(hit_depths, torch.float32, h * w, 1), hit_mask=(hit_mask, torch.uint8, h * w, 1))
+    check(load().curobo_hip_mapper_raycast(ptr(hit_points), ptr(hit_normals), ptr(hit_depths), ptr(hit_mask), ptr(intrinsics), ptr(position),
+                                           ptr(quaternion), ptr(block_data), ptr(block_mask), _C.addressof(params), float(minimum_tsdf_weight),
+                                           float(depth_minimum_distance), float(depth_maximum_distance), h, w, int(bool(accelerated)),
+                                           int(bool(z_depth)), current_stream(hit_depths)))
+
+
+def ray_align_samples(image_shape: Sequence[int], stride: int, n_samples_per_ray: int) -> int:
+    """how many samples ``mapper_ray_align`` evaluates: ceil(H / stride) ceil(W / stride) n_samples_per_ray -- the ``n_points`` of
+    ``pose_sdf_ws_bytes`` and ``pose_lm_step`` for its workspace"""
+    h, w = (int(v) for v in image_shape)
+    return -(-h // int(stride)) * -(-w // int(stride)) * int(n_samples_per_ray)
+
+
+def mapper_ray_align(workspace: torch.Tensor, depth: torch.Tensor, intrinsics: torch.Tensor, position: torch.Tensor,
+                     quaternion: torch.Tensor, block_data: torch.Tensor, block_mask: torch.Tensor, params: MapperParams,
+                     minimum_tsdf_weight: float, depth_minimum_distance: float, depth_maximum_distance: float, distance_threshold: float,
+                     stride: int, n_samples_per_ray: int) -> None:
+    """``curobo_hip_mapper_ray_align``: the along-ray SDF residuals of ``depth`` [H, W] at the pose ``position`` [3] / ``quaternion`` [4]
+    wxyz on the device -> one row of partial sums per workgroup of 256 samples in ``workspace``, for ``pose_lm_step``"""
+    what = "mapper_ray_align"
+    if depth.dim() != 2:
+        raise ValueError(f"{what}: depth must be (H, W), got {tuple(depth.shape)}")
+    _require(depth, "depth", torch.float32)
+    _require_map(params, what, block_data, like=depth, block_mask=block_mask)
+    _require_camera(intrinsics, position, quaternion, what, depth)
+    if not workspace.is_contiguous() or workspace.device != depth.device:
+        raise ValueError(f"{what}: workspace must be a contiguous tensor on depth's device")
+    check(load().curobo_hip_mapper_ray_align(ptr(workspace), int(workspace.numel() * workspace.element_size()), ptr(depth), ptr(intrinsics),
+                                             ptr(position), ptr(quaternion), ptr(block_data), ptr(block_mask), _C.addressof(params),
+                                             float(minimum_tsdf_weight), float(depth_minimum_distance), float(depth_maximum_distance),
+                                             float(distance_threshold), int(depth.shape[0]), int(depth.shape[1]), int(stride),
+                                             int(n_samples_per_ray), current_stream(depth)))

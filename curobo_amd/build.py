@@ -24,7 +24,7 @@ OBJ_DIR = os.path.join(_PKG, "build")
 ARCH = "gfx950"
 
 HEADERS = ["common.hpp", "cost_device.hpp", "scene_device.hpp", "fk_device.hpp", "self_device.hpp",
-           "bspline_device.hpp", "dynamics_device.hpp", "mesh_device.hpp", "pose_device.hpp", "fused_shapes.hpp", "fused_device.hpp",
+           "bspline_device.hpp", "dynamics_device.hpp", "mesh_device.hpp", "pose_device.hpp", "mapper_device.hpp", "fused_shapes.hpp", "fused_device.hpp",
            "tail_shapes.hpp"]
 
 SOURCES = [
@@ -40,6 +40,7 @@ SOURCES = [
     "pose_detect.hip",
     "pose_icp.hip",
     "mapper.hip",
+    "mapper_raycast.hip",
     "support_polygon.hip",
 ]
 

@@ -26,7 +26,9 @@
 // after x of the grid (the squared distance separates by axis).  Within a pass the site of the line's cell j keeps j as its
 // coordinate along the line, so the pass is min_j (d2(j) + (i - j)^2) with d2(j) the squared distance of cell j to its own
 // site: d2 of a tile of lines is staged in LDS once and every cell scans its line by brute force, in integers.
-#include "common.hpp"
+//
+// The grid, the fp16 pair's halves and the TSDF reads of the mesh launches are mapper_device.hpp's: mapper_raycast.hip shares them.
+#include "mapper_device.hpp"
 
 namespace curobo_hip {
 
@@ -35,29 +37,16 @@ constexpr int kEdtThreads = 256;
 constexpr int kEdtLdsWords = 8192;        // 32 KB: columns per tile = min(64, kEdtLdsWords / line length)
 constexpr int kEdtNoSite = 1 << 30;       // above 3 * 1023^2 + 1023^2; kEdtNoSite + 1023^2 does not overflow
 constexpr int kEsdfMaxAxis = 1024;        // sites pack 10 bits per axis
-constexpr float kSdfInvalid = 1e10f;      // wp_tsdf_sample.py SDF_INFINITY as the lookups return it
-
-struct MapGrid {
-  int grid_w, grid_h, grid_d, bs, nbx, nby, nbz, num_samples;
-  float ox, oy, oz, vs, trunc, depth_min, depth_max, min_weight, step;
-};
 
 struct MapCameras {
   const float *depth, *intrinsics, *position, *quaternion;
   int n, height, width;
 };
 
-// wp.quat_rotate for q = (w, v): x (2 w^2 - 1) + 2 w (v x x) + 2 v (v . x)
-__device__ __forceinline__ f3 quat_rotate(float w, f3 v, f3 x) {
-  return (2.0f * w * w - 1.0f) * x + (2.0f * w) * cross(v, x) + (2.0f * dot(v, x)) * v;
-}
-
 __device__ __forceinline__ uint32_t pack_half2(float a, float b) {
   const _Float16 ha = (_Float16)a, hb = (_Float16)b;  // round to nearest even
   return (uint32_t)__builtin_bit_cast(uint16_t, ha) | ((uint32_t)__builtin_bit_cast(uint16_t, hb) << 16);
 }
-__device__ __forceinline__ float half_lo(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(v & 0xffffu)); }
-__device__ __forceinline__ float half_hi(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(v >> 16)); }
 
 // ---------------------------------------------------------------------------------------------------- frame mask
 __global__ __launch_bounds__(kMapThreads) void mapper_clear_mask_kernel(uint32_t *mask, int64_t n_words) {
@@ -292,70 +281,6 @@ struct MeshArgs {
   float level;
 };
 
-// the stored sdf of voxel (gx, gy, gz) of the PADDED grid, kSdfInvalid where there is no such voxel, its block was never
-// visible or its weight is below the minimum (>=: builder_raycast.py:78, the lookups of the mesh and the renderer)
-__device__ __forceinline__ float mesh_voxel(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, int gx, int gy, int gz) {
-  if (gx < 0 || gx >= g.nbx * g.bs || gy < 0 || gy >= g.nby * g.bs || gz < 0 || gz >= g.nbz * g.bs) return kSdfInvalid;
-  const int b = ((gz / g.bs) * g.nby + gy / g.bs) * g.nbx + gx / g.bs;
-  if (block_mask[b] == 0) return kSdfInvalid;
-  const int local = ((gz % g.bs) * g.bs + gy % g.bs) * g.bs + gx % g.bs;
-  const uint32_t v = block_data[(size_t)b * (g.bs * g.bs * g.bs) + local];
-  const float w = half_hi(v);
-  return w >= g.min_weight ? half_lo(v) / w : kSdfInvalid;
-}
-
-// continuous voxel coordinate of a world position (builder_coord.py:45-54)
-__device__ __forceinline__ f3 mesh_continuous(const MapGrid &g, f3 p) {
-  return make_f3((p.x - g.ox) / g.vs + (float)g.grid_w * 0.5f, (p.y - g.oy) / g.vs + (float)g.grid_h * 0.5f,
-                 (p.z - g.oz) / g.vs + (float)g.grid_d * 0.5f);
-}
-
-// nearest-voxel sample: voxel floor(v)  (builder_raycast.py:92-109)
-__device__ __forceinline__ float mesh_nearest(const MeshArgs &a, const MapGrid &g, f3 p) {
-  const f3 v = mesh_continuous(g, p);
-  return mesh_voxel(a.block_data, a.block_mask, g, (int)floorf(v.x), (int)floorf(v.y), (int)floorf(v.z));
-}
-
-// trilinear sample, lower corner floor(v - 0.5); an invalid corner contributes the truncation distance, no valid corner at
-// all makes the sample invalid  (builder_raycast.py:168-258)
-__device__ __forceinline__ float mesh_trilinear(const MeshArgs &a, const MapGrid &g, f3 p) {
-  const f3 v = mesh_continuous(g, p);
-  const float fx = v.x - 0.5f, fy = v.y - 0.5f, fz = v.z - 0.5f;
-  const float x0 = floorf(fx), y0 = floorf(fy), z0 = floorf(fz);
-  const float tx = fx - x0, ty = fy - y0, tz = fz - z0;
-  const int ix = (int)x0, iy = (int)y0, iz = (int)z0;
-  float total = 0.0f;
-  bool any_valid = false;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-    const float s = mesh_voxel(a.block_data, a.block_mask, g, ix + dx, iy + dy, iz + dz);
-    const bool ok = !(s > 1e9f);
-    any_valid |= ok;
-    total += (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty) * (dz ? tz : 1.0f - tz) * (ok ? s : g.trunc);
-  }
-  return any_valid ? total : kSdfInvalid;
-}
-
-// normalised central difference of six samples at +-voxel_size; (0, 0, 1) where one of them is invalid or the magnitude is
-// below 1e-6  (builder_raycast.py:277-325 with trilinear samples, :327-375 with nearest-voxel samples)
-template <bool TRILINEAR>
-__device__ __forceinline__ f3 mesh_gradient(const MeshArgs &a, const MapGrid &g, f3 p) {
-  float s[6];
-#pragma unroll
-  for (int k = 0; k < 6; k++) {
-    const float e = (k & 1) ? -g.vs : g.vs;
-    const f3 q = make_f3(p.x + (k / 2 == 0 ? e : 0.0f), p.y + (k / 2 == 1 ? e : 0.0f), p.z + (k / 2 == 2 ? e : 0.0f));
-    s[k] = TRILINEAR ? mesh_trilinear(a, g, q) : mesh_nearest(a, g, q);
-  }
-  const f3 up = make_f3(0.0f, 0.0f, 1.0f);
-  if (s[0] > 1e9f || s[1] > 1e9f || s[2] > 1e9f || s[3] > 1e9f || s[4] > 1e9f || s[5] > 1e9f) return up;
-  const f3 grad = make_f3((s[0] - s[1]) / (2.0f * g.vs), (s[2] - s[3]) / (2.0f * g.vs), (s[4] - s[5]) / (2.0f * g.vs));
-  const float mag = sqrtf(grad.x * grad.x + grad.y * grad.y + grad.z * grad.z);
-  if (mag < 1e-6f) return up;
-  return make_f3(grad.x / mag, grad.y / mag, grad.z / mag);
-}
-
 // Stage 1, one workgroup per (slot, tile of min(bs, 8)^3 cubes): the (tile + 1)^3 corner values sw / w - level once into LDS,
 // then per cube: is it a surface cube (builder_mesh.py:147-229), its case (:610-626), how many of its own edges 0, 3, 8 are
 // cut (exactly one end negative) and how many triangles its table row holds.  A cube that is no surface cube gets case 0.
@@ -441,15 +366,15 @@ __global__ __launch_bounds__(kMapThreads) void mapper_mesh_vertices_kernel(float
     p[axis] = pa[axis] + t * (pb[axis] - pa[axis]);
     f3 pos = make_f3(p[0], p[1], p[2]);
     for (int it = 0; it < refine_iterations; it++) {
-      const float sdf = mesh_trilinear(a, g, pos);
+      const float sdf = mesh_trilinear(a.block_data, a.block_mask, g, pos);
       if (sdf > 1e9f) break;
       const float value = sdf - a.level;
       if (fabsf(value) < 1e-6f || value > 100.0f) break;
-      const f3 dir = mesh_gradient<true>(a, g, pos);
+      const f3 dir = mesh_gradient<true>(a.block_data, a.block_mask, g, pos);
       const float step = fminf(fmaxf(value, -0.5f * g.vs), 0.5f * g.vs);
       pos = pos - step * dir;
     }
-    const f3 n = mesh_gradient<false>(a, g, pos);
+    const f3 n = mesh_gradient<false>(a.block_data, a.block_mask, g, pos);
     float *vo = vertices + (size_t)vid * 3, *no = normals + (size_t)vid * 3;
     vo[0] = pos.x, vo[1] = pos.y, vo[2] = pos.z;
     no[0] = n.x, no[1] = n.y, no[2] = n.z;
@@ -521,26 +446,6 @@ using namespace curobo_hip;
 
 // ---------------------------------------------------------------------------------------------------- host side
 static int64_t map_blocks(const MapGrid &g) { return (int64_t)g.nbx * g.nby * g.nbz; }
-
-static int read_params(const curobo_hip_mapper_params *p, MapGrid *g, const char *what) {
-  CUROBO_REQUIRE(p, "%s: params must not be null", what);
-  CUROBO_REQUIRE(p->grid_w > 0 && p->grid_h > 0 && p->grid_d > 0, "%s: the grid must have voxels along every axis, got %d x %d x %d", what,
-                 p->grid_w, p->grid_h, p->grid_d);
-  const int bs = p->block_size;
-  CUROBO_REQUIRE(bs >= 1 && bs <= 32 && (bs & (bs - 1)) == 0, "%s: block_size must be 1 or a power of two in 2..32, got %d", what, bs);
-  CUROBO_REQUIRE(p->nbx == ceil_div(p->grid_w, bs) && p->nby == ceil_div(p->grid_h, bs) && p->nbz == ceil_div(p->grid_d, bs),
-                 "%s: nbx, nby, nbz must be ceil(grid / block_size) = %d, %d, %d, got %d, %d, %d", what, ceil_div(p->grid_w, bs),
-                 ceil_div(p->grid_h, bs), ceil_div(p->grid_d, bs), p->nbx, p->nby, p->nbz);
-  const int64_t voxels = (int64_t)p->nbx * p->nby * p->nbz * bs * bs * bs;
-  CUROBO_REQUIRE(voxels < ((int64_t)1 << 31), "%s: the padded grid holds %lld voxels, the kernels index below 2^31", what, (long long)voxels);
-  CUROBO_REQUIRE(p->voxel_size > 0.0f && p->truncation_distance > 0.0f, "%s: voxel_size and truncation_distance must be positive", what);
-  CUROBO_REQUIRE(p->depth_min < p->depth_max, "%s: depth_min must be below depth_max", what);
-  g->grid_w = p->grid_w, g->grid_h = p->grid_h, g->grid_d = p->grid_d, g->bs = bs, g->nbx = p->nbx, g->nby = p->nby, g->nbz = p->nbz;
-  g->num_samples = p->num_samples, g->ox = p->origin[0], g->oy = p->origin[1], g->oz = p->origin[2], g->vs = p->voxel_size;
-  g->trunc = p->truncation_distance, g->depth_min = p->depth_min, g->depth_max = p->depth_max, g->min_weight = p->minimum_tsdf_weight;
-  g->step = p->step_size;
-  return CUROBO_HIP_OK;
-}
 
 static int read_cameras(MapCameras *c, const float *depth, const float *intrinsics, const float *cam_position, const float *cam_quaternion,
                         int n_cameras, int height, int width, const char *what) {

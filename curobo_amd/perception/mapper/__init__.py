@@ -1,7 +1,11 @@
 """Volumetric mapper (reference ``curobo._src.perception.mapper``): ``Mapper`` / ``MapperCfg``, depth frames to a dense TSDF to
-the exact fp16 ESDF the planners read."""
+the exact fp16 ESDF the planners read; ``BlockSparseTSDFRenderer`` ray-casts the TSDF into images and
+``BlockSparseRaycastPoseRefiner`` tracks the camera against it."""
 
 from .mapper import DenseTSDF, Mapper
 from .mapper_cfg import MapperCfg
+from .pose_refiner import BlockSparseRaycastPoseRefiner, BlockSparseRaycastRefinerCfg
+from .renderer import BlockSparseTSDFRenderer, BlockSparseTSDFRendererCfg, depth_to_colormap, normals_to_colormap
 
-__all__ = ["DenseTSDF", "Mapper", "MapperCfg"]
+__all__ = ["DenseTSDF", "Mapper", "MapperCfg", "BlockSparseTSDFRenderer", "BlockSparseTSDFRendererCfg", "BlockSparseRaycastPoseRefiner",
+           "BlockSparseRaycastRefinerCfg", "depth_to_colormap", "normals_to_colormap"]

@@ -4,9 +4,10 @@ The reference's ``Mapper`` (``perception/mapper/mapper.py``) with the same calls
 batch of depth images, ``compute_esdf()`` returns the ``VoxelGrid`` that ``SceneData.update_voxel_data`` puts in front of
 the planners.  Where the reference keeps the blocks the camera has seen in a hash table over a pool, this mapper stores the
 whole grid, padded to whole blocks, and keeps one byte per block, "ever visible", for "allocated".  ``extract_mesh()`` is the
-reference's third read-out: marching cubes over the ever-visible blocks, as a ``Mesh``.  Not built: decay and block recycling,
-static obstacles, lidar, colour and feature channels, rendering, checkpoints, ``clear_blocks``, jump flooding, scatter
-seeding."""
+reference's third read-out: marching cubes over the ever-visible blocks, as a ``Mesh``.  ``render*()`` ray-cast the TSDF into
+depth, normal and shaded images (``renderer.py``); ``pose_refiner.py`` aligns a new depth image to the map before it is
+integrated.  Not built: decay and block recycling, static obstacles, lidar, colour and feature channels (rendered colour is
+zero), checkpoints, ``clear_blocks``, jump flooding, scatter seeding."""
 
 from __future__ import annotations
 
@@ -77,6 +78,7 @@ class Mapper:
         self._frame_count = 0
         self._last_voxel_grid: Optional[VoxelGrid] = None
         self._mc_tables = None  # (case table, edge owners) on the device, from the first extract_mesh on
+        self._renderer = None   # from the first render on
 
     # ------------------------------------------------------------------------------------------------ storage
     @property
@@ -285,6 +287,39 @@ class Mapper:
             triangles = torch.empty((n_triangles, 3), **i32)
             B.mapper_mesh_compact(triangles, raw, keep, keep_end - keep)
         return vertices, triangles, normals, torch.zeros((n_vertices, 3), dtype=torch.uint8, device=dev)
+
+    # ------------------------------------------------------------------------------------------------ rendering
+    def _get_renderer(self):
+        """the mapper's ``BlockSparseTSDFRenderer``, made on first use (reference mapper.py:504-512)"""
+        if self._renderer is None:
+            from .renderer import BlockSparseTSDFRenderer
+
+            self._renderer = BlockSparseTSDFRenderer(self)
+        return self._renderer
+
+    def render(self, intrinsics: torch.Tensor, pose, image_shape, **kwargs):
+        """``(depth [H, W], normals [H, W, 3], valid [H, W] bool)`` of the TSDF seen from ``pose``: ``renderer.py``, whose notes on the
+        depth's meaning (range along the ray unless ``z_depth=True``) and on the returned views apply"""
+        return self._get_renderer().render(intrinsics, pose, image_shape, **kwargs)
+
+    def render_color(self, intrinsics: torch.Tensor, pose, image_shape):
+        return self._get_renderer().render_color(intrinsics, pose, image_shape)
+
+    def render_depth(self, intrinsics: torch.Tensor, pose, image_shape, **kwargs) -> torch.Tensor:
+        return self._get_renderer().render_depth(intrinsics, pose, image_shape, **kwargs)
+
+    def render_color_only(self, intrinsics: torch.Tensor, pose, image_shape) -> torch.Tensor:
+        return self._get_renderer().render_color_only(intrinsics, pose, image_shape)
+
+    def render_shaded(self, intrinsics: torch.Tensor, pose, image_shape, light_direction=(0.0, 0.0, 1.0), ambient: float = 0.3,
+                      use_color: bool = False) -> torch.Tensor:
+        return self._get_renderer().render_shaded(intrinsics, pose, image_shape, light_direction, ambient, use_color)
+
+    def render_depth_colormap(self, intrinsics: torch.Tensor, pose, image_shape) -> torch.Tensor:
+        return self._get_renderer().render_depth_colormap(intrinsics, pose, image_shape)
+
+    def render_normal_colormap(self, intrinsics: torch.Tensor, pose, image_shape) -> torch.Tensor:
+        return self._get_renderer().render_normal_colormap(intrinsics, pose, image_shape)
 
     def memory_usage_mb(self) -> float:
         t = self._tsdf

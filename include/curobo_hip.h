@@ -1298,6 +1298,50 @@ int curobo_hip_mapper_mesh_triangles(int32_t *raw_triangles, uint8_t *keep, int 
 int curobo_hip_mapper_mesh_compact(int32_t *triangles, int n_triangles, const int32_t *raw_triangles, const uint8_t *keep,
                                    const int32_t *keep_offset, int n_raw, curobo_hip_stream_t stream);
 
+/* ---- the TSDF read back along camera rays (csrc/mapper_raycast.hip; reference kernel/builder/builder_raycast.py :381-834,
+ * kernel/wp_raycast_pose_refine.py :100-316).  Both launches read block_data / block_mask as described above, sample
+ * trilinearly (an invalid corner counts as the truncation distance, no valid corner = invalid) and take minimum_tsdf_weight
+ * as an argument in place of params->minimum_tsdf_weight (a voxel is valid iff its weight >= it).  The camera -- intrinsics
+ * [3][3], position [3], quaternion [4] wxyz -- is read from the DEVICE, so a replayed graph follows a moving camera.  A
+ * position is compared with the grid's extent in float before any conversion to int.
+ *
+ * One lane per pixel, 16 x 16 pixels per workgroup.  The ray through the pixel centre ((px + 0.5 - cx) / fx, (py + 0.5 - cy)
+ * / fy, 1), normalised and rotated, is marched from t = depth_minimum_distance in steps of voxel_size / 2 while t <=
+ * depth_maximum_distance; a hit is the first pair of valid samples prev > 0, cur < 0, refined by ten regula-falsi iterations
+ * (:381-422); the normal is the normalised central difference of six trilinear samples at the hit ((0, 0, 1) where one is
+ * invalid).  accelerated == 0 is raycast_block_sparse_kernel (:467-573): an invalid sample advances t and keeps prev, at most
+ * min((max - min) / step + 1, 10000) steps.  accelerated != 0 is raycast_block_sparse_accelerated_kernel (:690-834): on
+ * entering a block that was never visible (a block outside the grid included) t jumps to the block's slab exit (:424-461)
+ * + step and prev is forgotten, at most 10000 iterations.  The two forms sample at different t and give different depths.
+ * hit_points, hit_normals float [H W][3], hit_depths float [H W], hit_mask uint8 [H W] are all written by every launch, 0
+ * on a miss (:486-493).  hit_depths is the RANGE along the ray, as the reference's (its "z_depth" is hit_t * 1.0, :564,
+ * :825); z_depth != 0 writes range * ray_cam.z, the depth along the camera's axis, instead.  A camera pose that is not
+ * finite hits nothing. */
+int curobo_hip_mapper_raycast(float *hit_points, float *hit_normals, float *hit_depths, uint8_t *hit_mask, const float *intrinsics,
+                              const float *position, const float *quaternion, const void *block_data, const uint8_t *block_mask,
+                              const curobo_hip_mapper_params *params, float minimum_tsdf_weight, float depth_minimum_distance,
+                              float depth_maximum_distance, int height, int width, int accelerated, int z_depth,
+                              curobo_hip_stream_t stream);
+
+/* _ray_sdf_alignment_block_sparse_tiled_kernel (wp_raycast_pose_refine.py:100-316).  One lane per sample: out_H x out_W =
+ * ceil(H / stride) x ceil(W / stride) pixels (out_i stride, out_j stride) of depth [H][W], n_samples_per_ray (odd, 1..9)
+ * samples k = -n/2 .. n/2 each.  A pixel counts when its depth d is finite and in [depth_minimum_distance,
+ * depth_maximum_distance]; its ray is ((pj - cx) / fx, (pi - cy) / fy, 1) -- no half pixel here (:171-172) -- normalised and
+ * rotated, obs_t = d |ray|.  The sample at obs_t must be valid with |sdf| <= distance_threshold (:187); sample k lies at t =
+ * obs_t + k voxel_size >= 0.1 (:191), expects sdf = -k voxel_size (within the truncation distance, :198), residual r = sdf -
+ * expected times the Huber scale sqrt(0.05 t^2 / |r|) where |r| > 0.05 t^2 (:201-209), Jacobian row [g, g_z p_y - g_y p_z,
+ * g_x p_z - g_z p_x, g_y p_x - g_x p_y] times that scale (:225-230), g the trilinear gradient at the sample p.  The 44 sums
+ * the reference adds with atomics leave as rows of `workspace` (CUROBO_HIP_POSE_WS_ROW words, one per workgroup of 256
+ * samples: words 0..20 J^T J, 21..26 J^T r, 27 sum r^2, 28 the count), which curobo_hip_pose_lm_step adds in order when called
+ * with n_points = out_H out_W n_samples_per_ray; curobo_hip_pose_sdf_ws_bytes of that count is the size.  No atomics, nothing
+ * to zero between evaluations, bit-identical from run to run.  position / quaternion: DEVICE pointers, e.g. cand_position /
+ * cand_quaternion of a curobo_hip_pose_lm_state; a pose that is not finite yields no valid sample. */
+int curobo_hip_mapper_ray_align(void *workspace, int64_t workspace_bytes, const float *depth, const float *intrinsics,
+                                const float *position, const float *quaternion, const void *block_data, const uint8_t *block_mask,
+                                const curobo_hip_mapper_params *params, float minimum_tsdf_weight, float depth_minimum_distance,
+                                float depth_maximum_distance, float distance_threshold, int height, int width, int stride,
+                                int n_samples_per_ray, curobo_hip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

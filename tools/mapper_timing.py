@@ -1,13 +1,18 @@
 """Times of the depth mapper (csrc/mapper.hip) at the sizes a user runs -> <out>/mapper_timing.jsonl (one line per run).
 
-    python tools/mapper_timing.py [--out profiles]
+    python tools/mapper_timing.py [--out profiles] [--sections map raycast]
 
 integrate: one 480 x 640 frame into the default map of the reference, 2 m at 5 mm = 400^3 voxels in blocks of 4 (256 MB dense),
 split into the frame-mask clear, the marking stage and the voxel stage.  compute_esdf: the captured chain at 128^3 and 256^3
 cells over the same map, and its five launches one by one.  Device events around repeated launches after a warm-up, the median
 of the rounds.  extract_mesh: the whole call on that map after its one frame, by the host's clock (it reads three totals back, so
 the call ends synchronised), without and with two refinement steps.  Beside each time the bytes the stage has to move (computed from the shapes and the visible-block count; the
-definitions are in the code) and what share of the 6.29 TB/s a float4 copy reaches on this part that is."""
+definitions are in the code) and what share of the 6.29 TB/s a float4 copy reaches on this part that is.
+
+raycast (csrc/mapper_raycast.hip): a 640 x 480 view of a 256^3 map of 1 cm voxels after 24 frames from around the scene (about a
+tenth of the blocks visible; the share is in the output): one launch of each form of the render, one alignment evaluation at the
+refiner's default n_points = 92160 (stride 1 at this image: every pixel), and a whole ``refine_pose`` of 100 iterations by the
+host's clock."""
 import argparse
 import json
 import os
@@ -22,7 +27,9 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 import mapper_ref as R  # noqa: E402  (the analytic depth image of a sphere over a ground plane)
 from curobo_amd.backends import mapper as B  # noqa: E402
-from curobo_amd.perception.mapper import Mapper, MapperCfg  # noqa: E402
+from curobo_amd.backends import perception as BP  # noqa: E402
+from curobo_amd.perception.mapper import (BlockSparseRaycastPoseRefiner, BlockSparseRaycastRefinerCfg, BlockSparseTSDFRenderer, Mapper,  # noqa: E402
+                                          MapperCfg)
 from curobo_amd.types import CameraObservation, Pose  # noqa: E402
 
 DEV = "cuda:0"
@@ -62,9 +69,50 @@ def stage(ms: float, nbytes: float) -> dict:
     return {"ms": round(ms, 4), "MB": round(nbytes / 1e6, 2), "share_of_hbm": round(nbytes / (ms * 1e-3) / HBM_BYTES_PER_S, 4)}
 
 
+def raycast_times(H, W, K) -> dict:
+    t = lambda a: torch.as_tensor(a, device=DEV)  # noqa: E731
+    cfg = MapperCfg(extent_meters_xyz=(2.56, 2.56, 2.56), voxel_size=0.01, image_height=H, image_width=W, esdf_voxel_size=0.04,
+                    extent_esdf_meters_xyz=(2.56, 2.56, 2.56), truncation_distance=0.08)
+    m = Mapper(cfg)
+    # four rings of six eyes, each looking a little past the sphere, so that the frames also cover the ground around it
+    eyes = [(1.2 * np.cos(a), 1.2 * np.sin(a), h) for h in (0.35, 0.65, 0.95, 1.3) for a in np.arange(6) * (np.pi / 3) + h]
+    for eye in eyes:
+        eye = np.asarray(eye, np.float32)
+        quat = R.look_at(eye, (-0.25 * eye[0], -0.25 * eye[1], -0.05), 0.2).astype(np.float32)
+        m.integrate(CameraObservation(depth_image=t(R.render_depth(K, eye, quat, H, W)[None]), intrinsics=t(K[None]), pose=Pose(t(eye[None]), t(quat[None]))))
+    stats = m.get_stats()
+    eye = np.array([0.8, -0.9, 0.6], np.float32)  # a view that integrated nothing
+    quat = R.look_at(eye, (0.0, 0.0, -0.05), -0.1).astype(np.float32)
+    pose = Pose(t(eye[None]), t(quat[None]))
+    out = {"map_voxels": [int(v) for v in cfg.grid_shape], "blocks": stats["total_blocks"], "visible_share": round(stats["visible_blocks"] / stats["total_blocks"], 4)}
+    ts, n = m.tsdf, H * W
+    for name, accelerated in (("render_plain", False), ("render_accelerated", True)):
+        r = BlockSparseTSDFRenderer(m, use_block_acceleration=accelerated)
+        depth, _, valid = r.render(t(K), pose, (H, W))
+        c = r.config
+        launch = lambda r=r, c=c, a=accelerated: B.mapper_raycast(r._hit_points[:n], r._hit_normals[:n], r._hit_depths[:n], r._hit_mask[:n],  # noqa: E731
+                                                                  r.intrinsics_matrix, r.cam_position, r.cam_quaternion, ts.block_data, ts.block_visible,
+                                                                  ts.params, c.minimum_tsdf_weight, c.depth_minimum_distance, c.depth_maximum_distance,
+                                                                  (H, W), a)
+        out[name] = {"ms": round(timed(launch, reps=5, rounds=3, warmup=1), 4), "hit_share": round(float(valid.float().mean()), 4)}
+    z = BlockSparseTSDFRenderer(m).render_depth(t(K), pose, (H, W), z_depth=True).clone()
+    rcfg = BlockSparseRaycastRefinerCfg(minimum_tsdf_weight=cfg.minimum_tsdf_weight)
+    refiner = BlockSparseRaycastPoseRefiner(m, rcfg)
+    off = Pose(t((eye + np.float32([0.02, -0.02, 0.01]))[None]), t(quat[None]))
+    _, error, iterations = refiner.refine_pose(z, t(K), off)
+    run = refiner._runs[(H, W)]
+    out["align_evaluation"] = {"ms": round(timed(lambda: refiner._evaluate(run), reps=10, rounds=3, warmup=1), 4), "samples": run.n_samples,
+                               "rows": BP.pose_sdf_ws_bytes(run.n_samples) // 128}
+    out["lm_step"] = {"ms": round(timed(lambda: refiner._step(run, BP.POSE_LM_UPDATE), reps=10, rounds=3, warmup=1), 4)}
+    out["refine_pose"] = {"ms": round(wall_ms(lambda: refiner.refine_pose(z, t(K), off), reps=3), 3), "iterations": iterations, "final_error": round(error, 6)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
+    ap.add_argument("--sections", nargs="+", choices=["map", "raycast"], default=["map", "raycast"],
+                    help="map: integrate, compute_esdf, extract_mesh; raycast: render, alignment, refine_pose")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "mapper_timing needs a GPU"
     H, W = 480, 640
@@ -75,7 +123,7 @@ def main():
     t = lambda a: torch.as_tensor(a, device=DEV)  # noqa: E731
     obs = CameraObservation(depth_image=t(depth[None]), intrinsics=t(K[None]), pose=Pose(t(eye[None]), t(quat[None])))
     result = {"when": time.strftime("%Y-%m-%d"), "device": torch.cuda.get_device_name(0), "image": [H, W]}
-    for n_esdf in (128, 256):
+    for n_esdf in (128, 256) if "map" in args.sections else ():
         cfg = MapperCfg(extent_meters_xyz=(2.0, 2.0, 2.0), voxel_size=0.005, image_height=H, image_width=W, esdf_voxel_size=2.0 / n_esdf,
                         extent_esdf_meters_xyz=(2.0, 2.0, 2.0))
         m = Mapper(cfg)
@@ -121,6 +169,8 @@ def main():
         result[f"esdf_{n_esdf}"] = entry
         del m
         torch.cuda.empty_cache()
+    if "raycast" in args.sections:
+        result["raycast"] = raycast_times(H, W, K)
     os.makedirs(args.out, exist_ok=True)
     with open(os.path.join(args.out, "mapper_timing.jsonl"), "a") as fh:
         fh.write(json.dumps(result) + "\n")
