@@ -99,3 +99,55 @@ def self_collision_distance(
         horizon, nspheres, num_collision_pairs, int(store_pair_distance), int(compute_grad),
         current_stream(out_distance),
     ))
+
+
+#: limits of ``link_pair_sweep`` (LDS: 16 bytes per sphere + 12 per group <= 64 KiB)
+SWEEP_MAX_SPHERES, SWEEP_MAX_GROUPS = 1024, 4096
+#: workgroups the default split aims at (four per CU of an MI355X)
+SWEEP_TARGET_CHUNKS = 1024
+
+
+def link_pair_sweep(
+    max_penetration: torch.Tensor,
+    collision_count: torch.Tensor,
+    robot_spheres: torch.Tensor,
+    sphere_padding: torch.Tensor,
+    pair_locations: torch.Tensor,
+    pair_group: torch.Tensor,
+    n_groups: int,
+    points_per_workgroup: Optional[int] = None,
+    accumulate: bool = False,
+):
+    """Per link pair (group) statistics of a batch of configurations; modifies the two outputs in place, on the current stream.
+
+    ``robot_spheres`` [N, S, 4] fp32 (world frame, as the FK launch writes them; leading dimensions are flattened),
+    ``sphere_padding`` [S] fp32, ``pair_locations`` [P, 2] int16 sorted so that every group of ``pair_group`` [P] int32 (values
+    in ``[0, n_groups)``) is one contiguous run.  ``max_penetration`` [G] fp32 receives the largest
+    ``(r_i + pad_i) + (r_j + pad_j) - |c_i - c_j|`` (metres, signed) over the N points and the group's valid pairs -- both padded
+    radii >= 0 -- and ``-inf`` for a group without a valid pair; ``collision_count`` [G] int32 the number of points at which some
+    valid pair of the group penetrates.  ``accumulate``: the outputs are folded with what they hold (max / sum), so a run
+    over several batches needs no host round trip.  ``points_per_workgroup`` forces the split of the points over workgroups
+    (default: about ``SWEEP_TARGET_CHUNKS`` workgroups); the result is bit-identical for every split and from run to run.
+
+    Limits (``ValueError``): ``S <= 1024`` and ``G <= 4096``."""
+    S, G, P = int(robot_spheres.shape[-2]), int(n_groups), int(pair_locations.shape[0])
+    if robot_spheres.shape[-1] != 4 or not 1 <= S <= SWEEP_MAX_SPHERES:
+        raise ValueError(f"link_pair_sweep: robot_spheres must be [..., S, 4] with 1 <= S <= {SWEEP_MAX_SPHERES}, got {tuple(robot_spheres.shape)}")
+    if not 1 <= G <= SWEEP_MAX_GROUPS:
+        raise ValueError(f"link_pair_sweep: n_groups={G} out of range [1, {SWEEP_MAX_GROUPS}]")
+    if points_per_workgroup is not None and int(points_per_workgroup) < 1:
+        raise ValueError(f"link_pair_sweep: points_per_workgroup={points_per_workgroup} must be >= 1")
+    for name, t, dt, shape in (("max_penetration", max_penetration, torch.float32, (G,)), ("collision_count", collision_count, torch.int32, (G,)),
+                               ("sphere_padding", sphere_padding, torch.float32, (S,)), ("pair_locations", pair_locations, torch.int16, (P, 2)),
+                               ("pair_group", pair_group, torch.int32, (P,)), ("robot_spheres", robot_spheres, torch.float32, None)):
+        if t.dtype != dt or (shape is not None and tuple(t.shape) != shape) or not t.is_contiguous():
+            raise ValueError(f"link_pair_sweep: {name} must be contiguous {dt}" + (f" of shape {shape}" if shape else "")
+                             + f", got {t.dtype} {tuple(t.shape)}")
+    N = robot_spheres.numel() // (S * 4)
+    ppw = max(1, -(-N // SWEEP_TARGET_CHUNKS)) if points_per_workgroup is None else int(points_per_workgroup)
+    chunks = max(1, -(-N // ppw))
+    part_max = torch.empty((chunks, G), dtype=torch.float32, device=robot_spheres.device)
+    part_cnt = torch.empty((chunks, G), dtype=torch.int32, device=robot_spheres.device)
+    check(load().curobo_hip_link_pair_sweep(
+        ptr(max_penetration), ptr(collision_count), ptr(part_max), ptr(part_cnt), chunks, ptr(robot_spheres), ptr(sphere_padding),
+        ptr(pair_locations), ptr(pair_group), N, S, P, G, ppw, int(accumulate), current_stream(max_penetration)))

@@ -42,6 +42,7 @@ SOURCES = [
     "mapper.hip",
     "mapper_raycast.hip",
     "support_polygon.hip",
+    "link_pair_sweep.hip",
 ]
 
 
@@ -90,8 +91,11 @@ def _flags() -> List[str]:
 # AGPR form costs a v_accvgpr_write per accumulator input and a v_accvgpr_read per output, twelve moves per 16 x 16 tile
 # support_polygon.hip: the soft-min gradient divides differences of edge distances by the smoothing length (x 100), so the
 # distances are taken with the correctly rounded sqrt / divide; the kernel is a few hundred instructions per point either way
+# link_pair_sweep.hip: its penetrations are signed distances in metres held to a few fp32 roundings of a float64 restatement,
+# and "never collides" is decided at their sign: the correctly rounded sqrt (one per pair test, beside two 16-byte LDS reads)
 PER_SOURCE_FLAGS: dict = {"self_collision.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-                          "support_polygon.hip": ["-fhip-fp32-correctly-rounded-divide-sqrt"]}
+                          "support_polygon.hip": ["-fhip-fp32-correctly-rounded-divide-sqrt"],
+                          "link_pair_sweep.hip": ["-fhip-fp32-correctly-rounded-divide-sqrt"]}
 NO_SLP = ["-fno-slp-vectorize"]
 
 

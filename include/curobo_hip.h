@@ -135,6 +135,24 @@ int curobo_hip_self_collision_distance_dense(
     const uint8_t *tile_lane_masks, int batch_size, int horizon, int nspheres, int nslots, int compute_grad,
     curobo_hip_stream_t stream);
 
+/* Link-pair sweep (the self-collision matrix builder; reference RobotBuilder._prune_collision_pairs,
+ * robot/builder/builder_robot.py:1054-1172, without its [N, P] pair_distance buffer): robot_spheres [n_points, nspheres, 4]
+ * in the world frame, pair_locations [num_pairs, 2] sorted so that every group -- pair_group [num_pairs] in [0, n_groups),
+ * one link pair -- is one contiguous run.  Per group g:
+ *   max_penetration[g] = max over the points and the group's valid pairs of (r_i + pad_i) + (r_j + pad_j) - |c_i - c_j|
+ *                        (metres, signed; a pair is valid when both padded radii are >= 0; -inf without a valid pair)
+ *   collision_count[g] = number of points at which some valid pair of the group has penetration > 0
+ * accumulate != 0: folded into what the two outputs hold (max / sum) instead of replacing it.
+ * partial_max / partial_count: scratch [partial_chunks, n_groups], partial_chunks >= ceil(n_points / points_per_workgroup).
+ * No floating-point atomics; the result is bit-identical from run to run and for every points_per_workgroup.
+ * nspheres <= 1024, n_groups <= 4096 (LDS: 16 nspheres + 12 n_groups bytes <= 64 KiB); robot_spheres, pair_locations and
+ * pair_group 16-byte aligned. */
+int curobo_hip_link_pair_sweep(
+    float *max_penetration, int32_t *collision_count, float *partial_max, int32_t *partial_count, int partial_chunks,
+    const float *robot_spheres, const float *sphere_padding, const int16_t *pair_locations, const int32_t *pair_group,
+    int n_points, int nspheres, int num_pairs, int n_groups, int points_per_workgroup, int accumulate,
+    curobo_hip_stream_t stream);
+
 /* ---------------------------------------------------------------- collision: sphere vs scene
  * The reference has NO backend hook here: these are NVIDIA Warp kernels launched from
  * geom/collision/wp_autograd.py:37-249 (SphereObstacleCollision / SweptSphereObstacleCollision).
