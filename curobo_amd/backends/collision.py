@@ -142,6 +142,22 @@ def sphere_obstacle_collision(
                               num_spheres, use_multi_env, sweep_steps, enable_speed_metric, speed_dt, accumulate=others)
 
 
+#: kernel forms of ``sphere_obstacle_collision`` (``scene_collision_form``)
+SCENE_INLANE, SCENE_INLANE_STAGED, SCENE_PACKED = 0, 1, 2
+
+
+def scene_collision_form(scene: Scene, batch_size: int, horizon: int, num_spheres: int, sweep_steps: int = 0) -> int:
+    """The kernel form ``sphere_obstacle_collision`` runs for these arguments: ``SCENE_INLANE`` (obstacle records read
+    from global memory), ``SCENE_INLANE_STAGED`` (records staged in LDS) or ``SCENE_PACKED`` (voxel scenes with at most
+    32 records: early rejects, then a dense LDS queue).  The launcher's own decision, host side, no GPU work; every form
+    gives the same results bit for bit."""
+    form = int(load().curobo_hip_scene_collision_form(C.addressof(scene), int(batch_size), int(horizon), int(num_spheres),
+                                                      int(sweep_steps)))
+    if form < 0:
+        raise ValueError(f"no scene-collision launch for horizon {horizon}, num_spheres {num_spheres}")
+    return form
+
+
 def trajectory_cost_sum(
     out_cost: torch.Tensor,
     self_cost: Optional[torch.Tensor],

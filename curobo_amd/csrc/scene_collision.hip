@@ -33,6 +33,14 @@ struct SceneArgs {
   int batch, horizon, nspheres, use_multi_env, sweep_steps, enable_speed_metric;
 };
 
+// The speed metric of this file's kernels as ONE compiled body.  Inlined, every kernel contracts its products into fmas its
+// own way (-ffp-contract=fast), and the packed and the in-lane forms, whose sums are bit-identical, then hand out gradients
+// that differ in the last bit.  Called only for spheres in collision with both neighbours; arguments and result in registers.
+__device__ __noinline__ float4 speed_metric_shared(f3 center, f3 pp, f3 np, float speed_dt, float dsum, f3 gsum) {
+  speed_metric_apply(center, pp, np, speed_dt, dsum, gsum);
+  return make_float4(gsum.x, gsum.y, gsum.z, dsum);
+}
+
 // KINDS: bit 0 = cuboids present, bit 1 = voxel grids present (separate instantiations keep the
 // cuboid-only kernel's register footprint free of the 8-corner voxel gather state)
 template <int SWEEP, bool STAGED, int KINDS>
@@ -70,8 +78,11 @@ __global__ void __launch_bounds__(256) scene_collision_kernel(const SceneArgs a)
   float dsum;
   f3 gsum;
   sphere_scene_cost<SWEEP, STAGED, KINDS>(a.sc, recs + (size_t)(b - b_first) * n_rec, env, s, has_prev, ps, has_next, ns,
-                                          a.activation_distance[0], a.weight[0], a.enable_speed_metric != 0,
-                                          a.enable_speed_metric ? a.speed_dt[0] : 0.0f, dsum, gsum);
+                                          a.activation_distance[0], a.weight[0], false, 0.0f, dsum, gsum);
+  if (a.enable_speed_metric && has_prev && has_next && dsum > 0.0f) {
+    const float4 r = speed_metric_shared(make_f3(s.x, s.y, s.z), make_f3(ps.x, ps.y, ps.z), make_f3(ns.x, ns.y, ns.z), a.speed_dt[0], dsum, gsum);
+    dsum = r.w; gsum = make_f3(r.x, r.y, r.z);
+  }
   a.distance[sidx] = dsum;
   reinterpret_cast<float4 *>(a.gradient)[sidx] = make_float4(gsum.x, gsum.y, gsum.z, 0.0f);
 }
@@ -219,10 +230,39 @@ __global__ void __launch_bounds__(256) scene_collision_packed_kernel(const Scene
     }
   }
   if (!in) return;
-  if (a.enable_speed_metric && has_prev && has_next && dsum > 0.0f)
-    speed_metric_apply(make_f3(s.x, s.y, s.z), make_f3(ps.x, ps.y, ps.z), make_f3(ns.x, ns.y, ns.z), a.speed_dt[0], dsum, gsum);
+  if (a.enable_speed_metric && has_prev && has_next && dsum > 0.0f) {
+    const float4 r = speed_metric_shared(make_f3(s.x, s.y, s.z), make_f3(ps.x, ps.y, ps.z), make_f3(ns.x, ns.y, ns.z), a.speed_dt[0], dsum, gsum);
+    dsum = r.w; gsum = make_f3(r.x, r.y, r.z);
+  }
   a.distance[sidx] = dsum;
   reinterpret_cast<float4 *>(a.gradient)[sidx] = make_float4(gsum.x, gsum.y, gsum.z, 0.0f);
+}
+
+// What a launch of curobo_hip_sphere_obstacle_collision runs, decided ONCE: the launcher and the host-side query
+// curobo_hip_scene_collision_form both read this plan.  Neither the batch size nor the sweep changes the form.
+struct SceneLaunchPlan {
+  int form;           // CUROBO_HIP_SCENE_FORM_*
+  int kinds;          // KINDS of the instantiation
+  size_t lds;         // staged obstacle records of every batch row a 256-sphere workgroup can touch
+  size_t lds_packed;  // + the packed kernel's stash, results, prefix and queue
+};
+
+static SceneLaunchPlan scene_launch_plan(const curobo_hip_scene &scene, int horizon, int num_spheres) {
+  SceneLaunchPlan p{};
+  const long hs = (long)horizon * num_spheres;
+  const long slots = (256 + hs - 1) / hs + 1;
+  const int n_rec = scene.max_cuboids + scene.max_voxel_grids;
+  p.lds = (size_t)slots * n_rec * sizeof(ObsRec);
+  const bool staged = p.lds > 0 && p.lds <= 32 * 1024;
+  p.kinds = (scene.max_cuboids > 0 ? 1 : 0) | (scene.max_voxel_grids > 0 ? 2 : 0) |
+            ((scene.max_cuboids > 0 && scene.cuboid_has_primitives) ? 4 : 0);
+  // (the queue holds at most one item per sphere and obstacle record: sized by the scene, not by the 32-record limit --
+  // LDS per workgroup is occupancy)
+  p.lds_packed = p.lds + (size_t)(3 + 1) * 256 * 16 + (256 + 8) * 4 + (((size_t)256 * n_rec * 2 + 15) & ~(size_t)15);
+  static const bool no_packed = getenv("CUROBO_HIP_SCENE_UNPACKED") != nullptr;  // development knob: the in-lane obstacle loop
+  if (staged && (p.kinds & 2) && n_rec <= 32 && p.lds_packed <= 64 * 1024 && !no_packed) p.form = CUROBO_HIP_SCENE_FORM_PACKED;
+  else p.form = staged ? CUROBO_HIP_SCENE_FORM_INLANE_STAGED : CUROBO_HIP_SCENE_FORM_INLANE;
+  return p;
 }
 
 }  // namespace curobo_hip
@@ -249,13 +289,10 @@ CUROBO_EXPORT int curobo_hip_sphere_obstacle_collision(
   a.use_multi_env = use_multi_env; a.sweep_steps = sweep_steps; a.enable_speed_metric = enable_speed_metric;
   hipStream_t st = (hipStream_t)stream;
   const unsigned blocks = (unsigned)ceil_div_l(total, 256);
-  // obstacle records of every batch row a 256-sphere workgroup can touch, staged in LDS
-  const long hs = (long)horizon * num_spheres;
-  const long slots = (256 + hs - 1) / hs + 1;
-  const size_t lds = (size_t)slots * (scene->max_cuboids + scene->max_voxel_grids) * sizeof(ObsRec);
-  const bool staged = lds > 0 && lds <= 32 * 1024;
-  const int kinds = (scene->max_cuboids > 0 ? 1 : 0) | (scene->max_voxel_grids > 0 ? 2 : 0) |
-                    ((scene->max_cuboids > 0 && scene->cuboid_has_primitives) ? 4 : 0);
+  const SceneLaunchPlan plan = scene_launch_plan(*scene, horizon, num_spheres);
+  const size_t lds = plan.lds, lds_packed = plan.lds_packed;
+  const bool staged = plan.form != CUROBO_HIP_SCENE_FORM_INLANE;
+  const int kinds = plan.kinds;
 #define CUROBO_SCENE_LAUNCH(SW, ST, KD) \
   hipLaunchKernelGGL((scene_collision_kernel<SW, ST, KD>), dim3(blocks), dim3(256), (ST) ? lds : 0, st, a)
 #define CUROBO_SCENE_KINDS(SW, ST)                   \
@@ -266,12 +303,7 @@ CUROBO_EXPORT int curobo_hip_sphere_obstacle_collision(
     else if (kinds == 7) CUROBO_SCENE_LAUNCH(SW, ST, 7); \
     else CUROBO_SCENE_LAUNCH(SW, ST, 3);             \
   } while (0)
-  const int n_rec = scene->max_cuboids + scene->max_voxel_grids;
-  // (the queue holds at most one item per sphere and obstacle record: sized by the scene, not by the 32-record limit --
-  // LDS per workgroup is occupancy)
-  const size_t lds_packed = lds + (size_t)(3 + 1) * 256 * 16 + (256 + 8) * 4 + (((size_t)256 * n_rec * 2 + 15) & ~(size_t)15);
-  static const bool no_packed = getenv("CUROBO_HIP_SCENE_UNPACKED") != nullptr;  // development knob: the in-lane obstacle loop
-  if (staged && (kinds & 2) && n_rec <= 32 && lds_packed <= 64 * 1024 && !no_packed) {  // ESDF grids: see the kernel's header
+  if (plan.form == CUROBO_HIP_SCENE_FORM_PACKED) {  // ESDF grids: see the kernel's header
 #define CUROBO_SCENE_PACKED(SW)                                                                                              \
   do {                                                                                                                       \
     if (kinds == 1) hipLaunchKernelGGL((scene_collision_packed_kernel<SW, 1>), dim3(blocks), dim3(256), lds_packed, st, a);      \
@@ -289,4 +321,11 @@ CUROBO_EXPORT int curobo_hip_sphere_obstacle_collision(
 #undef CUROBO_SCENE_KINDS
 #undef CUROBO_SCENE_LAUNCH
   return check_launch(what, st);
+}
+
+CUROBO_EXPORT int curobo_hip_scene_collision_form(const curobo_hip_scene *scene, int batch_size, int horizon, int num_spheres,
+                                                  int sweep_steps) {
+  (void)batch_size; (void)sweep_steps;
+  if (scene == nullptr || horizon <= 0 || num_spheres <= 0 || scene->max_cuboids < 0 || scene->max_voxel_grids < 0) return -1;
+  return scene_launch_plan(*scene, horizon, num_spheres).form;
 }

@@ -198,6 +198,15 @@ __device__ __forceinline__ float voxel_sdf(const curobo_hip_scene &sc, int flat_
   return sdf;
 }
 
+// How far outside a grid's box (Euclidean distance) a point can still read a stored voxel.  Trilinear lookups have valid
+// corners up to HALF a voxel outside a face on every axis at once: sqrt(3) / 2 < 1 voxel.  A thin grid (fewer than two
+// voxels along an axis) answers with its nearest voxel, whose index is truncated towards zero: a point up to ONE voxel
+// below a low face still reads voxel 0, on all three axes at once: sqrt(3) < 1.75 voxels.
+__device__ __forceinline__ float voxel_read_margin(float4 prm) {
+  const bool thin = prm.x < 2.0f || prm.y < 2.0f || prm.z < 2.0f;
+  return thin ? 1.75f * prm.w : prm.w;
+}
+
 // penetration of one sample + its cost c and gradient scale gs * direction g (both 0 when it does not penetrate)
 template <bool VOXEL, bool PRIMS = false>
 __device__ __forceinline__ float point_terms(const curobo_hip_scene &sc, int flat, const ObsRec &rec, f3 lp, float r_adj,
@@ -341,7 +350,7 @@ __device__ __forceinline__ bool obstacle_early_reject(const curobo_hip_scene &sc
     const float vs = rec.shape.w;
     const float cx = fmaxf(fabsf(lc.x) - rec.shape.x * vs * 0.5f, 0.0f), cy = fmaxf(fabsf(lc.y) - rec.shape.y * vs * 0.5f, 0.0f),
                 cz = fmaxf(fabsf(lc.z) - rec.shape.z * vs * 0.5f, 0.0f);
-    const float thr_v = reach + vs;
+    const float thr_v = reach + voxel_read_margin(rec.shape);
     if (cx * cx + cy * cy + cz * cz > thr_v * thr_v * 1.00001f) return true;
     // Coarse minimum (scene upload, optional): every sample of this sphere -- centre and sweep -- interpolates
     // corner voxels within ceil(reach / vs) + 1 voxels of the centre's voxel, a convex combination of values
@@ -372,7 +381,7 @@ __device__ __forceinline__ bool obstacle_early_reject(const curobo_hip_scene &sc
 // cuboid whose squared outside distance exceeds it is clear of the centre by more than any sweep
 // can reach: no penetration, both sweep directions culled -> exactly zero, without sqrt, gradient
 // or sweep bookkeeping.  A voxel grid is skipped when the centre is so far outside its box (sweep
-// reach + one voxel) that every sample reads the constant max_distance.
+// reach + voxel_read_margin: one voxel, 1.75 for a thin grid) that every sample reads the constant max_distance.
 template <bool VOXEL, int SWEEP, bool STAGED, bool PRIMS = false>
 __device__ __forceinline__ void obstacle_set(const curobo_hip_scene &sc, const ObsRec *__restrict__ recs, int env,
                                              bool has_prev, bool has_next, f3 prev_c, f3 next_c, f3 center, float r_adj,
@@ -407,7 +416,7 @@ __device__ __forceinline__ void obstacle_set(const curobo_hip_scene &sc, const O
 // (>= the half sweep length of each of them)?  A signed distance field is 1-Lipschitz, so
 // sdf(c_s) - r_s >= sdf(C) - R; when that exceeds eta + reach the per-sphere test above would
 // reject the obstacle for every contained sphere, i.e. clearing its bit is result-preserving.
-// Voxel grids: cleared when the ball (+ reach + one voxel) lies outside the grid box, where every
+// Voxel grids: cleared when the ball (+ reach + voxel_read_margin) lies outside the grid box, where every
 // sample reads the constant max_distance.  Obstacles >= 32 are never culled.
 template <int KINDS>
 __device__ __forceinline__ uint32_t bounding_ball_obstacle_mask(const curobo_hip_scene &sc, const ObsRec *__restrict__ recs,
@@ -426,7 +435,7 @@ __device__ __forceinline__ uint32_t bounding_ball_obstacle_mask(const curobo_hip
     if (o >= n_c) {  // voxel grid: box half extents, one voxel of margin, only when no radius reaches max_distance
       const float vs = rec.shape.w;
       hx *= vs * 0.5f; hy *= vs * 0.5f; hz *= vs * 0.5f;
-      const float tv = (R + reach + vs) * 1.0001f + 4e-6f;
+      const float tv = (R + reach + voxel_read_margin(rec.shape)) * 1.0001f + 4e-6f;
       t2 = (R + eta < sc.voxel_max_distance) ? tv * tv * 1.00001f : 3.0e38f;
     }
     const float cx = fmaxf(fabsf(lc.x) - hx, 0.0f), cy = fmaxf(fabsf(lc.y) - hy, 0.0f), cz = fmaxf(fabsf(lc.z) - hz, 0.0f);

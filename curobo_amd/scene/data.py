@@ -278,7 +278,12 @@ class SceneData:
 
     def update_voxel_features(self, name: str, features, env_idx: int = 0) -> None:
         """new ESDF values of a voxel grid of unchanged shape ([nx ny nz] values, x slowest; any float dtype, stored as fp16),
-        in place; the culling grid follows.  Planners and captured optimiser graphs see the new grid on their next call."""
+        in place; the culling grid follows.  Planners and captured optimiser graphs see the new grid on their next call.
+
+        Precondition: the values are a 1-Lipschitz field (a signed distance, possibly clipped at ``voxel_max_distance``) up to
+        fp16 rounding.  Discrete collision matches the reference for any values; the swept kernels' culls rely on the
+        precondition: on a grid that stores e.g. "unknown = 1e4" next to occupied voxels they drop sweep samples the reference
+        takes, so the swept cost is at or below the reference's."""
         slot = self._voxel_slot(name, env_idx)
         nx, ny, nz = (int(v) for v in self.arrays["voxel_params"][env_idx, slot, :3])
         n_new = int(np.prod(tuple(features.shape)))
@@ -289,7 +294,9 @@ class SceneData:
 
     def update_voxel_data(self, voxel_grid, env_idx: int = 0, name: Optional[str] = None) -> None:
         """features, grid shape / voxel size, pose and enable flag of a voxel grid from a ``VoxelGrid`` (looked up by ``name``,
-        default the grid's own); the new grid must fit the feature buffer and the culling buffer the scene was built with"""
+        default the grid's own); the new grid must fit the feature buffer and the culling buffer the scene was built with.
+        The features must be a 1-Lipschitz field up to fp16 rounding, as for ``update_voxel_features``: otherwise the swept
+        cost can fall below the reference's."""
         slot = self._voxel_slot(name if name is not None else voxel_grid.name, env_idx)
         shape = voxel_grid.get_grid_shape()[0]
         if voxel_grid.feature_tensor is None:

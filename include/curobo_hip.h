@@ -202,6 +202,20 @@ int curobo_hip_sphere_obstacle_collision(
     int batch_size, int horizon, int num_spheres, int use_multi_env, int sweep_steps,
     int enable_speed_metric, const float *speed_dt, curobo_hip_stream_t stream);
 
+/* The kernel form curobo_hip_sphere_obstacle_collision runs for these arguments (host-side, no GPU work; `scene` is the
+ * host struct, only its capacities are read; -1 for arguments the launch would refuse).  All forms give the same
+ * results bit for bit:
+ *   INLANE        one lane per sphere walks the obstacles, records read from global memory (the staged records of the
+ *                 batch rows a 256-sphere workgroup can touch would exceed 32 KiB of LDS: small horizon * spheres);
+ *   INLANE_STAGED the same loop over records staged in LDS;
+ *   PACKED        scenes with voxel grids and at most 32 records: early rejects first, the surviving (sphere, obstacle)
+ *                 items evaluated densely from an LDS queue. */
+#define CUROBO_HIP_SCENE_FORM_INLANE 0
+#define CUROBO_HIP_SCENE_FORM_INLANE_STAGED 1
+#define CUROBO_HIP_SCENE_FORM_PACKED 2
+int curobo_hip_scene_collision_form(const curobo_hip_scene *scene, int batch_size, int horizon, int num_spheres,
+                                    int sweep_steps);
+
 /* Mesh obstacles -> one more ESDF grid of the voxel store (scene-upload time, not the hot path).  The reference
  * queries meshes through NVIDIA Warp's BVH (geom/data/data_mesh.py:555-700, wp.mesh_query_point); here a closed,
  * consistently oriented triangle mesh is baked into an fp16 grid [nx, ny, nz] (voxel centres

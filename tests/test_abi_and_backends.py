@@ -59,6 +59,7 @@ EXPECTED = {
 }
 # HIP-side extensions (no reference backend module of that name): exported and callable
 EXTENSIONS = {
+    "collision": ["scene_collision_form"],
     "cost": ["tool_pose_distance", "cspace_position_cost", "cspace_state_cost", "cspace_l2_distance", "rollout_point_aggregate"],
     "linalg": ["levenberg_marquardt_step", "seed_ik_update_state"],
     "rollout": ["rollout_trajectory_fused", "rollout_trajopt_fused", "rollout_ik_fused", "make_trajopt_terms", "DispatchOrder"],
