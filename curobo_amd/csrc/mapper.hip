@@ -27,7 +27,7 @@
 // coordinate along the line, so the pass is min_j (d2(j) + (i - j)^2) with d2(j) the squared distance of cell j to its own
 // site: d2 of a tile of lines is staged in LDS once and every cell scans its line by brute force, in integers.
 //
-// The grid, the fp16 pair's halves and the TSDF reads of the mesh launches are mapper_device.hpp's: mapper_raycast.hip shares them.
+// How positions, voxels, blocks, the stored pair, ESDF cells, sites and a camera's pixels are addressed and read: mapper_device.hpp.
 #include "mapper_device.hpp"
 
 namespace curobo_hip {
@@ -36,17 +36,11 @@ constexpr int kMapThreads = 256;
 constexpr int kEdtThreads = 256;
 constexpr int kEdtLdsWords = 8192;        // 32 KB: columns per tile = min(64, kEdtLdsWords / line length)
 constexpr int kEdtNoSite = 1 << 30;       // above 3 * 1023^2 + 1023^2; kEdtNoSite + 1023^2 does not overflow
-constexpr int kEsdfMaxAxis = 1024;        // sites pack 10 bits per axis
 
 struct MapCameras {
   const float *depth, *intrinsics, *position, *quaternion;
   int n, height, width;
 };
-
-__device__ __forceinline__ uint32_t pack_half2(float a, float b) {
-  const _Float16 ha = (_Float16)a, hb = (_Float16)b;  // round to nearest even
-  return (uint32_t)__builtin_bit_cast(uint16_t, ha) | ((uint32_t)__builtin_bit_cast(uint16_t, hb) << 16);
-}
 
 // ---------------------------------------------------------------------------------------------------- frame mask
 __global__ __launch_bounds__(kMapThreads) void mapper_clear_mask_kernel(uint32_t *mask, int64_t n_words) {
@@ -64,21 +58,17 @@ __global__ __launch_bounds__(kMapThreads) void mapper_mark_kernel(uint8_t *frame
   const int rem = (int)(tid - (int64_t)cam * per_cam);
   const int pixel = rem / g.num_samples, k = rem - pixel * g.num_samples;
   const int px = pixel % c.width, py = pixel / c.width;
-  const float *K = c.intrinsics + cam * 9;
-  const float fx = K[0], fy = K[4], cx = K[2], cy = K[5];
   const float depth = c.depth[(size_t)cam * n_pixels + pixel];
   if (depth < g.depth_min || depth > g.depth_max) return;
   const float z_start = fmaxf(depth - g.trunc, g.depth_min);
   const float z = z_start + (float)k * g.step;
   if (z > depth + g.trunc + g.step) return;
-  const f3 p_cam = make_f3(((float)px + 0.5f - cx) / fx * z, ((float)py + 0.5f - cy) / fy * z, z);
-  const float *q = c.quaternion + cam * 4, *t = c.position + cam * 3;
-  const f3 p = make_f3(t[0], t[1], t[2]) + quat_rotate(q[0], make_f3(q[1], q[2], q[3]), p_cam);
-  const int vx = (int)floorf((p.x - g.ox) / g.vs + (float)g.grid_w * 0.5f);
-  const int vy = (int)floorf((p.y - g.oy) / g.vs + (float)g.grid_h * 0.5f);
-  const int vz = (int)floorf((p.z - g.oz) / g.vs + (float)g.grid_d * 0.5f);
+  const MapCamera camera = read_camera(c.intrinsics, c.position, c.quaternion, cam);
+  const f3 p = camera.t + quat_rotate(camera.qw, camera.qv, z * pixel_ray<true>(camera, px, py));  // (the z = 1 ray scaled, not normalised)
+  const int vx = (int)floorf(grid_axis(g, p.x, g.ox, g.grid_w)), vy = (int)floorf(grid_axis(g, p.y, g.oy, g.grid_h));
+  const int vz = (int)floorf(grid_axis(g, p.z, g.oz, g.grid_d));
   if (vx < 0 || vx >= g.grid_w || vy < 0 || vy >= g.grid_h || vz < 0 || vz >= g.grid_d) return;
-  const int b = ((vz / g.bs) * g.nby + vy / g.bs) * g.nbx + vx / g.bs;  // < nbx nby nbz: the voxel is inside the grid
+  const int b = grid_block(g, vx, vy, vz);  // < nbx nby nbz: the voxel is inside the grid
   frame_mask[b] = 1;
   block_mask[b] = 1;
 }
@@ -87,94 +77,53 @@ __global__ __launch_bounds__(kMapThreads) void mapper_mark_kernel(uint8_t *frame
 __global__ __launch_bounds__(kMapThreads) void mapper_integrate_kernel(uint32_t *block_data, const uint8_t *frame_mask, MapCameras c, MapGrid g) {
   const int b = blockIdx.x;
   if (frame_mask[b] == 0) return;  // (uniform over the workgroup)
-  const int bx = b % g.nbx, by = (b / g.nbx) % g.nby, bz = b / (g.nbx * g.nby);
-  const int bs3 = g.bs * g.bs * g.bs;
+  const int bs3 = grid_block_voxels(g);
   for (int local = threadIdx.x; local < bs3; local += blockDim.x) {
-    const int lx = local % g.bs, ly = (local / g.bs) % g.bs, lz = local / (g.bs * g.bs);
-    const f3 centre = make_f3(((float)(bx * g.bs + lx) + 0.5f - (float)g.grid_w * 0.5f) * g.vs + g.ox,
-                              ((float)(by * g.bs + ly) + 0.5f - (float)g.grid_h * 0.5f) * g.vs + g.oy,
-                              ((float)(bz * g.bs + lz) + 0.5f - (float)g.grid_d * 0.5f) * g.vs + g.oz);
+    const i3 voxel = grid_voxel(g, b, local);
+    const f3 centre = grid_centre(g, voxel.x, voxel.y, voxel.z);
     float total_sw = 0.0f, total_w = 0.0f;
     for (int cam = 0; cam < c.n; cam++) {
-      const float *q = c.quaternion + cam * 4, *t = c.position + cam * 3;
-      // quat_inverse = the conjugate
-      const f3 v = quat_rotate(q[0], make_f3(-q[1], -q[2], -q[3]), centre - make_f3(t[0], t[1], t[2]));
+      const MapCamera camera = read_camera(c.intrinsics, c.position, c.quaternion, cam);
+      const f3 v = quat_rotate(camera.qw, make_f3(-camera.qv.x, -camera.qv.y, -camera.qv.z), centre - camera.t);  // quat_inverse = the conjugate
       // The depth along the camera's axis once more in double (the z row of the same rotation): sdf = depth - z cancels to
       // nothing at the surface, where an fp32 z leaves an absolute error of a few 1e-7 m -- more than one step of the fp16
       // word that stores sdf * weight there (steps of 6e-8 .. 5e-7 below 1e-3).  Pixel choice and weight stay fp32.
-      const double qw = q[0], qx = -(double)q[1], qy = -(double)q[2], qz = -(double)q[3];
-      const double ex = ((double)(bx * g.bs + lx) + 0.5 - (double)g.grid_w * 0.5) * (double)g.vs + (double)g.ox - (double)t[0];
-      const double ey = ((double)(by * g.bs + ly) + 0.5 - (double)g.grid_h * 0.5) * (double)g.vs + (double)g.oy - (double)t[1];
-      const double ez = ((double)(bz * g.bs + lz) + 0.5 - (double)g.grid_d * 0.5) * (double)g.vs + (double)g.oz - (double)t[2];
+      const double qw = camera.qw, qx = -(double)camera.qv.x, qy = -(double)camera.qv.y, qz = -(double)camera.qv.z;
+      const double ex = grid_centre_axis<double>(g, voxel.x, g.grid_w, g.ox) - (double)camera.t.x;
+      const double ey = grid_centre_axis<double>(g, voxel.y, g.grid_h, g.oy) - (double)camera.t.y;
+      const double ez = grid_centre_axis<double>(g, voxel.z, g.grid_d, g.oz) - (double)camera.t.z;
       const double zd = ez * (2.0 * qw * qw - 1.0) + 2.0 * qw * (qx * ey - qy * ex) + 2.0 * qz * (qx * ex + qy * ey + qz * ez);
       const float z = (float)zd;
       if (!(zd > (double)g.depth_min)) continue;
-      const float *K = c.intrinsics + cam * 9;
-      const float fx = K[0], fy = K[4];
-      const float u = fx * v.x / z + K[2], w = fy * v.y / z + K[5];
+      const float u = camera.fx * v.x / z + camera.cx, w = camera.fy * v.y / z + camera.cy;
       const int px = (int)u, py = (int)w;  // toward zero: u in (-1, 0) is pixel 0, as in the reference
       if (px < 0 || px >= c.width || py < 0 || py >= c.height) continue;
       const float depth = c.depth[((size_t)cam * c.height + py) * c.width + px];
       if (!(depth >= g.depth_min && depth <= g.depth_max)) continue;
       const float sdf = (float)((double)depth - zd);
       if (!(sdf >= -g.trunc)) continue;
-      const float weight = fmaxf((fx * g.vs / z) * (fy * g.vs / z), 1.0f);  // compute_tsdf_weight is 1
+      const float weight = fmaxf((camera.fx * g.vs / z) * (camera.fy * g.vs / z), 1.0f);  // compute_tsdf_weight is 1
       total_sw += fminf(sdf, g.trunc) * weight;
       total_w += weight;
     }
     if (total_w > 0.0f) {
       uint32_t *word = block_data + (size_t)b * bs3 + local;
-      const uint32_t old = *word;
-      *word = pack_half2(half_lo(old) + total_sw, half_hi(old) + total_w);
+      *word = tsdf_pair_add(*word, total_sw, total_w);
     }
   }
 }
-
-// ---------------------------------------------------------------------------------------------------- TSDF sample
-// sdf at a world position, kSdfInvalid when the voxel is outside the grid, its block was never visible or it is unobserved
-__device__ __forceinline__ float tsdf_sample(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, float wx, float wy,
-                                             float wz) {
-  const int gx = (int)((wx - g.ox) / g.vs + (float)g.grid_w * 0.5f);
-  const int gy = (int)((wy - g.oy) / g.vs + (float)g.grid_h * 0.5f);
-  const int gz = (int)((wz - g.oz) / g.vs + (float)g.grid_d * 0.5f);
-  if (gx < 0 || gx >= g.grid_w || gy < 0 || gy >= g.grid_h || gz < 0 || gz >= g.grid_d) return kSdfInvalid;
-  const int b = ((gz / g.bs) * g.nby + gy / g.bs) * g.nbx + gx / g.bs;
-  if (block_mask[b] == 0) return kSdfInvalid;
-  const int local = ((gz % g.bs) * g.bs + gy % g.bs) * g.bs + gx % g.bs;
-  const uint32_t v = block_data[(size_t)b * (g.bs * g.bs * g.bs) + local];
-  const float w = half_hi(v);
-  return w > g.min_weight ? half_lo(v) / w : kSdfInvalid;
-}
-
-__device__ __forceinline__ bool is_seed(float sdf, const MapGrid &g) {
-  if (sdf > 1e9f) return false;
-  return fabsf(sdf) <= g.vs * 0.9f || sdf < -(g.trunc - g.vs * 1.1f);
-}
-
-struct EsdfArgs {
-  const uint32_t *block_data;
-  const uint8_t *block_mask;
-  const float *origin, *voxel_size;
-  int d, h, w;
-};
 
 // ---------------------------------------------------------------------------------------------------- ESDF stage 1: seed
 __global__ __launch_bounds__(kMapThreads) void mapper_esdf_seed_kernel(int32_t *sites, EsdfArgs a, MapGrid g) {
   const int tid = blockIdx.x * kMapThreads + threadIdx.x;
   if (tid >= a.d * a.h * a.w) return;
   const int z = tid % a.w, y = (tid / a.w) % a.h, x = tid / (a.w * a.h);
-  const float vs = a.voxel_size[0], half = vs * 0.5f;
-  const float cx = a.origin[0] + ((float)x + 0.5f - (float)a.d * 0.5f) * vs;
-  const float cy = a.origin[1] + ((float)y + 0.5f - (float)a.h * 0.5f) * vs;
-  const float cz = a.origin[2] + ((float)z + 0.5f - (float)a.w * 0.5f) * vs;
-  const bool seed = is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx, cy, cz), g) ||
-                    is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx + half, cy, cz), g) ||
-                    is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx - half, cy, cz), g) ||
-                    is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx, cy + half, cz), g) ||
-                    is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx, cy - half, cz), g) ||
-                    is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx, cy, cz + half), g) ||
-                    is_seed(tsdf_sample(a.block_data, a.block_mask, g, cx, cy, cz - half), g);
-  sites[tid] = seed ? (x | (y << 10) | (z << 20)) : -1;
+  const float half = a.voxel_size[0] * 0.5f;
+  const f3 c = esdf_centre(a, x, y, z);
+  const auto seed_at = [&](float wx, float wy, float wz) { return is_seed(tsdf_probe(a.block_data, a.block_mask, g, make_f3(wx, wy, wz)), g); };
+  const bool seed = seed_at(c.x, c.y, c.z) || seed_at(c.x + half, c.y, c.z) || seed_at(c.x - half, c.y, c.z) || seed_at(c.x, c.y + half, c.z) ||
+                    seed_at(c.x, c.y - half, c.z) || seed_at(c.x, c.y, c.z + half) || seed_at(c.x, c.y, c.z - half);
+  sites[tid] = seed ? site_pack(x, y, z) : -1;
 }
 
 // ---------------------------------------------------------------------------------------------------- ESDF stage 2: one pass
@@ -204,7 +153,7 @@ __global__ __launch_bounds__(kEdtThreads) void mapper_edt_pass_kernel(EdtArgs a)
       if (s >= 0) {
         // the cell's own coordinates: axis 2 = (p, q, j), axis 1 = (p, j, q), axis 0 = (j, p, q)
         const int x = a.axis == 0 ? j : p, y = a.axis == 0 ? p : (a.axis == 1 ? j : q), z = a.axis == 2 ? j : q;
-        const int dx = x - (s & 0x3ff), dy = y - ((s >> 10) & 0x3ff), dz = z - ((s >> 20) & 0x3ff);
+        const int dx = site_offset(s, 0, x), dy = site_offset(s, 1, y), dz = site_offset(s, 2, z);
         v = dx * dx + dy * dy + dz * dz;
       }
     }
@@ -237,13 +186,10 @@ __global__ __launch_bounds__(kMapThreads) void mapper_esdf_distance_kernel(uint1
   float out = 1e4f;
   if (s >= 0) {
     const int z = tid % a.w, y = (tid / a.w) % a.h, x = tid / (a.w * a.h);
-    const float vs = a.voxel_size[0];
-    const float dx = (float)(x - (s & 0x3ff)), dy = (float)(y - ((s >> 10) & 0x3ff)), dz = (float)(z - ((s >> 20) & 0x3ff));
-    out = sqrtf(dx * dx + dy * dy + dz * dz) * vs;
-    const float sdf = tsdf_sample(a.block_data, a.block_mask, g, a.origin[0] + ((float)x + 0.5f - (float)a.d * 0.5f) * vs,
-                                  a.origin[1] + ((float)y + 0.5f - (float)a.h * 0.5f) * vs,
-                                  a.origin[2] + ((float)z + 0.5f - (float)a.w * 0.5f) * vs);
-    if (!(sdf > 1e9f) && sdf < 0.0f) out = -out;
+    const float dx = (float)site_offset(s, 0, x), dy = (float)site_offset(s, 1, y), dz = (float)site_offset(s, 2, z);
+    out = sqrtf(dx * dx + dy * dy + dz * dz) * a.voxel_size[0];
+    const float sdf = tsdf_probe(a.block_data, a.block_mask, g, esdf_centre(a, x, y, z));
+    if (sdf_is_valid(sdf) && sdf < 0.0f) out = -out;
   }
   distance[tid] = __builtin_bit_cast(uint16_t, (_Float16)out);
 }
@@ -256,12 +202,8 @@ __global__ __launch_bounds__(kMapThreads) void mapper_occupied_kernel(uint8_t *f
   if (i >= n_voxels) return;
   uint8_t flag = 0;
   if (block_mask[i / bs3] != 0) {
-    const uint32_t v = block_data[i];
-    const float w = half_hi(v);
-    if (w > min_weight) {
-      const float sdf = half_lo(v) / w;
-      flag = surface_only ? (fabsf(sdf) < sdf_threshold) : (sdf <= 0.0f);
-    }
+    const float sdf = tsdf_pair_sdf<false>(block_data[i], min_weight);  // (above the minimum, as the probe rule)
+    if (sdf_is_valid(sdf)) flag = surface_only ? (fabsf(sdf) < sdf_threshold) : (sdf <= 0.0f);
   }
   flags[i] = flag;
 }
@@ -292,14 +234,15 @@ __global__ __launch_bounds__(kMapThreads) void mapper_mesh_classify_kernel(uint8
   const int b = a.block_list[slot];
   if (b < 0 || b >= g.nbx * g.nby * g.nbz) return;  // (uniform over the workgroup; the caller's list holds block rows only)
   const int tx = tile % tiles, ty = (tile / tiles) % tiles, tz = tile / (tiles * tiles);
-  const int x0 = (b % g.nbx) * g.bs + tx * tb, y0 = ((b / g.nbx) % g.nby) * g.bs + ty * tb, z0 = (b / (g.nbx * g.nby)) * g.bs + tz * tb;
+  const i3 first = grid_voxel(g, b, 0);
+  const int x0 = first.x + tx * tb, y0 = first.y + ty * tb, z0 = first.z + tz * tb;
   const int tc = tb + 1;
   for (int idx = threadIdx.x; idx < tc * tc * tc; idx += blockDim.x) {
-    const float s = mesh_voxel(a.block_data, a.block_mask, g, x0 + idx % tc, y0 + (idx / tc) % tc, z0 + idx / (tc * tc));
-    corner[idx] = s > 1e9f ? kSdfInvalid : s - a.level;
+    const float s = tsdf_voxel(a.block_data, a.block_mask, g, x0 + idx % tc, y0 + (idx / tc) % tc, z0 + idx / (tc * tc));
+    corner[idx] = sdf_is_valid(s) ? s - a.level : kSdfInvalid;
   }
   __syncthreads();
-  const int bs3 = g.bs * g.bs * g.bs;
+  const int bs3 = grid_block_voxels(g);
   for (int v = threadIdx.x; v < tb * tb * tb; v += blockDim.x) {
     const int lx = v % tb, ly = (v / tb) % tb, lz = v / (tb * tb);
     const int at = (lz * tc + ly) * tc + lx;
@@ -310,7 +253,7 @@ __global__ __launch_bounds__(kMapThreads) void mapper_mesh_classify_kernel(uint8
     int config = 0;
 #pragma unroll
     for (int c = 0; c < 8; c++) {
-      valid &= !(s[c] > 1e9f);
+      valid &= sdf_is_valid(s[c]);
       positive |= s[c] > 0.0f;
       negative |= s[c] < 0.0f;
       in_band |= fabsf(s[c]) < g.trunc;
@@ -334,7 +277,7 @@ __global__ __launch_bounds__(kMapThreads) void mapper_mesh_classify_kernel(uint8
 __global__ __launch_bounds__(kMapThreads) void mapper_mesh_vertices_kernel(float *vertices, float *normals, int32_t *vert_ids, int n_vertices,
                                                                            const uint8_t *vert_count, const int32_t *vert_offset, MeshArgs a,
                                                                            int refine_iterations, MapGrid g) {
-  const int bs3 = g.bs * g.bs * g.bs;
+  const int bs3 = grid_block_voxels(g);
   const int64_t i = (int64_t)blockIdx.x * kMapThreads + threadIdx.x;
   if (i >= (int64_t)a.n_slots * bs3) return;
   int32_t *ids = vert_ids + (size_t)i * 3;
@@ -343,19 +286,16 @@ __global__ __launch_bounds__(kMapThreads) void mapper_mesh_vertices_kernel(float
   const int slot = (int)(i / bs3), local = (int)(i - (int64_t)slot * bs3);
   const int b = a.block_list[slot];
   if (b < 0 || b >= g.nbx * g.nby * g.nbz) return;
-  const int gx = (b % g.nbx) * g.bs + local % g.bs, gy = ((b / g.nbx) % g.nby) * g.bs + (local / g.bs) % g.bs;
-  const int gz = (b / (g.nbx * g.nby)) * g.bs + local / (g.bs * g.bs);
+  const i3 voxel = grid_voxel(g, b, local);
+  const int gx = voxel.x, gy = voxel.y, gz = voxel.z;
   // (a surface cube: all four are valid)
-  const float s0 = mesh_voxel(a.block_data, a.block_mask, g, gx, gy, gz) - a.level;
-  const float sb[3] = {mesh_voxel(a.block_data, a.block_mask, g, gx + 1, gy, gz) - a.level,
-                       mesh_voxel(a.block_data, a.block_mask, g, gx, gy + 1, gz) - a.level,
-                       mesh_voxel(a.block_data, a.block_mask, g, gx, gy, gz + 1) - a.level};
-  // the voxel centres origin + (g + 0.5 - N / 2) voxel_size: where the TSDF was sampled
-  const float pa[3] = {((float)gx + 0.5f - (float)g.grid_w * 0.5f) * g.vs + g.ox, ((float)gy + 0.5f - (float)g.grid_h * 0.5f) * g.vs + g.oy,
-                       ((float)gz + 0.5f - (float)g.grid_d * 0.5f) * g.vs + g.oz};
-  const float pb[3] = {((float)(gx + 1) + 0.5f - (float)g.grid_w * 0.5f) * g.vs + g.ox,
-                       ((float)(gy + 1) + 0.5f - (float)g.grid_h * 0.5f) * g.vs + g.oy,
-                       ((float)(gz + 1) + 0.5f - (float)g.grid_d * 0.5f) * g.vs + g.oz};
+  const float s0 = tsdf_voxel(a.block_data, a.block_mask, g, gx, gy, gz) - a.level;
+  const float sb[3] = {tsdf_voxel(a.block_data, a.block_mask, g, gx + 1, gy, gz) - a.level,
+                       tsdf_voxel(a.block_data, a.block_mask, g, gx, gy + 1, gz) - a.level,
+                       tsdf_voxel(a.block_data, a.block_mask, g, gx, gy, gz + 1) - a.level};
+  // the cube's edges run between voxel centres: this voxel's and, per axis, its upper neighbour's
+  const f3 ca = grid_centre(g, gx, gy, gz), cb = grid_centre(g, gx + 1, gy + 1, gz + 1);
+  const float pa[3] = {ca.x, ca.y, ca.z}, pb[3] = {cb.x, cb.y, cb.z};
   int vid = vert_offset[i];
 #pragma unroll
   for (int axis = 0; axis < 3; axis++) {
@@ -366,15 +306,15 @@ __global__ __launch_bounds__(kMapThreads) void mapper_mesh_vertices_kernel(float
     p[axis] = pa[axis] + t * (pb[axis] - pa[axis]);
     f3 pos = make_f3(p[0], p[1], p[2]);
     for (int it = 0; it < refine_iterations; it++) {
-      const float sdf = mesh_trilinear(a.block_data, a.block_mask, g, pos);
-      if (sdf > 1e9f) break;
+      const float sdf = tsdf_trilinear(a.block_data, a.block_mask, g, pos);
+      if (sdf_is_invalid(sdf)) break;
       const float value = sdf - a.level;
       if (fabsf(value) < 1e-6f || value > 100.0f) break;
-      const f3 dir = mesh_gradient<true>(a.block_data, a.block_mask, g, pos);
+      const f3 dir = tsdf_gradient<true>(a.block_data, a.block_mask, g, pos);
       const float step = fminf(fmaxf(value, -0.5f * g.vs), 0.5f * g.vs);
       pos = pos - step * dir;
     }
-    const f3 n = mesh_gradient<false>(a.block_data, a.block_mask, g, pos);
+    const f3 n = tsdf_gradient<false>(a.block_data, a.block_mask, g, pos);
     float *vo = vertices + (size_t)vid * 3, *no = normals + (size_t)vid * 3;
     vo[0] = pos.x, vo[1] = pos.y, vo[2] = pos.z;
     no[0] = n.x, no[1] = n.y, no[2] = n.z;
@@ -389,7 +329,7 @@ __global__ __launch_bounds__(kMapThreads) void mapper_mesh_triangles_kernel(int3
                                                                             const uint8_t *tri_count, const int32_t *tri_offset,
                                                                             const int32_t *vert_ids, const float *vertices, int n_vertices, MeshArgs a,
                                                                             const int8_t *table, const int8_t *edge_owner, MapGrid g) {
-  const int bs3 = g.bs * g.bs * g.bs;
+  const int bs3 = grid_block_voxels(g);
   const int64_t i = (int64_t)blockIdx.x * kMapThreads + threadIdx.x;
   if (i >= (int64_t)a.n_slots * bs3) return;
   const int count = tri_count[i];
@@ -397,8 +337,8 @@ __global__ __launch_bounds__(kMapThreads) void mapper_mesh_triangles_kernel(int3
   const int slot = (int)(i / bs3), local = (int)(i - (int64_t)slot * bs3);
   const int b = a.block_list[slot];
   if (b < 0 || b >= g.nbx * g.nby * g.nbz) return;
-  const int gx = (b % g.nbx) * g.bs + local % g.bs, gy = ((b / g.nbx) % g.nby) * g.bs + (local / g.bs) % g.bs;
-  const int gz = (b / (g.nbx * g.nby)) * g.bs + local / (g.bs * g.bs);
+  const i3 voxel = grid_voxel(g, b, local);
+  const int gx = voxel.x, gy = voxel.y, gz = voxel.z;
   const int8_t *row = table + (int)cube_case[i] * 16;
   const int base = tri_offset[i];
   const float min_cross2 = (g.vs * 1e-6f) * (g.vs * 1e-6f);
@@ -412,9 +352,9 @@ __global__ __launch_bounds__(kMapThreads) void mapper_mesh_triangles_kernel(int3
       if (e < 0 || e >= 12) continue;
       const int ox = gx + edge_owner[e * 4], oy = gy + edge_owner[e * 4 + 1], oz = gz + edge_owner[e * 4 + 2], axis = edge_owner[e * 4 + 3];
       if (ox >= g.nbx * g.bs || oy >= g.nby * g.bs || oz >= g.nbz * g.bs || axis < 0 || axis > 2) continue;
-      const int os = a.block_slot[((oz / g.bs) * g.nby + oy / g.bs) * g.nbx + ox / g.bs];
+      const int os = a.block_slot[grid_block(g, ox, oy, oz)];
       if (os < 0 || os >= a.n_slots) continue;
-      id[k] = vert_ids[((size_t)os * bs3 + ((oz % g.bs) * g.bs + oy % g.bs) * g.bs + ox % g.bs) * 3 + axis];
+      id[k] = vert_ids[((size_t)os * bs3 + grid_local(g, ox, oy, oz)) * 3 + axis];
       if (id[k] >= n_vertices) id[k] = -1;
     }
     bool stays = id[0] >= 0 && id[1] >= 0 && id[2] >= 0 && id[0] != id[1] && id[1] != id[2] && id[0] != id[2];
@@ -498,22 +438,24 @@ CUROBO_EXPORT int curobo_hip_mapper_integrate(void *block_data, const uint8_t *f
   MapCameras c;
   if (int rc = read_params(params, &g, what)) return rc;
   if (int rc = read_cameras(&c, depth, intrinsics, cam_position, cam_quaternion, n_cameras, height, width, what)) return rc;
-  CUROBO_REQUIRE(block_data && frame_mask, "%s: block_data and frame_mask must not be null", what);
-  CUROBO_REQUIRE(((uintptr_t)block_data & 3) == 0, "%s: block_data must be 4-byte aligned", what);
+  if (int rc = check_map(block_data && frame_mask, block_data, "block_data and frame_mask", what)) return rc;
   const int bs3 = g.bs * g.bs * g.bs;
   hipLaunchKernelGGL(mapper_integrate_kernel, dim3((unsigned)map_blocks(g)), dim3(bs3 >= kMapThreads ? kMapThreads : kWave), 0,
                      (hipStream_t)stream, (uint32_t *)block_data, frame_mask, c, g);
   return check_launch(what, (hipStream_t)stream);
 }
 
-static int read_esdf(EsdfArgs *a, const void *block_data, const uint8_t *block_mask, const float *esdf_origin, const float *esdf_voxel_size,
-                     int esdf_d, int esdf_h, int esdf_w, const char *what) {
-  CUROBO_REQUIRE(block_data && block_mask && esdf_origin && esdf_voxel_size,
-                 "%s: block_data, block_mask, esdf_origin and esdf_voxel_size must not be null", what);
-  CUROBO_REQUIRE(((uintptr_t)block_data & 3) == 0, "%s: block_data must be 4-byte aligned", what);
+static int check_esdf_shape(int esdf_d, int esdf_h, int esdf_w, const char *what) {
   CUROBO_REQUIRE(esdf_d > 0 && esdf_h > 0 && esdf_w > 0 && esdf_d <= kEsdfMaxAxis && esdf_h <= kEsdfMaxAxis && esdf_w <= kEsdfMaxAxis,
                  "%s: every axis of the ESDF grid must hold 1..%d cells (sites pack 10 bits per axis), got %d x %d x %d", what, kEsdfMaxAxis,
                  esdf_d, esdf_h, esdf_w);
+  return CUROBO_HIP_OK;
+}
+static int read_esdf(EsdfArgs *a, const void *block_data, const uint8_t *block_mask, const float *esdf_origin, const float *esdf_voxel_size,
+                     int esdf_d, int esdf_h, int esdf_w, const char *what) {
+  if (int rc = check_map(block_data && block_mask && esdf_origin && esdf_voxel_size, block_data,
+                         "block_data, block_mask, esdf_origin and esdf_voxel_size", what)) return rc;
+  if (int rc = check_esdf_shape(esdf_d, esdf_h, esdf_w, what)) return rc;
   a->block_data = (const uint32_t *)block_data, a->block_mask = block_mask, a->origin = esdf_origin, a->voxel_size = esdf_voxel_size;
   a->d = esdf_d, a->h = esdf_h, a->w = esdf_w;
   return CUROBO_HIP_OK;
@@ -537,9 +479,7 @@ CUROBO_EXPORT int curobo_hip_mapper_edt_pass(int32_t *sites_out, const int32_t *
                                              curobo_hip_stream_t stream) {
   const char *what = "mapper_edt_pass";
   CUROBO_REQUIRE(sites_out && sites_in, "%s: sites_out and sites_in must not be null", what);
-  CUROBO_REQUIRE(esdf_d > 0 && esdf_h > 0 && esdf_w > 0 && esdf_d <= kEsdfMaxAxis && esdf_h <= kEsdfMaxAxis && esdf_w <= kEsdfMaxAxis,
-                 "%s: every axis of the ESDF grid must hold 1..%d cells (sites pack 10 bits per axis), got %d x %d x %d", what, kEsdfMaxAxis,
-                 esdf_d, esdf_h, esdf_w);
+  if (int rc = check_esdf_shape(esdf_d, esdf_h, esdf_w, what)) return rc;
   CUROBO_REQUIRE(axis >= 0 && axis <= 2, "%s: axis must be 0 (x), 1 (y) or 2 (z), got %d", what, axis);
   const int64_t cells = (int64_t)esdf_d * esdf_h * esdf_w;
   CUROBO_REQUIRE(sites_out + cells <= sites_in || sites_in + cells <= sites_out, "%s: sites_out and sites_in must not overlap", what);
@@ -583,8 +523,7 @@ CUROBO_EXPORT int curobo_hip_mapper_occupied_flags(uint8_t *flags, const void *b
   const char *what = "mapper_occupied_flags";
   MapGrid g;
   if (int rc = read_params(params, &g, what)) return rc;
-  CUROBO_REQUIRE(flags && block_data && block_mask, "%s: flags, block_data and block_mask must not be null", what);
-  CUROBO_REQUIRE(((uintptr_t)block_data & 3) == 0, "%s: block_data must be 4-byte aligned", what);
+  if (int rc = check_map(flags && block_data && block_mask, block_data, "flags, block_data and block_mask", what)) return rc;
   const int bs3 = g.bs * g.bs * g.bs;
   const int64_t voxels = map_blocks(g) * bs3;
   hipLaunchKernelGGL(mapper_occupied_kernel, dim3((unsigned)ceil_div_l(voxels, kMapThreads)), dim3(kMapThreads), 0, (hipStream_t)stream, flags,
@@ -592,12 +531,14 @@ CUROBO_EXPORT int curobo_hip_mapper_occupied_flags(uint8_t *flags, const void *b
   return check_launch(what, (hipStream_t)stream);
 }
 
+static int check_slots(int n_slots, const MapGrid &g, const char *what) {
+  CUROBO_REQUIRE(n_slots > 0 && n_slots <= map_blocks(g), "%s: block_list must hold 1..%lld blocks, got %d", what, (long long)map_blocks(g), n_slots);
+  return CUROBO_HIP_OK;
+}
 static int read_mesh(MeshArgs *a, const void *block_data, const uint8_t *block_mask, const int32_t *block_list, const int32_t *block_slot,
                      int n_slots, float level, const MapGrid &g, const char *what) {
-  CUROBO_REQUIRE(block_data && block_mask && block_list, "%s: block_data, block_mask and block_list must not be null", what);
-  CUROBO_REQUIRE(((uintptr_t)block_data & 3) == 0, "%s: block_data must be 4-byte aligned", what);
-  CUROBO_REQUIRE(n_slots > 0 && n_slots <= map_blocks(g), "%s: block_list must hold 1..%lld blocks, got %d", what, (long long)map_blocks(g),
-                 n_slots);
+  if (int rc = check_map(block_data && block_mask && block_list, block_data, "block_data, block_mask and block_list", what)) return rc;
+  if (int rc = check_slots(n_slots, g, what)) return rc;
   a->block_data = (const uint32_t *)block_data, a->block_mask = block_mask, a->block_list = block_list, a->block_slot = block_slot;
   a->n_slots = n_slots, a->level = level;
   return CUROBO_HIP_OK;
@@ -650,8 +591,7 @@ CUROBO_EXPORT int curobo_hip_mapper_mesh_triangles(int32_t *raw_triangles, uint8
   CUROBO_REQUIRE(raw_triangles && keep && cube_case && tri_count && tri_offset && vert_ids && vertices && block_list && block_slot && table &&
                      edge_owner,
                  "%s: no pointer may be null", what);
-  CUROBO_REQUIRE(n_slots > 0 && n_slots <= map_blocks(g), "%s: block_list must hold 1..%lld blocks, got %d", what, (long long)map_blocks(g),
-                 n_slots);
+  if (int rc = check_slots(n_slots, g, what)) return rc;
   MeshArgs a{};  // (this launch reads no TSDF)
   a.block_list = block_list, a.block_slot = block_slot, a.n_slots = n_slots;
   CUROBO_REQUIRE(n_raw > 0 && n_vertices > 0, "%s: n_raw and n_vertices must be positive, got %d and %d", what, n_raw, n_vertices);

@@ -1,58 +1,97 @@
-// mapper_device.hpp -- what the mapper's units share (mapper.hip: integration, ESDF, mesh extraction; mapper_raycast.hip:
-// rendering and the along-ray alignment): the grid as the launches see it, the fp16 pair's halves, wp.quat_rotate, and the
-// reads of the TSDF -- one voxel, the nearest voxel, the trilinear sample and the gradients of builder_raycast.py
-// (sample_voxel :63-90, sample_tsdf_trilinear :168-258, compute_gradient :277-375).  The samplers take the two arrays they
-// read, block_data and block_mask, and nothing else of a launch's arguments.
+// mapper_device.hpp -- the one statement of the mapper's grid for mapper.hip and mapper_raycast.hip: how a world position, a voxel,
+// a block, the stored fp16 pair, an ESDF cell, a packed site and a camera's pixel are addressed and read.  The lookups take the two
+// arrays they read, block_data and block_mask, and nothing else of a launch's arguments.
 #pragma once
 #include "common.hpp"
 
 namespace curobo_hip {
 
-constexpr float kSdfInvalid = 1e10f;      // wp_tsdf_sample.py SDF_INFINITY as the lookups return it
-
+constexpr float kSdfInvalid = 1e10f, kSdfValidBelow = kSdfInvalid / 10.0f;  // SDF_INFINITY as the lookups return it; = 1e9f, builder_esdf.py:299
+constexpr int kSiteBits = 10, kSiteMask = 0x3ff, kEsdfMaxAxis = 1 << kSiteBits;  // a site packs three coordinates of 10 bits: an axis has <= 1024 cells
 struct MapGrid {
   int grid_w, grid_h, grid_d, bs, nbx, nby, nbz, num_samples;
   float ox, oy, oz, vs, trunc, depth_min, depth_max, min_weight, step;
 };
-
+struct EsdfArgs {
+  const uint32_t *block_data;
+  const uint8_t *block_mask;
+  const float *origin, *voxel_size;
+  int d, h, w;
+};
 #if defined(__HIPCC__)
-
-// wp.quat_rotate for q = (w, v): x (2 w^2 - 1) + 2 w (v x x) + 2 v (v . x)
-__device__ __forceinline__ f3 quat_rotate(float w, f3 v, f3 x) {
-  return (2.0f * w * w - 1.0f) * x + (2.0f * w) * cross(v, x) + (2.0f * dot(v, x)) * v;
+struct i3 { int x, y, z; };
+// continuous voxel coordinate of a world position (builder_coord.py:45-54): one axis (origin o, n voxels), and all three
+__device__ __forceinline__ float grid_axis(const MapGrid &g, float p, float o, int n) { return (p - o) / g.vs + (float)n * 0.5f; }
+__device__ __forceinline__ f3 grid_continuous(const MapGrid &g, f3 p) {
+  return make_f3(grid_axis(g, p.x, g.ox, g.grid_w), grid_axis(g, p.y, g.oy, g.grid_h), grid_axis(g, p.z, g.oz, g.grid_d));
 }
-
+// centre of voxel gv of an axis (n voxels, origin o), where the TSDF was sampled: o + (gv + 0.5 - n / 2) voxel_size
+// (builder_coord.py:57-66); T = double for the integrate kernel's depth along the camera axis
+template <typename T> __device__ __forceinline__ T grid_centre_axis(const MapGrid &g, int gv, int n, float o) {
+  return ((T)gv + (T)0.5 - (T)n * (T)0.5) * (T)g.vs + (T)o;
+}
+__device__ __forceinline__ f3 grid_centre(const MapGrid &g, int gx, int gy, int gz) {
+  return make_f3(grid_centre_axis<float>(g, gx, g.grid_w, g.ox), grid_centre_axis<float>(g, gy, g.grid_h, g.oy), grid_centre_axis<float>(g, gz, g.grid_d, g.oz));
+}
+// lower (UPPER: upper) face of block b of an axis, b a whole number held as a float (ray_block_exit_t).  Not grid_centre_axis: a
+// face has no half voxel and b stays a float, (b bs - n / 2) vs + o, so the centre's sum would be reassociated
+template <bool UPPER> __device__ __forceinline__ float grid_face(const MapGrid &g, float b, int n, float o) {
+  return ((UPPER ? b * (float)g.bs + (float)g.bs : b * (float)g.bs) - (float)n * 0.5f) * g.vs + o;
+}
+__device__ __forceinline__ int grid_block_voxels(const MapGrid &g) { return g.bs * g.bs * g.bs; }
+// block (bx, by, bz) is row (bz nby + by) nbx + bx; voxel (lx, ly, lz) of a block is its word (lz bs + ly) bs + lx (builder_coord.py:163-176)
+__device__ __forceinline__ int grid_block(const MapGrid &g, int gx, int gy, int gz) { return ((gz / g.bs) * g.nby + gy / g.bs) * g.nbx + gx / g.bs; }
+__device__ __forceinline__ int grid_local(const MapGrid &g, int gx, int gy, int gz) { return ((gz % g.bs) * g.bs + gy % g.bs) * g.bs + gx % g.bs; }
+__device__ __forceinline__ i3 grid_voxel(const MapGrid &g, int b, int local) {
+  return i3{(b % g.nbx) * g.bs + local % g.bs, ((b / g.nbx) % g.nby) * g.bs + (local / g.bs) % g.bs, (b / (g.nbx * g.nby)) * g.bs + local / (g.bs * g.bs)};
+}
 __device__ __forceinline__ float half_lo(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(v & 0xffffu)); }
 __device__ __forceinline__ float half_hi(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(v >> 16)); }
-
-// the stored sdf of voxel (gx, gy, gz) of the PADDED grid, kSdfInvalid where there is no such voxel, its block was never
-// visible or its weight is below the minimum (>=: builder_raycast.py:78, the lookups of the mesh and the renderer)
-__device__ __forceinline__ float mesh_voxel(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, int gx, int gy, int gz) {
-  if (gx < 0 || gx >= g.nbx * g.bs || gy < 0 || gy >= g.nby * g.bs || gz < 0 || gz >= g.nbz * g.bs) return kSdfInvalid;
-  const int b = ((gz / g.bs) * g.nby + gy / g.bs) * g.nbx + gx / g.bs;
-  if (block_mask[b] == 0) return kSdfInvalid;
-  const int local = ((gz % g.bs) * g.bs + gy % g.bs) * g.bs + gx % g.bs;
-  const uint32_t v = block_data[(size_t)b * (g.bs * g.bs * g.bs) + local];
+__device__ __forceinline__ uint32_t pack_half2(float a, float b) {  // (the casts round to nearest even)
+  return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)a) | ((uint32_t)__builtin_bit_cast(uint16_t, (_Float16)b) << 16);
+}
+__device__ __forceinline__ uint32_t tsdf_pair_add(uint32_t v, float sw, float w) { return pack_half2(half_lo(v) + sw, half_hi(v) + w); }
+// a lookup's answer is invalid above kSdfValidBelow; a value that is not a number counts as valid, as the kernels have left it
+__device__ __forceinline__ bool sdf_is_invalid(float s) { return s > kSdfValidBelow; }
+__device__ __forceinline__ bool sdf_is_valid(float s) { return !(s > kSdfValidBelow); }
+// the pair's sdf, kSdfInvalid below the minimum weight (the reference compares both ways: the two lookups); then a voxel that exists, read so
+template <bool AT_MINIMUM_TOO> __device__ __forceinline__ float tsdf_pair_sdf(uint32_t v, float min_weight) {
   const float w = half_hi(v);
-  return w >= g.min_weight ? half_lo(v) / w : kSdfInvalid;
+  return (AT_MINIMUM_TOO ? w >= min_weight : w > min_weight) ? half_lo(v) / w : kSdfInvalid;
 }
-
-// continuous voxel coordinate of a world position (builder_coord.py:45-54)
-__device__ __forceinline__ f3 mesh_continuous(const MapGrid &g, f3 p) {
-  return make_f3((p.x - g.ox) / g.vs + (float)g.grid_w * 0.5f, (p.y - g.oy) / g.vs + (float)g.grid_h * 0.5f,
-                 (p.z - g.oz) / g.vs + (float)g.grid_d * 0.5f);
+template <bool AT_MINIMUM_TOO>
+__device__ __forceinline__ float tsdf_read(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, int gx, int gy, int gz) {
+  const int b = grid_block(g, gx, gy, gz);
+  if (block_mask[b] == 0) return kSdfInvalid;
+  const int local = grid_local(g, gx, gy, gz);
+  return tsdf_pair_sdf<AT_MINIMUM_TOO>(block_data[(size_t)b * grid_block_voxels(g) + local], g.min_weight);
 }
-
+// THE PROBE RULE, of the ESDF path (builder_esdf.py:279-291, wp_tsdf_sample.py:46-52): the voxel of a world position by a cast
+// toward zero (a coordinate in (-1, 0) is voxel 0), which must lie in the grid proper, observed when its weight is ABOVE the minimum
+__device__ __forceinline__ float tsdf_probe(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, f3 p) {
+  const int gx = (int)grid_axis(g, p.x, g.ox, g.grid_w), gy = (int)grid_axis(g, p.y, g.oy, g.grid_h), gz = (int)grid_axis(g, p.z, g.oz, g.grid_d);
+  if (gx < 0 || gx >= g.grid_w || gy < 0 || gy >= g.grid_h || gz < 0 || gz >= g.grid_d) return kSdfInvalid;
+  return tsdf_read<false>(block_data, block_mask, g, gx, gy, gz);
+}
+// THE SAMPLE RULE, of the mesh, the renderer and the refiner (builder_raycast.py:63-90, the comparison :78): voxel (gx, gy, gz) of
+// the PADDED grid (the samplers below reach it by floor), observed when its weight is AT LEAST the minimum
+__device__ __forceinline__ float tsdf_voxel(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, int gx, int gy, int gz) {
+  if (gx < 0 || gx >= g.nbx * g.bs || gy < 0 || gy >= g.nby * g.bs || gz < 0 || gz >= g.nbz * g.bs) return kSdfInvalid;
+  return tsdf_read<true>(block_data, block_mask, g, gx, gy, gz);
+}
+__device__ __forceinline__ bool is_seed(float sdf, const MapGrid &g) {
+  if (sdf_is_invalid(sdf)) return false;
+  return fabsf(sdf) <= g.vs * 0.9f || sdf < -(g.trunc - g.vs * 1.1f);
+}
 // nearest-voxel sample: voxel floor(v)  (builder_raycast.py:92-109)
-__device__ __forceinline__ float mesh_nearest(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, f3 p) {
-  const f3 v = mesh_continuous(g, p);
-  return mesh_voxel(block_data, block_mask, g, (int)floorf(v.x), (int)floorf(v.y), (int)floorf(v.z));
+__device__ __forceinline__ float tsdf_nearest(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, f3 p) {
+  const f3 v = grid_continuous(g, p);
+  return tsdf_voxel(block_data, block_mask, g, (int)floorf(v.x), (int)floorf(v.y), (int)floorf(v.z));
 }
-
 // trilinear sample, lower corner floor(v - 0.5); an invalid corner contributes the truncation distance, no valid corner at
 // all makes the sample invalid  (builder_raycast.py:168-258)
-__device__ __forceinline__ float mesh_trilinear(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, f3 p) {
-  const f3 v = mesh_continuous(g, p);
+__device__ __forceinline__ float tsdf_trilinear(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, f3 p) {
+  const f3 v = grid_continuous(g, p);
   const float fx = v.x - 0.5f, fy = v.y - 0.5f, fz = v.z - 0.5f;
   const float x0 = floorf(fx), y0 = floorf(fy), z0 = floorf(fz);
   const float tx = fx - x0, ty = fy - y0, tz = fz - z0;
@@ -62,36 +101,56 @@ __device__ __forceinline__ float mesh_trilinear(const uint32_t *block_data, cons
 #pragma unroll
   for (int k = 0; k < 8; k++) {
     const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-    const float s = mesh_voxel(block_data, block_mask, g, ix + dx, iy + dy, iz + dz);
-    const bool ok = !(s > 1e9f);
+    const float s = tsdf_voxel(block_data, block_mask, g, ix + dx, iy + dy, iz + dz);
+    const bool ok = sdf_is_valid(s);
     any_valid |= ok;
     total += (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty) * (dz ? tz : 1.0f - tz) * (ok ? s : g.trunc);
   }
   return any_valid ? total : kSdfInvalid;
 }
-
 // normalised central difference of six samples at +-voxel_size; (0, 0, 1) where one of them is invalid or the magnitude is
 // below 1e-6  (builder_raycast.py:277-325 with trilinear samples, :327-375 with nearest-voxel samples)
 template <bool TRILINEAR>
-__device__ __forceinline__ f3 mesh_gradient(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, f3 p) {
+__device__ __forceinline__ f3 tsdf_gradient(const uint32_t *block_data, const uint8_t *block_mask, const MapGrid &g, f3 p) {
   float s[6];
 #pragma unroll
   for (int k = 0; k < 6; k++) {
     const float e = (k & 1) ? -g.vs : g.vs;
     const f3 q = make_f3(p.x + (k / 2 == 0 ? e : 0.0f), p.y + (k / 2 == 1 ? e : 0.0f), p.z + (k / 2 == 2 ? e : 0.0f));
-    s[k] = TRILINEAR ? mesh_trilinear(block_data, block_mask, g, q) : mesh_nearest(block_data, block_mask, g, q);
+    s[k] = TRILINEAR ? tsdf_trilinear(block_data, block_mask, g, q) : tsdf_nearest(block_data, block_mask, g, q);
   }
   const f3 up = make_f3(0.0f, 0.0f, 1.0f);
-  if (s[0] > 1e9f || s[1] > 1e9f || s[2] > 1e9f || s[3] > 1e9f || s[4] > 1e9f || s[5] > 1e9f) return up;
+  if (sdf_is_invalid(s[0]) || sdf_is_invalid(s[1]) || sdf_is_invalid(s[2]) || sdf_is_invalid(s[3]) || sdf_is_invalid(s[4]) || sdf_is_invalid(s[5])) return up;
   const f3 grad = make_f3((s[0] - s[1]) / (2.0f * g.vs), (s[2] - s[3]) / (2.0f * g.vs), (s[4] - s[5]) / (2.0f * g.vs));
   const float mag = sqrtf(grad.x * grad.x + grad.y * grad.y + grad.z * grad.z);
   if (mag < 1e-6f) return up;
   return make_f3(grad.x / mag, grad.y / mag, grad.z / mag);
 }
-
+// centre of cell (x, y, z) of the ESDF grid, x the slowest axis, of d cells (builder_esdf.py:334-336)
+__device__ __forceinline__ f3 esdf_centre(const EsdfArgs &a, int x, int y, int z) {
+  const float vs = a.voxel_size[0];
+  return make_f3(a.origin[0] + ((float)x + 0.5f - (float)a.d * 0.5f) * vs, a.origin[1] + ((float)y + 0.5f - (float)a.h * 0.5f) * vs,
+                 a.origin[2] + ((float)z + 0.5f - (float)a.w * 0.5f) * vs);
+}
+__device__ __forceinline__ int32_t site_pack(int x, int y, int z) { return x | (y << kSiteBits) | (z << (2 * kSiteBits)); }
+// coordinate c of a cell minus that coordinate (axis 0, 1, 2) of the cell that site s names
+__device__ __forceinline__ int site_offset(int32_t s, int axis, int c) { return c - ((s >> (axis * kSiteBits)) & kSiteMask); }
+// wp.quat_rotate for q = (w, v): x (2 w^2 - 1) + 2 w (v x x) + 2 v (v . x)
+__device__ __forceinline__ f3 quat_rotate(float w, f3 v, f3 x) {
+  return (2.0f * w * w - 1.0f) * x + (2.0f * w) * cross(v, x) + (2.0f * dot(v, x)) * v;
+}
+// camera `cam` of the arrays intrinsics [n, 3, 3], position [n, 3], quaternion [n, 4] wxyz: its pose in the world is t, (qw, qv)
+struct MapCamera { float fx, fy, cx, cy; f3 t; float qw; f3 qv; };
+__device__ __forceinline__ MapCamera read_camera(const float *intrinsics, const float *position, const float *quaternion, int cam) {
+  const float *K = intrinsics + cam * 9, *q = quaternion + cam * 4, *t = position + cam * 3;
+  return MapCamera{K[0], K[4], K[2], K[5], make_f3(t[0], t[1], t[2]), q[0], make_f3(q[1], q[2], q[3])};
+}
+// the ray of pixel (px, py) in the camera frame, z = 1, NOT normalised (marking scales it by z, the ray launches normalise it).
+// HALF_PIXEL: through the pixel's centre (builder_camera_integrate.py:125-127, the renders); not so wp_raycast_pose_refine.py:171-172
+template <bool HALF_PIXEL> __device__ __forceinline__ f3 pixel_ray(const MapCamera &c, int px, int py) {
+  return make_f3(((HALF_PIXEL ? (float)px + 0.5f : (float)px) - c.cx) / c.fx, ((HALF_PIXEL ? (float)py + 0.5f : (float)py) - c.cy) / c.fy, 1.0f);
+}
 #endif  // __HIPCC__
-
-// ---------------------------------------------------------------------------------------------------- host side
 static int read_params(const curobo_hip_mapper_params *p, MapGrid *g, const char *what) {
   CUROBO_REQUIRE(p, "%s: params must not be null", what);
   CUROBO_REQUIRE(p->grid_w > 0 && p->grid_h > 0 && p->grid_d > 0, "%s: the grid must have voxels along every axis, got %d x %d x %d", what,
@@ -109,6 +168,11 @@ static int read_params(const curobo_hip_mapper_params *p, MapGrid *g, const char
   g->num_samples = p->num_samples, g->ox = p->origin[0], g->oy = p->origin[1], g->oz = p->origin[2], g->vs = p->voxel_size;
   g->trunc = p->truncation_distance, g->depth_min = p->depth_min, g->depth_max = p->depth_max, g->min_weight = p->minimum_tsdf_weight;
   g->step = p->step_size;
+  return CUROBO_HIP_OK;
+}
+static int check_map(bool pointers_non_null, const void *block_data, const char *pointer_names, const char *what) {
+  CUROBO_REQUIRE(pointers_non_null, "%s: %s must not be null", what, pointer_names);
+  CUROBO_REQUIRE(((uintptr_t)block_data & 3) == 0, "%s: block_data must be 4-byte aligned", what);
   return CUROBO_HIP_OK;
 }
 

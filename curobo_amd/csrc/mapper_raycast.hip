@@ -5,11 +5,11 @@
 //
 // Reference: perception/mapper/kernel/builder/builder_raycast.py (refine_hit_bisection :381-422, ray_block_exit_t :424-461,
 // raycast_block_sparse_kernel :467-573, raycast_block_sparse_accelerated_kernel :690-834) and
-// kernel/wp_raycast_pose_refine.py (_ray_sdf_alignment_block_sparse_tiled_kernel :100-316).  The samplers are
-// mapper_device.hpp's.  The reference asks its hash table whether a block is allocated; here that is the byte block_mask, and
-// a block outside the grid is not allocated.
+// kernel/wp_raycast_pose_refine.py (_ray_sdf_alignment_block_sparse_tiled_kernel :100-316).  The grid's addressing, the samplers
+// (under the sample rule, tsdf_voxel), the camera and the pixel's ray are mapper_device.hpp's.  The reference asks its hash table
+// whether a block is allocated; here that is the byte block_mask, and a block outside the grid is not allocated.
 //
-// Range of the casts: mesh_trilinear turns floor(v - 0.5) of the continuous voxel coordinate v into an int.  Both launches
+// Range of the casts: tsdf_trilinear turns floor(v - 0.5) of the continuous voxel coordinate v into an int.  Both launches
 // compare v with the padded grid's extent in float first (ray_sample, ray_gradient): a position further out than one voxel
 // (three for the gradient) has no valid corner, so the answer is known without the cast.  The accelerated march keeps the
 // block coordinate floor(v / block_size) in float and converts it only once it lies inside the grid.
@@ -30,15 +30,15 @@ struct RayMap {
 };
 
 __device__ __forceinline__ bool ray_within(const MapGrid &g, f3 p, float margin) {
-  const f3 v = mesh_continuous(g, p);
+  const f3 v = grid_continuous(g, p);
   return v.x >= -margin && v.x < (float)(g.nbx * g.bs) + margin && v.y >= -margin && v.y < (float)(g.nby * g.bs) + margin &&
          v.z >= -margin && v.z < (float)(g.nbz * g.bs) + margin;  // (false for a coordinate that is not a number)
 }
 __device__ __forceinline__ float ray_sample(const RayMap &m, f3 p) {
-  return ray_within(m.g, p, 1.0f) ? mesh_trilinear(m.block_data, m.block_mask, m.g, p) : kSdfInvalid;
+  return ray_within(m.g, p, 1.0f) ? tsdf_trilinear(m.block_data, m.block_mask, m.g, p) : kSdfInvalid;
 }
 __device__ __forceinline__ f3 ray_gradient(const RayMap &m, f3 p) {
-  return ray_within(m.g, p, 3.0f) ? mesh_gradient<true>(m.block_data, m.block_mask, m.g, p) : make_f3(0.0f, 0.0f, 1.0f);
+  return ray_within(m.g, p, 3.0f) ? tsdf_gradient<true>(m.block_data, m.block_mask, m.g, p) : make_f3(0.0f, 0.0f, 1.0f);
 }
 
 __device__ __forceinline__ bool pose_is_finite(const float *position, const float *quaternion) {
@@ -53,7 +53,7 @@ __device__ __forceinline__ float ray_refine_hit(const RayMap &m, f3 cam, f3 ray,
   float t_mid = t_lo + sdf_lo * (t_hi - t_lo) / denom;
   for (int it = 0; it < kHitRefineIterations; it++) {
     const float sdf_mid = ray_sample(m, cam + t_mid * ray);
-    if (sdf_mid > 1e9f) break;
+    if (sdf_is_invalid(sdf_mid)) break;
     if (fabsf(sdf_mid) < 1e-6f) break;
     if (sdf_mid > 0.0f) t_lo = t_mid, sdf_lo = sdf_mid;
     else t_hi = t_mid, sdf_hi = sdf_mid;
@@ -65,10 +65,8 @@ __device__ __forceinline__ float ray_refine_hit(const RayMap &m, f3 cam, f3 ray,
 
 // ray_block_exit_t (:424-461) for the block whose coordinate is b (whole numbers held as floats); wp.sign(0) is +1
 __device__ __forceinline__ float ray_block_exit(const MapGrid &g, f3 o, f3 d, f3 b) {
-  const float bs = (float)g.bs;
-  const f3 half = make_f3((float)g.grid_w * 0.5f, (float)g.grid_h * 0.5f, (float)g.grid_d * 0.5f);
-  const f3 lo = make_f3((b.x * bs - half.x) * g.vs + g.ox, (b.y * bs - half.y) * g.vs + g.oy, (b.z * bs - half.z) * g.vs + g.oz);
-  const f3 hi = make_f3((b.x * bs + bs - half.x) * g.vs + g.ox, (b.y * bs + bs - half.y) * g.vs + g.oy, (b.z * bs + bs - half.z) * g.vs + g.oz);
+  const f3 lo = make_f3(grid_face<false>(g, b.x, g.grid_w, g.ox), grid_face<false>(g, b.y, g.grid_h, g.oy), grid_face<false>(g, b.z, g.grid_d, g.oz));
+  const f3 hi = make_f3(grid_face<true>(g, b.x, g.grid_w, g.ox), grid_face<true>(g, b.y, g.grid_h, g.oy), grid_face<true>(g, b.z, g.grid_d, g.oz));
   const float ix = fabsf(d.x) > 1e-8f ? 1.0f / d.x : (d.x < 0.0f ? -1e10f : 1e10f);
   const float iy = fabsf(d.y) > 1e-8f ? 1.0f / d.y : (d.y < 0.0f ? -1e10f : 1e10f);
   const float iz = fabsf(d.z) > 1e-8f ? 1.0f / d.z : (d.z < 0.0f ? -1e10f : 1e10f);
@@ -93,15 +91,15 @@ __global__ __launch_bounds__(kRayThreads) void mapper_raycast_kernel(RaycastArgs
   if (px >= a.width || py >= a.height) return;
   const size_t pixel = (size_t)py * a.width + px;
   const MapGrid &g = a.m.g;
-  const float fx = a.intrinsics[0], fy = a.intrinsics[4], cx = a.intrinsics[2], cy = a.intrinsics[5];
-  const f3 cam = make_f3(a.position[0], a.position[1], a.position[2]);
-  const float rx = ((float)px + 0.5f - cx) / fx, ry = ((float)py + 0.5f - cy) / fy;
-  const float ray_len = sqrtf(rx * rx + ry * ry + 1.0f);
-  const f3 ray_cam = make_f3(rx / ray_len, ry / ray_len, 1.0f / ray_len);
-  const f3 ray = quat_rotate(a.quaternion[0], make_f3(a.quaternion[1], a.quaternion[2], a.quaternion[3]), ray_cam);
+  const MapCamera camera = read_camera(a.intrinsics, a.position, a.quaternion, 0);
+  const f3 cam = camera.t;
+  const f3 r = pixel_ray<true>(camera, px, py);
+  const float ray_len = sqrtf(r.x * r.x + r.y * r.y + 1.0f);
+  const f3 ray_cam = make_f3(r.x / ray_len, r.y / ray_len, 1.0f / ray_len);
+  const f3 ray = quat_rotate(camera.qw, camera.qv, ray_cam);
   const float step = g.vs * 0.5f;  // MIN_STEP_SCALE
 
-  float t = a.t_min, prev_sdf = 1e10f, prev_t = a.t_min, hit_t = 0.0f;
+  float t = a.t_min, prev_sdf = kSdfInvalid, prev_t = a.t_min, hit_t = 0.0f;
   bool hit = false;
   f3 cur = make_f3(-999999.0f, -999999.0f, -999999.0f);
   bool allocated = false;
@@ -111,7 +109,7 @@ __global__ __launch_bounds__(kRayThreads) void mapper_raycast_kernel(RaycastArgs
     if (!(t <= a.t_max)) break;  // (also ends a march whose t is no number any more)
     const f3 pos = cam + t * ray;
     if (ACCEL) {
-      const f3 v = mesh_continuous(g, pos);
+      const f3 v = grid_continuous(g, pos);
       const float bs = (float)g.bs;
       const f3 b = make_f3(floorf(v.x / bs), floorf(v.y / bs), floorf(v.z / bs));  // world_to_block_coords
       if (b.x != cur.x || b.y != cur.y || b.z != cur.z) {
@@ -123,16 +121,16 @@ __global__ __launch_bounds__(kRayThreads) void mapper_raycast_kernel(RaycastArgs
       }
       if (!allocated) {
         t = exit_t + step;
-        prev_sdf = 1e10f;
+        prev_sdf = kSdfInvalid;
         continue;
       }
     }
     const float sdf = ray_sample(a.m, pos);
-    if (sdf > 1e9f) {
+    if (sdf_is_invalid(sdf)) {
       t += step;
       continue;
     }
-    if (prev_sdf < 1e9f && prev_sdf > 0.0f && sdf < 0.0f) {
+    if (prev_sdf < kSdfValidBelow && prev_sdf > 0.0f && sdf < 0.0f) {  // (false for a prev_sdf that is not a number)
       hit_t = ray_refine_hit(a.m, cam, ray, prev_t, t, prev_sdf, sdf);
       hit = true;
       break;
@@ -177,21 +175,19 @@ __global__ __launch_bounds__(kAlignThreads) void mapper_ray_align_kernel(AlignAr
     if (pi < a.height && pj < a.width) {
       const float d = a.depth[(size_t)pi * a.width + pj];
       if (d >= a.depth_min && d <= a.depth_max && isfinite(d)) {
-        const f3 cam = make_f3(a.position[0], a.position[1], a.position[2]);
-        const float fx = a.intrinsics[0], fy = a.intrinsics[4], cx = a.intrinsics[2], cy = a.intrinsics[5];
-        const float rx = ((float)pj - cx) / fx, ry = ((float)pi - cy) / fy;  // (no half pixel: :171-172)
-        const float ray_len = sqrtf(rx * rx + ry * ry + 1.0f);
-        const f3 ray = quat_rotate(a.quaternion[0], make_f3(a.quaternion[1], a.quaternion[2], a.quaternion[3]),
-                                   make_f3(rx / ray_len, ry / ray_len, 1.0f / ray_len));
+        const MapCamera camera = read_camera(a.intrinsics, a.position, a.quaternion, 0);
+        const f3 d1 = pixel_ray<false>(camera, pj, pi);  // (no half pixel: :171-172)
+        const float ray_len = sqrtf(d1.x * d1.x + d1.y * d1.y + 1.0f);
+        const f3 ray = quat_rotate(camera.qw, camera.qv, make_f3(d1.x / ray_len, d1.y / ray_len, 1.0f / ray_len));
         const float obs_t = d * ray_len;
-        const float sdf_k0 = ray_sample(a.m, cam + obs_t * ray);
-        if (!(sdf_k0 > 1e9f) && fabsf(sdf_k0) <= a.distance_threshold) {
+        const float sdf_k0 = ray_sample(a.m, camera.t + obs_t * ray);
+        if (sdf_is_valid(sdf_k0) && fabsf(sdf_k0) <= a.distance_threshold) {
           const float sample_t = obs_t + (float)k * g.vs;
           if (sample_t >= 0.1f) {
-            const f3 p = cam + sample_t * ray;
+            const f3 p = camera.t + sample_t * ray;
             const float sdf = ray_sample(a.m, p);
             const float expected = (float)(-k) * g.vs;
-            if (!(sdf > 1e9f) && fabsf(expected) <= g.trunc) {
+            if (sdf_is_valid(sdf) && fabsf(expected) <= g.trunc) {
               r = sdf - expected;
               const float abs_r = fabsf(r), huber_delta = 0.05f * (sample_t * sample_t);
               float hs = 1.0f;
@@ -239,8 +235,7 @@ using namespace curobo_hip;
 static int read_ray_map(RayMap *m, const void *block_data, const uint8_t *block_mask, const curobo_hip_mapper_params *params,
                         float minimum_tsdf_weight, const char *what) {
   if (int rc = read_params(params, &m->g, what)) return rc;
-  CUROBO_REQUIRE(block_data && block_mask, "%s: block_data and block_mask must not be null", what);
-  CUROBO_REQUIRE(((uintptr_t)block_data & 3) == 0, "%s: block_data must be 4-byte aligned", what);
+  if (int rc = check_map(block_data && block_mask, block_data, "block_data and block_mask", what)) return rc;
   CUROBO_REQUIRE(minimum_tsdf_weight >= 0.0f, "%s: minimum_tsdf_weight must not be negative, got %g", what, (double)minimum_tsdf_weight);
   m->block_data = (const uint32_t *)block_data, m->block_mask = block_mask;
   m->g.min_weight = minimum_tsdf_weight;

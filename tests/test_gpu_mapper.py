@@ -146,6 +146,74 @@ def test_esdf_stages_on_injected_states(grid, device, empty):
     assert R.half_steps(dist, ref["distance"]).max() <= 1
 
 
+OVERHANG_ESDF_SHAPE = (10, 10, 10)
+OVERHANG_ESDF_ORIGIN = (-0.005, -0.005, -0.005)
+
+
+def _overhanging_state(seed=5):
+    """(grid, sw, w, visible): 8^3 voxels of 0.02 m in blocks of 4 about the origin, minimum weight 0.5, every block visible, the
+    voxels drawn as ``_inject`` draws them except that the low-weight kind carries weight EXACTLY the minimum (and sdf 0: a seed
+    if it were read)"""
+    vs, tr = float(np.float32(0.02)), float(np.float32(0.08))
+    g = R.Grid(8, 8, 8, 4, [0.0, 0.0, 0.0], vs, tr, 0.1, 5.0, 0.5)
+    rng = np.random.default_rng(seed)
+    n, v = g.n_blocks, g.bs ** 3
+    kind = rng.integers(0, 6, (n, v))
+    lo = np.select([kind == 2, kind == 3, kind == 4, kind == 5], [-0.5 * vs, 1.3 * vs, -tr, -(tr - 1.5 * vs)], 0.0)
+    hi = np.select([kind == 2, kind == 3, kind == 4, kind == 5], [0.5 * vs, tr, -(tr - 0.8 * vs), -1.3 * vs], 0.0)
+    sdf = lo + (hi - lo) * rng.random((n, v))
+    w = np.select([kind == 0, kind == 1], [0.0, 0.5], rng.integers(1, 40, (n, v)) * 0.5).astype(np.float16)
+    sw = (sdf * w.astype(np.float64)).astype(np.float16)
+    return g, sw, w, np.ones(n, bool)
+
+
+def _overhanging_device(g, sw, w, visible, device):
+    from curobo_amd.backends import mapper as B
+
+    p = B.make_params((g.nz, g.ny, g.nx), g.bs, g.origin, g.vs, g.trunc, g.depth_min, g.depth_max, g.min_weight)
+    data = torch.as_tensor(np.stack([sw, w], -1), device=device)
+    mask = torch.zeros(B.mask_bytes(p), dtype=torch.uint8, device=device)
+    mask[: g.n_blocks] = torch.as_tensor(visible.astype(np.uint8), device=device)
+    return p, data, mask
+
+
+def test_esdf_probe_rule_outside_the_grid_and_at_the_minimum_weight(device):
+    """The two things the ESDF path's voxel read does otherwise than the mesh and the renderer's, where they show: the ESDF grid
+    overhangs the TSDF grid by a cell on every side, its lowest centres at continuous voxel coordinate -0.75, which the cast
+    toward zero puts in voxel 0 (floor: outside, builder_esdf.py:279-282); and a sixth of the voxels weigh exactly the minimum,
+    which ``>`` leaves unobserved (wp_tsdf_sample.py:49; ``>=`` would seed at each: their sdf is 0).  Measured on the oracle for
+    this draw of the state (seed 5, drawn as ``_overhanging_state`` does): 640 of the 1000 cells are seeds and 300 inside; floor changes 172 seed cells, ``>=`` 164 and 97 occupied flags."""
+    from curobo_amd.backends import mapper as B
+
+    g, sw, w, visible = _overhanging_state()
+    shape, origin = OVERHANG_ESDF_SHAPE, OVERHANG_ESDF_ORIGIN
+    lowest = (R.esdf_centres(shape, origin, g.vs)[0, 0, 0] - np.asarray(g.origin)) / g.vs + 0.5 * g.nx
+    assert np.allclose(lowest, -0.75, atol=1e-6) and (w == np.float16(g.min_weight)).sum() > 50
+    ref = R.esdf(g, sw, w, visible, shape, origin, g.vs)
+    assert not ref["ambiguous"].any(), "the injected state and the ESDF origin keep every probe and sdf off the thresholds"
+    p, data, mask = _overhanging_device(g, sw, w, visible, device)
+    n = int(np.prod(shape))
+    o, vs = torch.tensor(origin, device=device), torch.tensor([g.vs], dtype=torch.float32, device=device)
+    sites = torch.empty(n, dtype=torch.int32, device=device)
+    B.mapper_esdf_seed(sites, data, mask, o, vs, p, shape)
+    got = sites.cpu().numpy().reshape(shape)
+    assert np.array_equal(got >= 0, ref["seed"])
+    own = R.pack_sites(np.stack(np.meshgrid(*[np.arange(k) for k in shape], indexing="ij"), -1))
+    assert np.array_equal(got[got >= 0], own[got >= 0]) and (got[got < 0] == -1).all()
+    nearest = B.mapper_edt(sites, torch.empty_like(sites), shape)
+    out = torch.zeros(n, dtype=torch.float16, device=device)
+    B.mapper_esdf_distance(out, nearest, data, mask, o, vs, p, shape)
+    dist = out.cpu().numpy().reshape(shape)
+    assert 200 < ref["seed"].sum() < ref["seed"].size and ref["inside"].sum() > 100 and (~ref["inside"]).sum() > 100
+    assert np.array_equal(np.signbit(dist), ref["inside"]), "negative exactly where the TSDF at the cell's centre is observed and < 0"
+    assert R.half_steps(dist, ref["distance"]).max() <= 1
+    for kw in (dict(), dict(surface_only=True)):
+        flags = torch.full((g.n_blocks * g.bs ** 3,), 7, dtype=torch.uint8, device=device)
+        B.mapper_occupied_flags(flags, data, mask, p, kw.get("surface_only", False), g.vs)
+        want = R.occupied(g, sw, w, visible, **kw)
+        assert want.sum() > 50 and np.array_equal(flags.cpu().numpy().reshape(want.shape) != 0, want)
+
+
 # ---------------------------------------------------------------------------------------------------- 4: the nearest-site transform
 def _site_sets(shape, rng):
     cells = int(np.prod(shape))
