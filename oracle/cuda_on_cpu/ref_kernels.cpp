@@ -306,7 +306,7 @@ static int full_block_size(int B) {
 }
 
 // rnea_forward_kernel<N_LINKS, N_DOF, 1, false> / rnea_backward_kernel<N_LINKS, N_DOF, 1, false> (one thread per element; the
-// link and dof counts are template parameters there: franka 13 / 7 and unitree_g1 56 / 49 are instantiated);
+// link and dof counts are template parameters there: franka 13 / 7, unitree_g1 56 / 49 and the joint zoo of tests/joint_zoo.py, 10 / 6, are instantiated);
 // cuda_core_backend/dynamics.py:24-260.  forward_cache is the reference's own [batch, links * 20] scratch.
 template <int L, int D>
 static int rnea_fwd(float *tau, const float *q, const float *qd, const float *qdd, const float *fixed, const float *masses,
@@ -331,12 +331,17 @@ static int rnea_bwd(float *gq, float *gqd, float *gqdd, const float *gtau, const
   });
   return 0;
 }
+// whether the two entry points below serve a robot of these sizes (a library built before a size was added lacks this symbol)
+extern "C" int ref_rnea_instantiated(int num_links, int num_dof) {
+  return (num_links == 13 && num_dof == 7) || (num_links == 56 && num_dof == 49) || (num_links == 10 && num_dof == 6);
+}
 extern "C" int ref_rnea_forward(float *tau, const float *q, const float *qd, const float *qdd, const float *fixed, const float *masses,
                                 const float *inertias, const int8_t *jtype, const int16_t *jmap, const int16_t *lmap, const float *joff,
                                 const float *gravity, const int16_t *level_starts, const int16_t *level_links, float *cache, int B,
                                 int n_levels, int num_links, int num_dof) {
   if (num_links == 13 && num_dof == 7) return rnea_fwd<13, 7>(tau, q, qd, qdd, fixed, masses, inertias, jtype, jmap, lmap, joff, gravity, level_starts, level_links, cache, B, n_levels);
   if (num_links == 56 && num_dof == 49) return rnea_fwd<56, 49>(tau, q, qd, qdd, fixed, masses, inertias, jtype, jmap, lmap, joff, gravity, level_starts, level_links, cache, B, n_levels);
+  if (num_links == 10 && num_dof == 6) return rnea_fwd<10, 6>(tau, q, qd, qdd, fixed, masses, inertias, jtype, jmap, lmap, joff, gravity, level_starts, level_links, cache, B, n_levels);
   return 1;
 }
 extern "C" int ref_rnea_backward(float *gq, float *gqd, float *gqdd, const float *gtau, const float *q, const float *qd, const float *fixed,
@@ -345,6 +350,7 @@ extern "C" int ref_rnea_backward(float *gq, float *gqd, float *gqdd, const float
                                  const float *cache, int B, int n_levels, int num_links, int num_dof) {
   if (num_links == 13 && num_dof == 7) return rnea_bwd<13, 7>(gq, gqd, gqdd, gtau, q, qd, fixed, masses, inertias, jtype, jmap, lmap, joff, gravity, level_starts, level_links, cache, B, n_levels);
   if (num_links == 56 && num_dof == 49) return rnea_bwd<56, 49>(gq, gqd, gqdd, gtau, q, qd, fixed, masses, inertias, jtype, jmap, lmap, joff, gravity, level_starts, level_links, cache, B, n_levels);
+  if (num_links == 10 && num_dof == 6) return rnea_bwd<10, 6>(gq, gqd, gqdd, gtau, q, qd, fixed, masses, inertias, jtype, jmap, lmap, joff, gravity, level_starts, level_links, cache, B, n_levels);
   return 1;
 }
 

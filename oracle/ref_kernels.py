@@ -14,7 +14,7 @@ g++, over a CUDA-on-CPU shim: a CUDA block is a group of cooperatively scheduled
     position_clique_loop_idx_fwd_kernel / _bwd_kernel, acceleration_loop_idx_kernel / _rk2_kernel
                                                             (kernels/trajectory/legacy/*.cuh)
     kernel_line_search                                      (kernels/optimization/line_search/*.cuh)
-    rnea_forward_kernel, rnea_backward_kernel               (kernels/dynamics/*.cuh; franka and unitree_g1 instantiations)
+    rnea_forward_kernel, rnea_backward_kernel               (kernels/dynamics/*.cuh; franka, unitree_g1 and joint-zoo instantiations)
 
 The methods mirror ``oracle.Oracle`` (same arguments, same result dictionaries) so that a test can put the two side by
 side.  ``available()`` is False where the library was not built (no reference checkout and no prebuilt copy).
@@ -32,6 +32,15 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_ref", "lib
 
 def available() -> bool:
     return os.path.exists(LIB_PATH)
+
+
+def rnea_instantiated(num_links: int, num_dof: int) -> bool:
+    """whether the library is there AND its RNEA entry points serve these sizes (a copy built from older sources that cannot be
+    rebuilt, for want of the reference checkout, may not)"""
+    if not available():
+        return False
+    lib = C.CDLL(LIB_PATH)
+    return hasattr(lib, "ref_rnea_instantiated") and bool(lib.ref_rnea_instantiated(int(num_links), int(num_dof)))
 
 
 def _p(a):
@@ -280,7 +289,8 @@ class ReferenceKernels:
                                        _p(t["jmap"]), _p(t["lmap"]), _p(t["joff"]), _p(_f32(gravity)), _p(t["starts"]), _p(t["links"]),
                                        _p(cache), b, len(t["starts"]) - 1, L, dof)
         if rc != 0:
-            raise ValueError(f"rnea kernels are instantiated for franka (13 links / 7 dof) and unitree_g1 (56 / 49), not {L} / {dof}")
+            raise ValueError(f"rnea kernels are instantiated for franka (13 links / 7 dof), unitree_g1 (56 / 49) and the joint zoo "
+                             f"(10 / 6), not {L} / {dof}")
         return tau, cache
 
     def rnea_backward(self, grad_tau, q, qd, cache, model, gravity=(0, 0, 0, 0, 0, 9.81)):
@@ -293,5 +303,5 @@ class ReferenceKernels:
                                         _p(t["inertias"]), _p(t["jtype"]), _p(t["jmap"]), _p(t["lmap"]), _p(t["joff"]), _p(_f32(gravity)),
                                         _p(t["starts"]), _p(t["links"]), _p(_f32(cache)), b, len(t["starts"]) - 1, L, dof)
         if rc != 0:
-            raise ValueError(f"rnea kernels are instantiated for franka and unitree_g1, not {L} / {dof}")
+            raise ValueError(f"rnea kernels are instantiated for franka, unitree_g1 and the joint zoo, not {L} / {dof}")
         return tuple(g)

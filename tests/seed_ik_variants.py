@@ -13,6 +13,10 @@ fewer dofs, land in ``<0,0>``.
     C     franka + panda_link6                     7, 2   <0,0>           46 656 B
     D     ur10e + wrist_1_link, wrist_3_link       6, 3   <0,0>           43 136 B
     E     franka, panda_joint5 / _joint7 locked    5, 1   <0,0>, D < 6    smaller than A
+    F     the joint zoo (tests/joint_zoo.py)       6, 4   <0,0>           fits (asserted)
+
+F is no packaged robot: prismatic joints behind revolute ones, multipliers outside {+-1}, biases and two dofs with two links
+each (the ``atomicAdd`` Jacobian columns of the launch).
 """
 
 import dataclasses
@@ -93,16 +97,23 @@ def with_locked_joints(model, joint_indices):
         lock_joints={**model.lock_joints, **{model.joint_names[j]: 0.0 for j in drop}})
 
 
-#: case -> (packaged robot, extra tool-frame links, locked joints, D, T, instantiation)
+def _joint_zoo():
+    import joint_zoo
+
+    return joint_zoo.model()
+
+
+#: case -> (packaged robot or a model factory, extra tool-frame links, locked joints, D, T, instantiation)
 CASES = {
     "A": ("franka", (), (), 7, 1, "<7,1>"),
     "B": ("ur10e", (), (), 6, 1, "<6,1>"),
     "C": ("franka", (6,), (), 7, 2, "<0,0>"),          # + panda_link6
     "D": ("ur10e", (5, 7), (), 6, 3, "<0,0>"),          # + wrist_1_link, wrist_3_link
     "E": ("franka", (), (4, 6), 5, 1, "<0,0>"),         # panda_joint5 and panda_joint7 locked: D < 6
+    "F": (_joint_zoo, (), (), 6, 4, "<0,0>"),           # no packaged robot: every joint type, mimic links, biases
 }
 #: seed of the problem's random draws per case (a case whose knife-edge share exceeded the cap would get another seed here)
-PROBLEM_SEED = {"A": 0, "B": 0, "C": 0, "D": 0, "E": 0}
+PROBLEM_SEED = {"A": 0, "B": 0, "C": 0, "D": 0, "E": 0, "F": 0}
 
 
 @functools.lru_cache(maxsize=None)
@@ -115,7 +126,7 @@ def packaged(name):
 @functools.lru_cache(maxsize=None)
 def case_model(case):
     name, frames, locked, D, T, _ = CASES[case]
-    m = packaged(name)
+    m = name() if callable(name) else packaged(name)
     if frames:
         m = with_tool_frames(m, frames)
     if locked:
@@ -213,6 +224,7 @@ MEASURED = {
     "C": {1: (1.6e-6, 7.4e-7), 2: (3.6e-6, 3.6e-6), 4: (2.2e-5, 4.8e-6)},
     "D": {1: (2.1e-6, 1.7e-6), 2: (5.8e-6, 2.5e-6), 4: (7.8e-6, 4.6e-6)},
     "E": {1: (7.1e-7, 6.1e-7), 2: (3.1e-6, 1.5e-6), 4: (3.4e-6, 1.4e-6)},
+    "F": {1: (2.3e-6, 2.2e-6), 2: (2.9e-6, 3.5e-6), 4: (1.7e-6, 2.0e-6)},
 }
 SENSITIVITY_FACTOR = 8.0
 

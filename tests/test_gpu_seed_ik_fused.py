@@ -10,6 +10,8 @@ Cases (tests/seed_ik_variants.py; n = 13 problems x 7 seeds = 91 rows: the last 
     C     franka + panda_link6                     7, 2   <0,0>   run-time sizes, row-distributed Cholesky, broadcast solves
     D     ur10e + wrist_1_link, wrist_3_link       6, 3   <0,0>
     E     franka, panda_joint5 / _joint7 locked    5, 1   <0,0>   D < 6
+    F     the joint zoo (tests/joint_zoo.py)       6, 4   <0,0>   prismatic joints behind revolute ones, multipliers outside
+                                                                  {+-1}, biases, two dofs with two links (atomicAdd columns)
 
 Bounds.  k = 0 (the initial evaluation): those the launch sequence meets in tests/test_gpu_seed_ik.py.  k >= 1: the accept
 decision is a threshold, so rows whose trust ratio comes within 1e-3 (1 + |rho|) of ``rho_min`` in the oracle's run are left out
@@ -25,11 +27,12 @@ between the fp32 oracle and the same iteration with the LM solve in float64, mea
     C                1.6e-6   3.6e-6   2.2e-5             7.4e-7   3.6e-6   4.8e-6
     D                2.1e-6   5.8e-6   7.8e-6             1.7e-6   2.5e-6   4.6e-6
     E                7.1e-7   3.1e-6   3.4e-6             6.1e-7   1.5e-6   1.4e-6
+    F                2.3e-6   2.9e-6   1.7e-6             2.2e-6   3.5e-6   2.0e-6
 
 (joint positions of those two CPU runs differ by at most 6.0e-6, 1.1e-5 and 2.3e-5 after 1, 2 and 4 iterations; their decisions
 and dampings are identical.)
 
-Out of scope: prismatic joints and D in 8..16 -- no packaged robot that fits the launch's LDS has them.
+Out of scope: D in 8..16 -- no robot here that fits the launch's LDS has them.
 """
 
 import functools
@@ -132,6 +135,18 @@ def test_fused_iterations_match_oracle_per_seed(oracle, device, case, k):
         assert acc.any() and (~acc).any()
         assert (ref["jacobian"][:, 6 * x["md"]["tool_frame_map"].shape[0]:] != 0).any(axis=(1, 2)).mean() > 0.1
     _compare(_launch(device, case, x, k), ref, x, case, k)
+
+
+@pytest.mark.parametrize("k", [0, 1, 2, 4])
+def test_five_launch_sequence_matches_oracle_on_the_joint_zoo(oracle, device, k):
+    """case F through the five-launch iteration (LM step, FK with Jacobian from kinematics.hip, tool-pose distance, FK VJP,
+    state update): the same oracle run, the same bounds as the one-launch iteration"""
+    x = V.inputs("F")
+    s = _solver(device, "F", x)
+    s._evaluate_candidate(torch.as_tensor(np.array(x["seeds"]), device=device), initial=True)
+    for _ in range(k):
+        s._lm_iteration()
+    _compare(_state(s), V.reference("F", k), x, "F", k)
 
 
 @pytest.mark.parametrize("case", list(V.CASES))

@@ -201,7 +201,7 @@ def test_velocity_acceleration_block_matches_reference_golden():
         np.testing.assert_allclose(d2, want_d2, rtol=5e-5)
 
 
-@pytest.mark.parametrize("case", ["A", "B", "C", "D", "E"])
+@pytest.mark.parametrize("case", ["A", "B", "C", "D", "E", "F"])
 def test_fused_test_inputs_stay_off_the_knife_edge(oracle, case):
     """conditions on the inputs of tests/test_gpu_seed_ik_fused.py, checked on the oracle alone: at most 2 % of the rows
     come within 1e-3 (1 + |rho|) of the accept threshold (every case, option and iteration count used there), goal sets keep
