@@ -28,6 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ("fuzz_perception.py", ["24", "5"], ", 0 failed"),
     ("fuzz_graph.py", ["12", "5"], ", 0 failed"),  # (new rows go last: the ids above carry their position)
     ("fuzz_voxel.py", ["24", "5"], ", 0 failed"),
+    ("fuzz_lbfgs_iteration.py", ["24", "5"], ", 0 failed"),
 ])
 def test_randomised_sweep(script, args, ok):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "randomised", script), *args], capture_output=True, text=True, timeout=600,
