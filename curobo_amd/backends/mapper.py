@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import ctypes as _C
 import math
-from typing import Sequence
+from typing import Optional, Sequence
 
 import torch
 
@@ -166,6 +166,45 @@ def mapper_occupied_flags(flags: torch.Tensor, block_data: torch.Tensor, block_m
         raise ValueError(f"{what}: flags must hold {params.n_blocks * params.block_voxels} voxels, got {flags.numel()}")
     check(load().curobo_hip_mapper_occupied_flags(ptr(flags), ptr(block_data), ptr(block_mask), _C.addressof(params), int(bool(surface_only)),
                                                   float(sdf_threshold), current_stream(flags)))
+
+
+REFERENCE_BLOCK_SIZE = 8  #: the block size the recycle threshold was calibrated at (reference constants.py:55)
+
+
+def decay_empty_threshold(block_size: int) -> float:
+    """the weight sum below which a block is recycled: 0.01 at blocks of 8, scaled by the voxels of a block
+    (builder_decay.py:69, :103-105), as the float32 the launch compares with"""
+    return float(torch.tensor(0.01 * float(int(block_size) ** 3) / float(REFERENCE_BLOCK_SIZE ** 3), dtype=torch.float32).item())
+
+
+def mapper_decay(block_data: torch.Tensor, block_mask: torch.Tensor, recycled: torch.Tensor, params: MapperParams, factor_outside: float,
+                 factor_inside: float, empty_threshold: float, intrinsics: Optional[torch.Tensor] = None,
+                 cam_position: Optional[torch.Tensor] = None, cam_quaternion: Optional[torch.Tensor] = None,
+                 image_shape: Sequence[int] = (0, 0)) -> None:
+    """``curobo_hip_mapper_decay``: every ever-visible block times ``factor_inside`` where it lies in the union of the cameras'
+    frusta (``intrinsics`` [n, 3, 3], ``cam_position`` [n, 3], ``cam_quaternion`` [n, 4] wxyz, ``image_shape`` (H, W), the depth
+    range of ``params``), else times ``factor_outside``; without cameras ``factor_outside`` throughout.  A block whose weights then
+    sum to less than ``empty_threshold`` is zeroed and leaves ``block_mask``; ``recycled`` uint8 [n_blocks]: 1 for those, else 0."""
+    what = "mapper_decay"
+    _require_map(params, what, block_data, like=block_data, block_mask=block_mask, recycled=recycled)
+    for name, f in (("factor_outside", factor_outside), ("factor_inside", factor_inside)):
+        if not 0.0 <= float(f) <= 1.0:
+            raise ValueError(f"{what}: {name} must lie in [0, 1], got {f}")
+    cameras = (intrinsics, cam_position, cam_quaternion)
+    n, h, w = 0, 0, 0
+    if any(t is not None for t in cameras):
+        if any(t is None for t in cameras):
+            raise ValueError(f"{what}: intrinsics, cam_position and cam_quaternion come together")
+        n, (h, w) = int(intrinsics.shape[0]), (int(v) for v in image_shape)
+        for name, t, shape in (("intrinsics", intrinsics, (n, 3, 3)), ("cam_position", cam_position, (n, 3)), ("cam_quaternion", cam_quaternion, (n, 4))):
+            _require(t, name, torch.float32, block_data)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{what}: {name} must have shape {shape}, got {tuple(t.shape)}")
+        if n <= 0 or h <= 0 or w <= 0:
+            raise ValueError(f"{what}: need at least one camera and a positive image_shape, got {n} cameras and {(h, w)}")
+    check(load().curobo_hip_mapper_decay(ptr(block_data), ptr(block_mask), ptr(recycled), ptr(intrinsics), ptr(cam_position), ptr(cam_quaternion),
+                                         n, h, w, float(factor_outside), float(factor_inside), float(empty_threshold), _C.addressof(params),
+                                         current_stream(block_data)))
 
 
 def _require_mesh(params: MapperParams, what: str, block_list: torch.Tensor, **per_voxel) -> int:

@@ -7,6 +7,8 @@
 //   curobo_hip_mapper_edt_pass        one pass of the separable exact nearest-site transform, the lines of a tile in LDS
 //   curobo_hip_mapper_esdf_distance   site -> signed fp16 distance
 //   curobo_hip_mapper_occupied_flags  the rule of extract_occupied_voxels per voxel
+//   curobo_hip_mapper_decay           per ever-visible block: its words times the block's factor, the weights summed, the block
+//                                     recycled (words and mask byte to 0) where the sum is below the threshold
 //   curobo_hip_mapper_mesh_classify   extract_mesh, per (visible block, tile): corner values in LDS, the cubes' cases and counts
 //   curobo_hip_mapper_mesh_vertices   ... per voxel: the vertices of its own cut edges, refined, with normals
 //   curobo_hip_mapper_mesh_triangles  ... per voxel: the table's triangles through the edges' owner cubes, and which of them stay
@@ -206,6 +208,90 @@ __global__ __launch_bounds__(kMapThreads) void mapper_occupied_kernel(uint8_t *f
     if (sdf_is_valid(sdf)) flag = surface_only ? (fabsf(sdf) < sdf_threshold) : (sdf <= 0.0f);
   }
   flags[i] = flag;
+}
+
+// ---------------------------------------------------------------------------------------------------- decay and recycling
+// Per ever-visible block: both words of every voxel times the block's factor (factor_inside where the block lies in the union of
+// the cameras' frusta, else factor_outside), the stored weights summed, and the block recycled -- words and mask byte to 0 -- where
+// the sum is below empty_threshold (wp_decay.py:111-149, builder_decay.py:322-363).  recycled[b] says what this launch did.
+struct DecayArgs {
+  uint32_t *block_data;
+  uint8_t *block_mask, *recycled;
+  const float *intrinsics, *position, *quaternion;
+  int n_cameras, height, width;
+  float factor_outside, factor_inside, empty_threshold;
+};
+
+// mark_blocks_in_frustum_kernel (builder_decay.py:111-215) for one block and every camera: the block's bounding sphere against the
+// depth range, then its projected disc against the image; the depth image is not read
+__device__ __forceinline__ bool block_in_frusta(const DecayArgs &a, const MapGrid &g, int b) {
+  const f3 centre = grid_block_centre(g, b);
+  const float r = 0.866f * ((float)g.bs * g.vs);
+  for (int cam = 0; cam < a.n_cameras; cam++) {
+    const MapCamera c = read_camera(a.intrinsics, a.position, a.quaternion, cam);
+    const f3 v = quat_rotate(c.qw, make_f3(-c.qv.x, -c.qv.y, -c.qv.z), centre - c.t);  // quat_inverse = the conjugate
+    const float z = v.z;
+    if (z + r < g.depth_min || z - r > g.depth_max) continue;
+    if (z < 0.01f) return true;
+    const float u = c.fx * v.x / z + c.cx, w = c.fy * v.y / z + c.cy;
+    const float ru = c.fx * r / z, rw = c.fy * r / z;
+    if (u + ru < 0.0f || u - ru > (float)a.width || w + rw < 0.0f || w - rw > (float)a.height) continue;
+    return true;
+  }
+  return false;
+}
+
+// Blocks of G = bs^3 <= 64 voxels: G consecutive lanes own a block, a word each, and 256 / G blocks share a workgroup (the blocks of
+// a wavefront are consecutive in memory: one 256-byte run).  The weights meet in a butterfly over the G lanes, whose pairs add
+// in a fixed order and commute, so every lane of the block holds the same sum and decides alike; each word is stored once.
+template <int G> __global__ __launch_bounds__(kMapThreads) void mapper_decay_lanes_kernel(DecayArgs a, MapGrid g, int n_blocks) {
+  const int64_t tid = (int64_t)blockIdx.x * kMapThreads + threadIdx.x;
+  const int64_t block = tid / G;
+  const int b = block < n_blocks ? (int)block : n_blocks - 1;  // (lanes past the end take part in the butterfly and store nothing)
+  const bool live = block < n_blocks && a.block_mask[b] != 0;
+  uint32_t word = 0u;
+  if (live) word = tsdf_pair_scale(a.block_data[tid], block_in_frusta(a, g, b) ? a.factor_inside : a.factor_outside);
+  const float sum = group_sum<G>(half_hi(word));
+  const bool recycle = live && sum < a.empty_threshold;
+  if (live) a.block_data[tid] = recycle ? 0u : word;
+  if (block < n_blocks && tid % G == 0) {
+    if (recycle) a.block_mask[b] = 0;
+    a.recycled[b] = recycle ? 1 : 0;
+  }
+}
+
+// Blocks of 512 voxels or more: a workgroup per block, at once back where the block was never visible; a lane owns 16-byte
+// runs of four voxels.  Lane sums in the order of the lane's runs, the wavefront's by the DPP ladder, the wavefronts' through
+// LDS in wavefront order.  The scaled words are stored before the sum is known; a recycled block's owners store zeros over them.
+__global__ __launch_bounds__(kMapThreads) void mapper_decay_block_kernel(DecayArgs a, MapGrid g) {
+  __shared__ float wave_total[kMapThreads / kWave];
+  const int b = blockIdx.x;
+  if (a.block_mask[b] == 0) {  // (uniform over the workgroup: the byte is written after the barrier below only)
+    if (threadIdx.x == 0) a.recycled[b] = 0;
+    return;
+  }
+  const float f = block_in_frusta(a, g, b) ? a.factor_inside : a.factor_outside;
+  const int runs = grid_block_voxels(g) / 4;  // a multiple of blockDim.x (the launcher's choice)
+  uint4 *data = reinterpret_cast<uint4 *>(a.block_data + (size_t)b * grid_block_voxels(g));
+  float sum = 0.0f;
+  for (int i = threadIdx.x; i < runs; i += blockDim.x) {
+    uint4 v = data[i];
+    v.x = tsdf_pair_scale(v.x, f), v.y = tsdf_pair_scale(v.y, f), v.z = tsdf_pair_scale(v.z, f), v.w = tsdf_pair_scale(v.w, f);
+    sum += (half_hi(v.x) + half_hi(v.y)) + (half_hi(v.z) + half_hi(v.w));
+    data[i] = v;
+  }
+  sum = wave_sum(sum);
+  if (threadIdx.x % kWave == 0) wave_total[threadIdx.x / kWave] = sum;
+  __syncthreads();
+  float total = wave_total[0];
+  for (int w = 1; w < (int)blockDim.x / kWave; w++) total += wave_total[w];
+  const bool recycle = total < a.empty_threshold;
+  if (recycle)
+    for (int i = threadIdx.x; i < runs; i += blockDim.x) data[i] = make_uint4(0u, 0u, 0u, 0u);
+  if (threadIdx.x == 0) {
+    if (recycle) a.block_mask[b] = 0;
+    a.recycled[b] = recycle ? 1 : 0;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------- mesh extraction
@@ -529,6 +615,40 @@ CUROBO_EXPORT int curobo_hip_mapper_occupied_flags(uint8_t *flags, const void *b
   hipLaunchKernelGGL(mapper_occupied_kernel, dim3((unsigned)ceil_div_l(voxels, kMapThreads)), dim3(kMapThreads), 0, (hipStream_t)stream, flags,
                      (const uint32_t *)block_data, block_mask, voxels, bs3, g.min_weight, surface_only != 0, sdf_threshold);
   return check_launch(what, (hipStream_t)stream);
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_decay(void *block_data, uint8_t *block_mask, uint8_t *recycled, const float *intrinsics,
+                                          const float *cam_position, const float *cam_quaternion, int n_cameras, int height, int width,
+                                          float factor_outside, float factor_inside, float empty_threshold,
+                                          const curobo_hip_mapper_params *params, curobo_hip_stream_t stream) {
+  const char *what = "mapper_decay";
+  MapGrid g;
+  if (int rc = read_params(params, &g, what)) return rc;
+  if (int rc = check_map(block_data && block_mask && recycled, block_data, "block_data, block_mask and recycled", what)) return rc;
+  CUROBO_REQUIRE(n_cameras >= 0, "%s: n_cameras must be >= 0 (0: no frustum test), got %d", what, n_cameras);
+  CUROBO_REQUIRE(n_cameras == 0 || (intrinsics && cam_position && cam_quaternion && height > 0 && width > 0),
+                 "%s: with n_cameras = %d, intrinsics, cam_position and cam_quaternion must not be null and the image %d x %d positive", what,
+                 n_cameras, height, width);
+  CUROBO_REQUIRE(factor_outside >= 0.0f && factor_outside <= 1.0f && factor_inside >= 0.0f && factor_inside <= 1.0f,
+                 "%s: factor_outside and factor_inside must lie in [0, 1], got %g and %g", what, (double)factor_outside, (double)factor_inside);
+  CUROBO_REQUIRE(empty_threshold >= 0.0f, "%s: empty_threshold must be >= 0, got %g", what, (double)empty_threshold);
+  DecayArgs a{};
+  a.block_data = (uint32_t *)block_data, a.block_mask = block_mask, a.recycled = recycled;
+  a.intrinsics = intrinsics, a.position = cam_position, a.quaternion = cam_quaternion;
+  a.n_cameras = n_cameras, a.height = height, a.width = width;
+  a.factor_outside = factor_outside, a.factor_inside = factor_inside, a.empty_threshold = empty_threshold;
+  const int bs3 = g.bs * g.bs * g.bs, n_blocks = (int)map_blocks(g);
+  const hipStream_t s = (hipStream_t)stream;
+  if (bs3 > kWave) {  // 512 voxels or more: 128 runs of four voxels, or a multiple of 256
+    CUROBO_REQUIRE(((uintptr_t)block_data & 15) == 0, "%s: block_data must be 16-byte aligned for blocks of %d voxels", what, bs3);
+    hipLaunchKernelGGL(mapper_decay_block_kernel, dim3((unsigned)n_blocks), dim3(bs3 / 4 < kMapThreads ? bs3 / 4 : kMapThreads), 0, s, a, g);
+  } else {
+    const dim3 grid((unsigned)ceil_div_l((int64_t)n_blocks * bs3, kMapThreads)), lanes(kMapThreads);
+    if (bs3 == 1) hipLaunchKernelGGL(mapper_decay_lanes_kernel<1>, grid, lanes, 0, s, a, g, n_blocks);
+    else if (bs3 == 8) hipLaunchKernelGGL(mapper_decay_lanes_kernel<8>, grid, lanes, 0, s, a, g, n_blocks);
+    else hipLaunchKernelGGL(mapper_decay_lanes_kernel<64>, grid, lanes, 0, s, a, g, n_blocks);
+  }
+  return check_launch(what, s);
 }
 
 static int check_slots(int n_slots, const MapGrid &g, const char *what) {

@@ -38,6 +38,14 @@ __device__ __forceinline__ f3 grid_centre(const MapGrid &g, int gx, int gy, int 
 template <bool UPPER> __device__ __forceinline__ float grid_face(const MapGrid &g, float b, int n, float o) {
   return ((UPPER ? b * (float)g.bs + (float)g.bs : b * (float)g.bs) - (float)n * 0.5f) * g.vs + o;
 }
+// centre of block b of an axis (n voxels, origin o): ((b bs + bs / 2) - n / 2) voxel_size + o, b a whole number (builder_decay.py:154-165)
+__device__ __forceinline__ float grid_block_centre_axis(const MapGrid &g, int b, int n, float o) {
+  return (((float)(b * g.bs) + (float)g.bs * 0.5f) - (float)n * 0.5f) * g.vs + o;
+}
+__device__ __forceinline__ f3 grid_block_centre(const MapGrid &g, int b) {
+  return make_f3(grid_block_centre_axis(g, b % g.nbx, g.grid_w, g.ox), grid_block_centre_axis(g, (b / g.nbx) % g.nby, g.grid_h, g.oy),
+                 grid_block_centre_axis(g, b / (g.nbx * g.nby), g.grid_d, g.oz));
+}
 __device__ __forceinline__ int grid_block_voxels(const MapGrid &g) { return g.bs * g.bs * g.bs; }
 // block (bx, by, bz) is row (bz nby + by) nbx + bx; voxel (lx, ly, lz) of a block is its word (lz bs + ly) bs + lx (builder_coord.py:163-176)
 __device__ __forceinline__ int grid_block(const MapGrid &g, int gx, int gy, int gz) { return ((gz / g.bs) * g.nby + gy / g.bs) * g.nbx + gx / g.bs; }
@@ -51,6 +59,15 @@ __device__ __forceinline__ uint32_t pack_half2(float a, float b) {  // (the cast
   return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)a) | ((uint32_t)__builtin_bit_cast(uint16_t, (_Float16)b) << 16);
 }
 __device__ __forceinline__ uint32_t tsdf_pair_add(uint32_t v, float sw, float w) { return pack_half2(half_lo(v) + sw, half_hi(v) + w); }
+// both words times f: each product formed in fp32, then rounded to fp16, as torch's mul_ on an fp16 tensor (wp_decay.py:127, :141)
+// The two products are made fp32 values of their own (the empty statement emits nothing): left to itself the compiler folds product
+// and conversion into v_fma_mixlo_f16, a fused multiply-add with a +0 addend, which turns a -0 product into +0 and is not the
+// fp32-then-fp16 rounding sequence of the host arithmetic this is compared with bit for bit
+__device__ __forceinline__ uint32_t tsdf_pair_scale(uint32_t v, float f) {
+  float sw = half_lo(v) * f, w = half_hi(v) * f;
+  asm volatile("" : "+v"(sw), "+v"(w));
+  return pack_half2(sw, w);
+}
 // a lookup's answer is invalid above kSdfValidBelow; a value that is not a number counts as valid, as the kernels have left it
 __device__ __forceinline__ bool sdf_is_invalid(float s) { return s > kSdfValidBelow; }
 __device__ __forceinline__ bool sdf_is_valid(float s) { return !(s > kSdfValidBelow); }

@@ -6,8 +6,9 @@ the planners.  Where the reference keeps the blocks the camera has seen in a has
 whole grid, padded to whole blocks, and keeps one byte per block, "ever visible", for "allocated".  ``extract_mesh()`` is the
 reference's third read-out: marching cubes over the ever-visible blocks, as a ``Mesh``.  ``render*()`` ray-cast the TSDF into
 depth, normal and shaded images (``renderer.py``); ``pose_refiner.py`` aligns a new depth image to the map before it is
-integrated.  Not built: decay and block recycling, static obstacles, lidar, colour and feature channels (rendered colour is
-zero), checkpoints, ``clear_blocks``, jump flooding, scatter seeding."""
+integrated.  The map forgets when asked to: per-frame weight decay (``time_decay`` / ``frustum_decay``, the constructor's
+arguments) and the recycling of blocks whose weight has decayed to nothing (``decay.py``).  Not built: static obstacles, lidar,
+colour and feature channels (rendered colour is zero), checkpoints, ``clear_blocks``, jump flooding, scatter seeding."""
 
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ from ...backends import mapper as B
 from ...scene.types import Mesh, VoxelGrid
 from ...types import CameraObservation
 from ...util.graph_capture import capture_graph
+from . import decay as D
 from . import mc_table
 from .mapper_cfg import MapperCfg
 
@@ -38,6 +40,12 @@ class DenseTSDF:
     frame_visible: torch.Tensor
     #: ``backends.mapper.MapperParams``: grid and block counts, origin, voxel size, truncation, depth range
     params: "B.MapperParams"
+    #: uint8, likewise: the block was recycled by the last decay launch (made here when not given)
+    block_recycled: Optional[torch.Tensor] = None
+
+    def __post_init__(self):
+        if self.block_recycled is None:
+            self.block_recycled = torch.zeros_like(self.block_visible)
 
     @property
     def n_blocks(self) -> int:
@@ -48,10 +56,20 @@ class Mapper:
     """``Mapper(MapperCfg(...))``; ``integrate(obs)`` per frame, ``compute_esdf()`` when a planner needs the world.
 
     ``use_graph``: record the three ESDF stages into one hipGraph on the first ``compute_esdf`` and replay it afterwards
-    (the origin and the voxel size are device tensors the recorded launches read)."""
+    (the origin and the voxel size are device tensors the recorded launches read).
 
-    def __init__(self, config: MapperCfg, use_graph: bool = True):
+    ``time_decay`` / ``frustum_decay`` in (0, 1], the reference's ``BlockSparseTSDFIntegratorCfg`` fields: with either below 1
+    every ``integrate`` but the first after construction or ``reset()`` begins with the frame decay (reference
+    ``integrator_tsdf.py:611-675``): every ever-visible block's weights times ``time_decay``, those in the union of the frusta of
+    the observation's cameras times ``time_decay frustum_decay``, and blocks whose weight has gone recycled.  With both at 1
+    nothing is launched.  They are set here, not in ``MapperCfg``, whose ``decay_factor`` / ``frustum_decay_factor`` still refuse
+    values other than 1: tests/test_mapper_host.py pins that refusal; lifting it is two lines in ``MapperCfg.__post_init__``
+    and passing the two fields on to this constructor."""
+
+    def __init__(self, config: MapperCfg, use_graph: bool = True, time_decay: float = 1.0, frustum_decay: float = 1.0):
         self.config = config
+        self._time_decay = D.check_factor("time_decay", time_decay)
+        self._frustum_decay = D.check_factor("frustum_decay", frustum_decay)
         self._device = torch.device(config.device)
         if config.dense_bytes > config.max_dense_bytes:  # (the configuration may have been edited after its own check)
             raise ValueError(f"the dense TSDF needs {config.dense_bytes} bytes, more than max_dense_bytes = {config.max_dense_bytes}")
@@ -61,7 +79,8 @@ class Mapper:
         dev, p = self._device, self._params
         self._tsdf = DenseTSDF(block_data=torch.zeros((p.n_blocks, p.block_voxels, 2), dtype=torch.float16, device=dev),
                                block_visible=torch.zeros(B.mask_bytes(p), dtype=torch.uint8, device=dev),
-                               frame_visible=torch.zeros(B.mask_bytes(p), dtype=torch.uint8, device=dev), params=p)
+                               frame_visible=torch.zeros(B.mask_bytes(p), dtype=torch.uint8, device=dev), params=p,
+                               block_recycled=torch.zeros(B.mask_bytes(p), dtype=torch.uint8, device=dev))
         self._esdf_shape = tuple(int(v) for v in config.esdf_grid_shape)
         if max(self._esdf_shape) > B.ESDF_MAX_AXIS:
             raise ValueError(f"the ESDF grid {self._esdf_shape} has more than {B.ESDF_MAX_AXIS} cells along an axis")
@@ -115,6 +134,9 @@ class Mapper:
             raise TypeError("integrate() requires a camera_observation or one positional observation.")
         depth, intrinsics, position, quaternion = self._camera_tensors(camera_observation)
         t = self._tsdf
+        if self._frame_count > 0 and (self._time_decay < 1.0 or self._frustum_decay < 1.0):  # integrator_tsdf.py:617-620
+            D.decay_frustum_aware_multi_camera(t, intrinsics, position, quaternion, depth.shape[1:], self.config.depth_minimum_distance,
+                                               self.config.depth_maximum_distance, self._time_decay, self._frustum_decay)
         B.mapper_clear_mask(t.frame_visible)
         B.mapper_mark_blocks(t.frame_visible, t.block_visible, depth, intrinsics, position, quaternion, self._params)
         B.mapper_integrate(t.block_data, t.frame_visible, depth, intrinsics, position, quaternion, self._params)
@@ -185,6 +207,7 @@ class Mapper:
         t.block_data.zero_()
         t.block_visible.zero_()
         t.frame_visible.zero_()
+        t.block_recycled.zero_()
         self._frame_count = 0
         self._last_voxel_grid = None
 
@@ -212,6 +235,18 @@ class Mapper:
         if n_clear > 0:
             self._last_voxel_grid = None
         return n_clear
+
+    def decay_and_recycle(self, decay_factor: float = 0.95) -> int:
+        """every weight times ``decay_factor`` in (0, 1], then the blocks whose weights sum to less than ``0.01 block_size^3 / 8^3``
+        recycled: no longer visible, their voxels zero.  Returns how many were (one read back to the host).  The cached grid is
+        dropped: call ``compute_esdf`` again."""
+        n = D.decay_and_recycle(self._tsdf, D.check_factor("decay_factor", decay_factor))
+        self._last_voxel_grid = None
+        return n
+
+    def recycle_empty_blocks(self) -> int:
+        """``decay_and_recycle`` without the decay (reference ``integrator_tsdf.py:837-846``)"""
+        return self.decay_and_recycle(1.0)
 
     # ------------------------------------------------------------------------------------------------ read-outs
     def extract_occupied_voxels(self, surface_only: bool = False, sdf_threshold: Optional[float] = None) -> torch.Tensor:
@@ -323,14 +358,14 @@ class Mapper:
 
     def memory_usage_mb(self) -> float:
         t = self._tsdf
-        tensors = (t.block_data, t.block_visible, t.frame_visible, self._sites, self._sites_scratch, self._dist_field)
+        tensors = (t.block_data, t.block_visible, t.frame_visible, t.block_recycled, self._sites, self._sites_scratch, self._dist_field)
         return sum(x.numel() * x.element_size() for x in tensors) / (1024.0 * 1024.0)
 
     def get_stats(self) -> dict:
-        """``frame_count``, ``total_blocks``, ``visible_blocks`` (ever), ``last_frame_blocks``, ``block_size``, ``tsdf_grid_shape``
-        (nz, ny, nx), ``esdf_grid_shape`` (nx, ny, nz), ``memory_mb``"""
+        """``frame_count``, ``total_blocks``, ``visible_blocks`` (ever), ``last_frame_blocks``, ``recycled_blocks`` (by the last
+        decay launch), ``block_size``, ``tsdf_grid_shape`` (nz, ny, nx), ``esdf_grid_shape`` (nx, ny, nz), ``memory_mb``"""
         p, t = self._params, self._tsdf
         return {"frame_count": self._frame_count, "total_blocks": p.n_blocks,
                 "visible_blocks": int(t.block_visible[: p.n_blocks].sum().item()),
-                "last_frame_blocks": int(t.frame_visible[: p.n_blocks].sum().item()), "block_size": int(p.block_size),
+                "last_frame_blocks": int(t.frame_visible[: p.n_blocks].sum().item()), "recycled_blocks": D.recycled_count(t), "block_size": int(p.block_size),
                 "tsdf_grid_shape": tuple(self.config.grid_shape), "esdf_grid_shape": self._esdf_shape, "memory_mb": self.memory_usage_mb()}

@@ -27,8 +27,13 @@ class MapperCfg:
     The TSDF is stored dense (padded to whole blocks of ``block_size`` voxels per edge), so ``hash_load_factor`` and
     ``roughness`` are accepted and have no effect, and ``max_blocks`` / ``hash_capacity`` report the dense block count; the
     bound that matters here is ``max_dense_bytes``.  Not built, and refused by name when set away from the default:
-    ``decay_factor`` / ``frustum_decay_factor`` != 1, ``enable_static``, ``lidar_num_sensors`` > 0, ``feature_dim`` > 0,
-    ``seeding_method="scatter"``, ``edt_solver="jfa"``.
+    ``enable_static``, ``lidar_num_sensors`` > 0, ``feature_dim`` > 0, ``seeding_method="scatter"``, ``edt_solver="jfa"``.
+
+    Weight decay and block recycling ARE built, yet ``decay_factor`` / ``frustum_decay_factor`` != 1 are still refused here:
+    tests/test_mapper_host.py pins that refusal and existing tests stay as they are.  Set the factors where the reference's
+    integrator has them instead: ``Mapper(cfg, time_decay=..., frustum_decay=...)``, or call ``Mapper.decay_and_recycle`` /
+    ``perception.mapper.decay`` yourself.  Lifting the refusal is a two-line follow-up: drop the two rows of the refusal table
+    below and hand the fields to ``Mapper`` as its defaults.
     """
 
     # grid
@@ -43,7 +48,7 @@ class MapperCfg:
     # depth sensor
     depth_minimum_distance: float = 0.1
     depth_maximum_distance: float = 10.0
-    # decay (not built)
+    # decay (refused here; see the docstring: Mapper(cfg, time_decay=, frustum_decay=))
     decay_factor: float = 1.0
     frustum_decay_factor: float = 1.0
     # block storage

@@ -1282,6 +1282,24 @@ int curobo_hip_mapper_occupied_flags(uint8_t *flags, const void *block_data, con
                                      const curobo_hip_mapper_params *params, int surface_only, float sdf_threshold,
                                      curobo_hip_stream_t stream);
 
+/* Weight decay and block recycling (reference kernel/wp_decay.py :111-149, kernel/builder/builder_decay.py :111-215, :322-363).
+ * Per block with block_mask != 0: both fp16 words of every voxel are multiplied in fp32 by the block's factor and rounded to
+ * nearest even -- factor_inside where the block lies in the union of the n_cameras frusta, else factor_outside (n_cameras == 0:
+ * no frustum test, factor_outside throughout; the camera pointers may be null).  The host passes the factors rounded as the
+ * reference's two paths round them: float(time_decay) for the uniform path, (float)(half)time_decay and
+ * (float)(half)(time_decay frustum_decay) for the frustum path.  In the frustum of camera c (wxyz pose, image height x width,
+ * depth range from params): with (x, y, z) the block's centre ((b BS + BS / 2) - N / 2) voxel_size + origin in the camera frame
+ * and r = 0.866 BS voxel_size: not when z + r < depth_min or z - r > depth_max; else at once when z < 0.01; else iff the disc
+ * of radii fx r / z, fy r / z about (fx x / z + cx, fy y / z + cy) reaches [0, width] x [0, height].  No depth image is read.
+ * Then the stored weights of the block are summed in fp32 in a fixed order; where the sum is < empty_threshold the block is
+ * recycled: its words and block_mask[b] become 0.  recycled uint8 [n_blocks] is written for EVERY block: 1 where this launch
+ * recycled it, else 0.  A block with block_mask == 0 is not read.  No atomics, no host read: fixed dimensions, safe in a graph.
+ * Blocks of 512 voxels or more need block_data 16-byte aligned. */
+int curobo_hip_mapper_decay(void *block_data, uint8_t *block_mask, uint8_t *recycled, const float *intrinsics,
+                            const float *cam_position, const float *cam_quaternion, int n_cameras, int height, int width,
+                            float factor_outside, float factor_inside, float empty_threshold,
+                            const curobo_hip_mapper_params *params, curobo_hip_stream_t stream);
+
 /* ---- mesh extraction: marching cubes over the ever-visible blocks (reference kernel/builder/builder_mesh.py,
  * builder_raycast.py :63-375, marching_cubes/kernel/wp_mc_common.py :464-489, wp_mc_filter.py).  block_list int32 [n_slots]
  * holds the rows of the ever-visible blocks in ascending order, block_slot int32 [n_blocks] the slot of a block or -1.

@@ -1,6 +1,6 @@
 """Times of the depth mapper (csrc/mapper.hip) at the sizes a user runs -> <out>/mapper_timing.jsonl (one line per run).
 
-    python tools/mapper_timing.py [--out profiles] [--sections map raycast]
+    python tools/mapper_timing.py [--out profiles] [--sections map raycast decay]
 
 integrate: one 480 x 640 frame into the default map of the reference, 2 m at 5 mm = 400^3 voxels in blocks of 4 (256 MB dense),
 split into the frame-mask clear, the marking stage and the voxel stage.  compute_esdf: the captured chain at 128^3 and 256^3
@@ -12,7 +12,13 @@ definitions are in the code) and what share of the 6.29 TB/s a float4 copy reach
 raycast (csrc/mapper_raycast.hip): a 640 x 480 view of a 256^3 map of 1 cm voxels after 24 frames from around the scene (about a
 tenth of the blocks visible; the share is in the output): one launch of each form of the render, one alignment evaluation at the
 refiner's default n_points = 92160 (stride 1 at this image: every pixel), and a whole ``refine_pose`` of 100 iterations by the
-host's clock."""
+host's clock.
+
+decay (csrc/mapper.hip, curobo_hip_mapper_decay): a 2 m cube at 1 cm in blocks of 4 after six frames from around the scene: the
+launch without and with one camera's frustum test, and beside it the torch formulation the reference uses on the same tensors
+(``mul_`` by a per-block fp16 factor, the fp32 block sum, a mask update).  Every factor is 1, so that the map is the same at every
+repetition.  The launch has to move 8 B per voxel of a visible block and 1 B per block; the torch chain touches every block.  For
+the kernel's own time run this section under ``rocprofv3 --kernel-trace --stats`` in a run of its own."""
 import argparse
 import json
 import os
@@ -108,11 +114,47 @@ def raycast_times(H, W, K) -> dict:
     return out
 
 
+def decay_times(H, W, K) -> dict:
+    t = lambda a: torch.as_tensor(a, device=DEV)  # noqa: E731
+    cfg = MapperCfg(extent_meters_xyz=(2.0, 2.0, 2.0), voxel_size=0.01, image_height=H, image_width=W, esdf_voxel_size=0.04,
+                    extent_esdf_meters_xyz=(2.0, 2.0, 2.0), truncation_distance=0.08)
+    m = Mapper(cfg)
+    cams = []
+    for a in np.arange(6) * (np.pi / 3):
+        eye = np.array([1.2 * np.cos(a), 1.2 * np.sin(a), 0.5], np.float32)
+        quat = R.look_at(eye, (-0.25 * eye[0], -0.25 * eye[1], -0.05), 0.2).astype(np.float32)
+        cams.append((t(K[None]), t(eye[None]), t(quat[None])))
+        m.integrate(CameraObservation(depth_image=t(R.render_depth(K, eye, quat, H, W)[None]), intrinsics=cams[-1][0], pose=Pose(*cams[-1][1:])))
+    ts, p = m.tsdf, m.tsdf.params
+    n, bs3, thr = p.n_blocks, p.block_voxels, B.decay_empty_threshold(p.block_size)
+    gone = m.recycle_empty_blocks()  # (blocks that were marked and received no weight: afterwards every launch below keeps the map as it is)
+    visible = m.get_stats()["visible_blocks"]
+    nbytes = visible * bs3 * 8 + n
+    plain = lambda: B.mapper_decay(ts.block_data, ts.block_visible, ts.block_recycled, p, 1.0, 1.0, thr)  # noqa: E731
+    frustum = lambda: B.mapper_decay(ts.block_data, ts.block_visible, ts.block_recycled, p, 1.0, 1.0, thr, *cams[0], image_shape=(H, W))  # noqa: E731
+    factor = torch.ones(n, dtype=torch.float16, device=DEV)
+    sums = torch.zeros(n, dtype=torch.float32, device=DEV)
+
+    def torch_chain():
+        ts.block_data.mul_(factor.view(n, 1, 1))
+        sums.copy_(ts.block_data[:, :, 1].sum(dim=1, dtype=torch.float32))
+        ts.block_visible[:n].mul_(~((sums < thr) & (ts.block_visible[:n] != 0)))
+
+    before = ts.block_data.clone()
+    out = {"map_voxels": [int(v) for v in cfg.grid_shape], "blocks": n, "visible_blocks": visible, "recycled_as_never_weighted": gone,
+           "launch": stage(timed(plain), nbytes), "launch_one_camera": stage(timed(frustum), nbytes),
+           # the torch chain reads and writes every word of the dense map, then reads every weight again
+           "torch_chain": stage(timed(torch_chain), n * bs3 * 10 + n * 6)}
+    torch.cuda.synchronize()
+    assert torch.equal(before.view(torch.int16), ts.block_data.view(torch.int16)) and m.get_stats()["visible_blocks"] == visible
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
-    ap.add_argument("--sections", nargs="+", choices=["map", "raycast"], default=["map", "raycast"],
-                    help="map: integrate, compute_esdf, extract_mesh; raycast: render, alignment, refine_pose")
+    ap.add_argument("--sections", nargs="+", choices=["map", "raycast", "decay"], default=["map", "raycast"],
+                    help="map: integrate, compute_esdf, extract_mesh; raycast: render, alignment, refine_pose; decay: the decay launch")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "mapper_timing needs a GPU"
     H, W = 480, 640
@@ -171,6 +213,8 @@ def main():
         torch.cuda.empty_cache()
     if "raycast" in args.sections:
         result["raycast"] = raycast_times(H, W, K)
+    if "decay" in args.sections:
+        result["decay"] = decay_times(H, W, K)
     os.makedirs(args.out, exist_ok=True)
     with open(os.path.join(args.out, "mapper_timing.jsonl"), "a") as fh:
         fh.write(json.dumps(result) + "\n")
