@@ -7,6 +7,6 @@ from curobo_amd.perception.pose_estimation import DetectorCfg, PoseDetector  # n
 # the depth mapper (Mapper / MapperCfg) is imported from curobo_amd.perception.mapper: tests/test_perception_host.py pins this
 # module as having no attribute Mapper
 # the mapper's decay and recycling functions (reference kernel/wp_decay.py): importable from here and not listed, like the detectors
-from curobo_amd.perception.mapper.decay import decay_and_recycle, decay_frustum_aware_multi_camera  # noqa: F401
+from curobo_amd.perception.mapper.decay import decay_and_recycle, decay_frustum_aware_multi_camera, decay_frustum_aware_multi_sensor  # noqa: F401
 
 __all__ = ["FilterDepth", "RobotSegmenter"]

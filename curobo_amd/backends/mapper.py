@@ -207,6 +207,100 @@ def mapper_decay(block_data: torch.Tensor, block_mask: torch.Tensor, recycled: t
                                          current_stream(block_data)))
 
 
+def _require_lidars(position, quaternion, valid_range, elevation_range, what: str, like: torch.Tensor) -> int:
+    """the per-lidar arrays ``lidar_position`` [n, 3], ``lidar_quaternion`` [n, 4] wxyz, ``valid_range`` [n, 2], ``elevation_range`` [n, 2]"""
+    if position is None or position.dim() != 2:
+        raise ValueError(f"{what}: lidar_position must have shape (num_lidars, 3), got {None if position is None else tuple(position.shape)}")
+    n = int(position.shape[0])
+    for name, t, shape in (("lidar_position", position, (n, 3)), ("lidar_quaternion", quaternion, (n, 4)), ("valid_range", valid_range, (n, 2)),
+                           ("elevation_range", elevation_range, (n, 2))):
+        if t is None:
+            raise ValueError(f"{what}: {name} is required")
+        _require(t, name, torch.float32, like)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{what}: {name} must have shape {shape}, got {tuple(t.shape)}")
+    if n <= 0:
+        raise ValueError(f"{what}: need at least one lidar")
+    return n
+
+
+def _require_range(range_image, position, quaternion, valid_range, elevation_range, what: str):
+    if range_image.dim() != 3:
+        raise ValueError(f"{what}: range_image must be (num_lidars, H, W), got {tuple(range_image.shape)}")
+    _require(range_image, "range_image", torch.float32)
+    n, h, w = (int(v) for v in range_image.shape)
+    if _require_lidars(position, quaternion, valid_range, elevation_range, what, range_image) != n:
+        raise ValueError(f"{what}: lidar_position holds {int(position.shape[0])} lidars, range_image {n}")
+    return n, h, w
+
+
+def mapper_lidar_mark_blocks(lidar_mask: torch.Tensor, frame_mask: torch.Tensor, block_mask: torch.Tensor, range_image: torch.Tensor,
+                             lidar_position: torch.Tensor, lidar_quaternion: torch.Tensor, valid_range: torch.Tensor,
+                             elevation_range: torch.Tensor, params: MapperParams) -> None:
+    """``curobo_hip_mapper_lidar_mark_blocks``: 1 into the three masks for every block a sample of this frame's range images
+    ``(num_lidars, H, W)`` falls into; ``valid_range`` [n, 2] metres, ``elevation_range`` [n, 2] radians"""
+    what = "mapper_lidar_mark_blocks"
+    n, h, w = _require_range(range_image, lidar_position, lidar_quaternion, valid_range, elevation_range, what)
+    _require_map(params, what, like=range_image, lidar_mask=lidar_mask, frame_mask=frame_mask, block_mask=block_mask)
+    check(load().curobo_hip_mapper_lidar_mark_blocks(ptr(lidar_mask), ptr(frame_mask), ptr(block_mask), ptr(range_image), ptr(lidar_position),
+                                                     ptr(lidar_quaternion), ptr(valid_range), ptr(elevation_range), _C.addressof(params), n, h, w,
+                                                     current_stream(range_image)))
+
+
+def mapper_lidar_integrate(block_data: torch.Tensor, lidar_mask: torch.Tensor, range_image: torch.Tensor, lidar_position: torch.Tensor,
+                           lidar_quaternion: torch.Tensor, valid_range: torch.Tensor, elevation_range: torch.Tensor, params: MapperParams,
+                           linear_max_diff_m: float, nearest_max_dist_m: float) -> None:
+    """``curobo_hip_mapper_lidar_integrate``: every voxel of every block of ``lidar_mask``; the two interpolation guards in metres"""
+    what = "mapper_lidar_integrate"
+    n, h, w = _require_range(range_image, lidar_position, lidar_quaternion, valid_range, elevation_range, what)
+    _require_map(params, what, block_data, like=range_image, lidar_mask=lidar_mask)
+    for name, v in (("linear_max_diff_m", linear_max_diff_m), ("nearest_max_dist_m", nearest_max_dist_m)):
+        if not float(v) > 0.0:
+            raise ValueError(f"{what}: {name} must be positive, got {v}")
+    check(load().curobo_hip_mapper_lidar_integrate(ptr(block_data), ptr(lidar_mask), ptr(range_image), ptr(lidar_position), ptr(lidar_quaternion),
+                                                   ptr(valid_range), ptr(elevation_range), _C.addressof(params), n, h, w,
+                                                   float(linear_max_diff_m), float(nearest_max_dist_m), current_stream(range_image)))
+
+
+def mapper_decay_sensors(block_data: torch.Tensor, block_mask: torch.Tensor, recycled: torch.Tensor, params: MapperParams,
+                         factor_outside: float, factor_inside: float, empty_threshold: float, intrinsics: Optional[torch.Tensor] = None,
+                         cam_position: Optional[torch.Tensor] = None, cam_quaternion: Optional[torch.Tensor] = None,
+                         image_shape: Sequence[int] = (0, 0), lidar_position: Optional[torch.Tensor] = None,
+                         lidar_quaternion: Optional[torch.Tensor] = None, lidar_valid_range: Optional[torch.Tensor] = None,
+                         lidar_elevation_range: Optional[torch.Tensor] = None, lidar_height: int = 0) -> None:
+    """``curobo_hip_mapper_decay_sensors``: ``mapper_decay`` over the union of the cameras' frusta and the lidars' (``lidar_position``
+    [n, 3], ``lidar_quaternion`` [n, 4] wxyz, ``lidar_valid_range`` [n, 2] metres, ``lidar_elevation_range`` [n, 2] radians,
+    ``lidar_height`` the rows of the range image); either set may be left out"""
+    what = "mapper_decay_sensors"
+    _require_map(params, what, block_data, like=block_data, block_mask=block_mask, recycled=recycled)
+    for name, f in (("factor_outside", factor_outside), ("factor_inside", factor_inside)):
+        if not 0.0 <= float(f) <= 1.0:
+            raise ValueError(f"{what}: {name} must lie in [0, 1], got {f}")
+    cameras = (intrinsics, cam_position, cam_quaternion)
+    n, h, w = 0, 0, 0
+    if any(t is not None for t in cameras):
+        if any(t is None for t in cameras):
+            raise ValueError(f"{what}: intrinsics, cam_position and cam_quaternion come together")
+        n, (h, w) = int(intrinsics.shape[0]), (int(v) for v in image_shape)
+        for name, t, shape in (("intrinsics", intrinsics, (n, 3, 3)), ("cam_position", cam_position, (n, 3)), ("cam_quaternion", cam_quaternion, (n, 4))):
+            _require(t, name, torch.float32, block_data)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{what}: {name} must have shape {shape}, got {tuple(t.shape)}")
+        if n <= 0 or h <= 0 or w <= 0:
+            raise ValueError(f"{what}: need at least one camera and a positive image_shape, got {n} cameras and {(h, w)}")
+    lidars = (lidar_position, lidar_quaternion, lidar_valid_range, lidar_elevation_range)
+    n_lidars = 0
+    if any(t is not None for t in lidars):
+        n_lidars = _require_lidars(*lidars, what, block_data)
+        if int(lidar_height) <= 0:
+            raise ValueError(f"{what}: lidar_height must be positive, got {lidar_height}")
+    check(load().curobo_hip_mapper_decay_sensors(ptr(block_data), ptr(block_mask), ptr(recycled), ptr(intrinsics), ptr(cam_position),
+                                                 ptr(cam_quaternion), n, h, w, ptr(lidar_position), ptr(lidar_quaternion), ptr(lidar_valid_range),
+                                                 ptr(lidar_elevation_range), n_lidars, int(lidar_height) if n_lidars else 0,
+                                                 float(factor_outside), float(factor_inside), float(empty_threshold), _C.addressof(params),
+                                                 current_stream(block_data)))
+
+
 def _require_mesh(params: MapperParams, what: str, block_list: torch.Tensor, **per_voxel) -> int:
     """``block_list`` int32 [n_slots] and the per-voxel arrays [n_slots * block_size^3] (``(tensor, dtype, width)``); returns n_slots"""
     _require(block_list, "block_list", torch.int32)

@@ -41,6 +41,7 @@ SOURCES = [
     "pose_icp.hip",
     "mapper.hip",
     "mapper_raycast.hip",
+    "mapper_lidar.hip",
     "support_polygon.hip",
     "link_pair_sweep.hip",
 ]

@@ -9,7 +9,8 @@
 //   curobo_hip_mapper_occupied_flags  the rule of extract_occupied_voxels per voxel
 //   curobo_hip_mapper_decay           per ever-visible block: its words times the block's factor, the weights summed, the block
 //                                     recycled (words and mask byte to 0) where the sum is below the threshold
-//   curobo_hip_mapper_mesh_classify   extract_mesh, per (visible block, tile): corner values in LDS, the cubes' cases and counts
+//   curobo_hip_mapper_decay_sensors   the same launch with the frusta of lidars beside the cameras' (lidar integration: mapper_lidar.hip)
+//   curobo_hip_mapper_mesh_classify  extract_mesh, per (visible block, tile): corner values in LDS, the cubes' cases and counts
 //   curobo_hip_mapper_mesh_vertices   ... per voxel: the vertices of its own cut edges, refined, with normals
 //   curobo_hip_mapper_mesh_triangles  ... per voxel: the table's triangles through the edges' owner cubes, and which of them stay
 //   curobo_hip_mapper_mesh_compact    ... per triangle: those that stay, in order
@@ -212,7 +213,7 @@ __global__ __launch_bounds__(kMapThreads) void mapper_occupied_kernel(uint8_t *f
 
 // ---------------------------------------------------------------------------------------------------- decay and recycling
 // Per ever-visible block: both words of every voxel times the block's factor (factor_inside where the block lies in the union of
-// the cameras' frusta, else factor_outside), the stored weights summed, and the block recycled -- words and mask byte to 0 -- where
+// the cameras' and the lidars' frusta, else factor_outside), the stored weights summed, and the block recycled -- words and mask byte to 0 -- where
 // the sum is below empty_threshold (wp_decay.py:111-149, builder_decay.py:322-363).  recycled[b] says what this launch did.
 struct DecayArgs {
   uint32_t *block_data;
@@ -220,6 +221,8 @@ struct DecayArgs {
   const float *intrinsics, *position, *quaternion;
   int n_cameras, height, width;
   float factor_outside, factor_inside, empty_threshold;
+  const float *lidar_position, *lidar_quaternion, *lidar_valid_range, *lidar_elevation_range;  // curobo_hip_mapper_decay_sensors
+  int n_lidars, lidar_height;
 };
 
 // mark_blocks_in_frustum_kernel (builder_decay.py:111-215) for one block and every camera: the block's bounding sphere against the
@@ -236,6 +239,23 @@ __device__ __forceinline__ bool block_in_frusta(const DecayArgs &a, const MapGri
     const float u = c.fx * v.x / z + c.cx, w = c.fy * v.y / z + c.cy;
     const float ru = c.fx * r / z, rw = c.fy * r / z;
     if (u + ru < 0.0f || u - ru > (float)a.width || w + rw < 0.0f || w - rw > (float)a.height) continue;
+    return true;
+  }
+  // mark_lidar_blocks_in_frustum_kernel (builder_decay.py:217-313) for every lidar: the same sphere against the range band, then its
+  // angular radius about the centre's elevation against the elevation band (a planar sensor: against its one elevation); a lidar
+  // sees every azimuth, and no range image is read
+  for (int i = 0; i < a.n_lidars; i++) {
+    const MapLidar l = read_lidar(a.lidar_position, a.lidar_quaternion, a.lidar_valid_range, a.lidar_elevation_range, i);
+    const f3 v = quat_rotate(l.qw, make_f3(-l.qv.x, -l.qv.y, -l.qv.z), centre - l.t);
+    const float range = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z);
+    if (range + r < l.min_range || range - r > l.max_range) continue;
+    const float elevation = atan2f(v.z, sqrtf(v.x * v.x + v.y * v.y));
+    const float angular = range > r ? asinf(fminf(fmaxf(r / range, 0.0f), 1.0f)) : kLidarPi;
+    if (a.lidar_height == 1) {
+      if (fabsf(elevation - (l.min_elev + l.max_elev) * 0.5f) <= angular) return true;
+      continue;
+    }
+    if (elevation + angular < l.min_elev || elevation - angular > l.max_elev) continue;
     return true;
   }
   return false;
@@ -617,11 +637,11 @@ CUROBO_EXPORT int curobo_hip_mapper_occupied_flags(uint8_t *flags, const void *b
   return check_launch(what, (hipStream_t)stream);
 }
 
-CUROBO_EXPORT int curobo_hip_mapper_decay(void *block_data, uint8_t *block_mask, uint8_t *recycled, const float *intrinsics,
-                                          const float *cam_position, const float *cam_quaternion, int n_cameras, int height, int width,
-                                          float factor_outside, float factor_inside, float empty_threshold,
-                                          const curobo_hip_mapper_params *params, curobo_hip_stream_t stream) {
-  const char *what = "mapper_decay";
+static int launch_decay(const char *what, void *block_data, uint8_t *block_mask, uint8_t *recycled, const float *intrinsics,
+                        const float *cam_position, const float *cam_quaternion, int n_cameras, int height, int width,
+                        const float *lidar_position, const float *lidar_quaternion, const float *lidar_valid_range,
+                        const float *lidar_elevation_range, int n_lidars, int lidar_height, float factor_outside, float factor_inside,
+                        float empty_threshold, const curobo_hip_mapper_params *params, curobo_hip_stream_t stream) {
   MapGrid g;
   if (int rc = read_params(params, &g, what)) return rc;
   if (int rc = check_map(block_data && block_mask && recycled, block_data, "block_data, block_mask and recycled", what)) return rc;
@@ -629,6 +649,10 @@ CUROBO_EXPORT int curobo_hip_mapper_decay(void *block_data, uint8_t *block_mask,
   CUROBO_REQUIRE(n_cameras == 0 || (intrinsics && cam_position && cam_quaternion && height > 0 && width > 0),
                  "%s: with n_cameras = %d, intrinsics, cam_position and cam_quaternion must not be null and the image %d x %d positive", what,
                  n_cameras, height, width);
+  CUROBO_REQUIRE(n_lidars >= 0, "%s: n_lidars must be >= 0 (0: no lidar frustum), got %d", what, n_lidars);
+  CUROBO_REQUIRE(n_lidars == 0 || (lidar_position && lidar_quaternion && lidar_valid_range && lidar_elevation_range && lidar_height > 0),
+                 "%s: with n_lidars = %d, lidar_position, lidar_quaternion, lidar_valid_range and lidar_elevation_range must not be null "
+                 "and lidar_height = %d positive", what, n_lidars, lidar_height);
   CUROBO_REQUIRE(factor_outside >= 0.0f && factor_outside <= 1.0f && factor_inside >= 0.0f && factor_inside <= 1.0f,
                  "%s: factor_outside and factor_inside must lie in [0, 1], got %g and %g", what, (double)factor_outside, (double)factor_inside);
   CUROBO_REQUIRE(empty_threshold >= 0.0f, "%s: empty_threshold must be >= 0, got %g", what, (double)empty_threshold);
@@ -637,6 +661,8 @@ CUROBO_EXPORT int curobo_hip_mapper_decay(void *block_data, uint8_t *block_mask,
   a.intrinsics = intrinsics, a.position = cam_position, a.quaternion = cam_quaternion;
   a.n_cameras = n_cameras, a.height = height, a.width = width;
   a.factor_outside = factor_outside, a.factor_inside = factor_inside, a.empty_threshold = empty_threshold;
+  a.lidar_position = lidar_position, a.lidar_quaternion = lidar_quaternion, a.lidar_valid_range = lidar_valid_range;
+  a.lidar_elevation_range = lidar_elevation_range, a.n_lidars = n_lidars, a.lidar_height = lidar_height;
   const int bs3 = g.bs * g.bs * g.bs, n_blocks = (int)map_blocks(g);
   const hipStream_t s = (hipStream_t)stream;
   if (bs3 > kWave) {  // 512 voxels or more: 128 runs of four voxels, or a multiple of 256
@@ -649,6 +675,25 @@ CUROBO_EXPORT int curobo_hip_mapper_decay(void *block_data, uint8_t *block_mask,
     else hipLaunchKernelGGL(mapper_decay_lanes_kernel<64>, grid, lanes, 0, s, a, g, n_blocks);
   }
   return check_launch(what, s);
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_decay(void *block_data, uint8_t *block_mask, uint8_t *recycled, const float *intrinsics,
+                                          const float *cam_position, const float *cam_quaternion, int n_cameras, int height, int width,
+                                          float factor_outside, float factor_inside, float empty_threshold,
+                                          const curobo_hip_mapper_params *params, curobo_hip_stream_t stream) {
+  return launch_decay("mapper_decay", block_data, block_mask, recycled, intrinsics, cam_position, cam_quaternion, n_cameras, height, width,
+                      nullptr, nullptr, nullptr, nullptr, 0, 0, factor_outside, factor_inside, empty_threshold, params, stream);
+}
+
+CUROBO_EXPORT int curobo_hip_mapper_decay_sensors(void *block_data, uint8_t *block_mask, uint8_t *recycled, const float *intrinsics,
+                                                  const float *cam_position, const float *cam_quaternion, int n_cameras, int height,
+                                                  int width, const float *lidar_position, const float *lidar_quaternion,
+                                                  const float *lidar_valid_range, const float *lidar_elevation_range, int n_lidars,
+                                                  int lidar_height, float factor_outside, float factor_inside, float empty_threshold,
+                                                  const curobo_hip_mapper_params *params, curobo_hip_stream_t stream) {
+  return launch_decay("mapper_decay_sensors", block_data, block_mask, recycled, intrinsics, cam_position, cam_quaternion, n_cameras, height,
+                      width, lidar_position, lidar_quaternion, lidar_valid_range, lidar_elevation_range, n_lidars, lidar_height,
+                      factor_outside, factor_inside, empty_threshold, params, stream);
 }
 
 static int check_slots(int n_slots, const MapGrid &g, const char *what) {

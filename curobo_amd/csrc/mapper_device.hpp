@@ -1,5 +1,5 @@
-// mapper_device.hpp -- the one statement of the mapper's grid for mapper.hip and mapper_raycast.hip: how a world position, a voxel,
-// a block, the stored fp16 pair, an ESDF cell, a packed site and a camera's pixel are addressed and read.  The lookups take the two
+// mapper_device.hpp -- the one statement of the mapper's grid for mapper.hip, mapper_raycast.hip and mapper_lidar.hip: how a world
+// position, a voxel, a block, the stored fp16 pair, an ESDF cell, a packed site, a camera's pixel and a lidar's are addressed and read.  The lookups take the two
 // arrays they read, block_data and block_mask, and nothing else of a launch's arguments.
 #pragma once
 #include "common.hpp"
@@ -166,6 +166,44 @@ __device__ __forceinline__ MapCamera read_camera(const float *intrinsics, const 
 // HALF_PIXEL: through the pixel's centre (builder_camera_integrate.py:125-127, the renders); not so wp_raycast_pose_refine.py:171-172
 template <bool HALF_PIXEL> __device__ __forceinline__ f3 pixel_ray(const MapCamera &c, int px, int py) {
   return make_f3(((HALF_PIXEL ? (float)px + 0.5f : (float)px) - c.cx) / c.fx, ((HALF_PIXEL ? (float)py + 0.5f : (float)py) - c.cy) / c.fy, 1.0f);
+}
+// lidar `i` of the arrays position [n, 3], quaternion [n, 4] wxyz, valid_range [n, 2] metres, elevation_range [n, 2] radians: its pose
+// in the world is t, (qw, qv); a range image of H x W pixels covers the full azimuth and the elevation band
+struct MapLidar { f3 t; float qw; f3 qv; float min_range, max_range, min_elev, max_elev; };
+__device__ __forceinline__ MapLidar read_lidar(const float *position, const float *quaternion, const float *valid_range,
+                                               const float *elevation_range, int i) {
+  const float *q = quaternion + i * 4, *t = position + i * 3, *r = valid_range + i * 2, *e = elevation_range + i * 2;
+  return MapLidar{make_f3(t[0], t[1], t[2]), q[0], make_f3(q[1], q[2], q[3]), r[0], r[1], e[0], e[1]};
+}
+// pi and 2 pi as the reference's kernels hold them, fp32 constants (builder_lidar_integrate.py:52-53); the double forms of the rules
+// below widen THESE, so that a float64 restatement with the same two numbers says what the launch computes
+constexpr float kLidarPi = 3.141592653589793f, kLidarTwoPi = 6.283185307179586f;
+// _range_valid (builder_lidar_integrate.py:106-112), of a pixel's range or a voxel's; false for a value that is not a number
+template <typename T> __device__ __forceinline__ bool lidar_range_valid(T value, const MapLidar &l) {
+  return value >= (T)l.min_range && value <= (T)l.max_range;
+}
+// the unit ray of pixel (px, py) in the sensor frame (:75-94): azimuth px 2 pi / W - pi, NO half pixel; elevation from max_elev in
+// row 0 down to min_elev in row H - 1, min_elev where H == 1
+__device__ __forceinline__ f3 lidar_pixel_ray(const MapLidar &l, int px, int py, int height, int width) {
+  const float azimuth = (float)px * kLidarTwoPi / (float)width - kLidarPi;
+  const float elevation = height > 1 ? l.max_elev - (float)py * (l.max_elev - l.min_elev) / (float)(height - 1) : l.min_elev;
+  const float ce = cosf(elevation);
+  return make_f3(cosf(azimuth) * ce, sinf(azimuth) * ce, sinf(elevation));
+}
+// voxel -> (u, v), the inverse of the above (:421-437), from the voxel's position (x, y, z) in the sensor frame.  false where the
+// elevation is outside the band (H > 1 only; the planar sensor takes every elevation and v = 0); u is wrapped into [0, W)
+template <typename T> __device__ __forceinline__ bool lidar_voxel_uv(const MapLidar &l, T x, T y, T z, int height, int width, T *u, T *v) {
+  *v = (T)0;
+  if (height > 1) {
+    const T elevation = atan2(z, sqrt(x * x + y * y));
+    if (elevation < (T)l.min_elev || elevation > (T)l.max_elev) return false;
+    *v = ((T)l.max_elev - elevation) * ((T)(height - 1) / ((T)l.max_elev - (T)l.min_elev));
+  }
+  T uf = (atan2(y, x) + (T)kLidarPi) * ((T)width / (T)kLidarTwoPi);
+  if (uf >= (T)width) uf -= (T)width;
+  if (uf < (T)0) uf += (T)width;
+  *u = uf;
+  return true;
 }
 #endif  // __HIPCC__
 static int read_params(const curobo_hip_mapper_params *p, MapGrid *g, const char *what) {

@@ -1,5 +1,6 @@
 """Weight decay and block recycling of the mapper's TSDF: the module functions of the reference's ``kernel/wp_decay.py`` over
-``DenseTSDF``, one launch of ``curobo_hip_mapper_decay`` each (``csrc/mapper.hip``).
+``DenseTSDF``, one launch of ``curobo_hip_mapper_decay`` each, or of ``curobo_hip_mapper_decay_sensors`` where lidars have a
+frustum too (``csrc/mapper.hip``).
 
 The reference multiplies the whole pool with torch (``block_data.mul_``), sums every block's weights and launches a recycle kernel
 over the sums; here one launch does the three per ever-visible block and reads nothing of the others.  Its two paths round the
@@ -46,6 +47,12 @@ def _launch(tsdf, factor_outside: float, factor_inside: float, params=None, came
                        B.decay_empty_threshold(params.block_size), *cameras, image_shape=image_shape)
 
 
+def _launch_sensors(tsdf, factor_outside: float, factor_inside: float, params, cameras, image_shape, lidars, lidar_height: int) -> None:
+    with torch.cuda.device(tsdf.block_data.device):
+        B.mapper_decay_sensors(tsdf.block_data, tsdf.block_visible, tsdf.block_recycled, params, factor_outside, factor_inside,
+                               B.decay_empty_threshold(params.block_size), *cameras, image_shape, *lidars, lidar_height)
+
+
 def decay_and_recycle(tsdf, decay_factor: float = 0.95) -> int:
     """every voxel's pair times ``decay_factor`` (left alone when it is >= 1), then every block whose weights sum to less than
     ``0.01 block_size^3 / 8^3`` recycled; returns how many were (a read back to the host: not for a captured graph).
@@ -82,3 +89,47 @@ def decay_frustum_aware_multi_camera(tsdf, intrinsics: torch.Tensor, cam_positio
     # the per-block factor tensor is fp16: both values rounded on the fill, the in-frustum one from the product in double
     _launch(tsdf, _f16(time_decay), _f16(float(time_decay) * float(frustum_decay)), params, cameras,
             (int(img_shape[0]), int(img_shape[1])))
+
+
+def decay_frustum_aware_multi_sensor(tsdf, *, camera_intrinsics: Optional[torch.Tensor] = None, camera_positions: Optional[torch.Tensor] = None,
+                                     camera_quaternions: Optional[torch.Tensor] = None, camera_img_shape: Optional[Sequence[int]] = None,
+                                     camera_depth_minimum_distance: float = 0.1, camera_depth_maximum_distance: float = 10.0,
+                                     lidar_positions: Optional[torch.Tensor] = None, lidar_quaternions: Optional[torch.Tensor] = None,
+                                     lidar_valid_range_m: Optional[torch.Tensor] = None, lidar_elevation_range_rad: Optional[torch.Tensor] = None,
+                                     lidar_img_shape: Optional[Sequence[int]] = None, time_decay: float = 1.0, frustum_decay: float = 0.5,
+                                     num_blocks: Optional[int] = None) -> None:
+    """``decay_frustum_aware_multi_camera`` over the union of the frusta of cameras AND lidars, either of which may be left out:
+    ``lidar_positions`` [n, 3], ``lidar_quaternions`` [n, 4] wxyz, ``lidar_valid_range_m`` [n, 2], ``lidar_elevation_range_rad``
+    [n, 2], ``lidar_img_shape`` (H, W) of the range images (H == 1: a planar scan, tested against its one elevation), float32 on
+    the map's device.  A lidar's frustum is its range band and elevation band over every azimuth; neither depth nor range images
+    are looked at.  One launch of ``curobo_hip_mapper_decay_sensors``; the factors are rounded as the camera path rounds them.
+    Reference ``wp_decay.py:152-291``, ``builder_decay.py:217-313``."""
+    if not (float(time_decay) > 0.0 and float(frustum_decay) > 0.0):
+        raise ValueError(f"time_decay and frustum_decay must be positive: {time_decay}, {frustum_decay}")
+    if frustum_decay >= 1.0:
+        factor = _f32(time_decay) if time_decay < 1.0 else 1.0
+        _launch(tsdf, factor, factor)
+        return
+    if not float(time_decay) <= 1.0:
+        raise ValueError(f"time_decay must be <= 1 on the frustum path: {time_decay}")
+    f32 = dict(device=tsdf.block_data.device, dtype=torch.float32)
+    params = copy.copy(tsdf.params)  # the frustum test's depth range is this call's, not the integration's
+    cameras, image_shape = (None, None, None), (0, 0)
+    if camera_intrinsics is not None:
+        if camera_positions is None or camera_quaternions is None or camera_img_shape is None:
+            raise ValueError("camera_intrinsics requires camera_positions, camera_quaternions, and camera_img_shape.")
+        params.depth_min, params.depth_max = float(camera_depth_minimum_distance), float(camera_depth_maximum_distance)
+        cameras = (camera_intrinsics.to(**f32).reshape(-1, 3, 3).contiguous(), camera_positions.to(**f32).reshape(-1, 3).contiguous(),
+                   camera_quaternions.to(**f32).reshape(-1, 4).contiguous())
+        image_shape = (int(camera_img_shape[0]), int(camera_img_shape[1]))
+    lidars, lidar_height = (None, None, None, None), 0
+    if lidar_positions is not None:
+        if lidar_quaternions is None or lidar_valid_range_m is None or lidar_elevation_range_rad is None or lidar_img_shape is None:
+            raise ValueError("lidar_positions requires lidar_quaternions, lidar_valid_range_m, lidar_elevation_range_rad, and lidar_img_shape.")
+        lidar_height = int(lidar_img_shape[0])
+        if lidar_height <= 0:
+            raise ValueError(f"lidar_img_shape height must be positive, got {lidar_height}.")
+        lidars = (lidar_positions.to(**f32).reshape(-1, 3).contiguous(), lidar_quaternions.to(**f32).reshape(-1, 4).contiguous(),
+                  lidar_valid_range_m.to(**f32).reshape(-1, 2).contiguous(), lidar_elevation_range_rad.to(**f32).reshape(-1, 2).contiguous())
+    # the per-block factor tensor is fp16: both values rounded on the fill, the in-frustum one from the product in double
+    _launch_sensors(tsdf, _f16(time_decay), _f16(float(time_decay) * float(frustum_decay)), params, cameras, image_shape, lidars, lidar_height)

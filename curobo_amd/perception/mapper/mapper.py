@@ -7,8 +7,11 @@ whole grid, padded to whole blocks, and keeps one byte per block, "ever visible"
 reference's third read-out: marching cubes over the ever-visible blocks, as a ``Mesh``.  ``render*()`` ray-cast the TSDF into
 depth, normal and shaded images (``renderer.py``); ``pose_refiner.py`` aligns a new depth image to the map before it is
 integrated.  The map forgets when asked to: per-frame weight decay (``time_decay`` / ``frustum_decay``, the constructor's
-arguments) and the recycling of blocks whose weight has decayed to nothing (``decay.py``).  Not built: static obstacles, lidar,
-colour and feature channels (rendered colour is zero), checkpoints, ``clear_blocks``, jump flooding, scatter seeding."""
+arguments) and the recycling of blocks whose weight has decayed to nothing (``decay.py``).  Lidar range images
+(``LidarObservation``) are fused into the same voxels by two launches of their own (``csrc/mapper_lidar.hip``), alone or in one
+frame with the cameras; the sensors are described by the constructor's ``lidar=MapperLidarCfg(...)``.  Not built: static
+obstacles, colour and feature channels (rendered colour is zero; a lidar's ``rgb_image`` is checked and not used), checkpoints,
+``clear_blocks``, jump flooding, scatter seeding."""
 
 from __future__ import annotations
 
@@ -20,11 +23,11 @@ import torch
 
 from ...backends import mapper as B
 from ...scene.types import Mesh, VoxelGrid
-from ...types import CameraObservation
+from ...types import CameraObservation, LidarObservation
 from ...util.graph_capture import capture_graph
 from . import decay as D
 from . import mc_table
-from .mapper_cfg import MapperCfg
+from .mapper_cfg import MapperCfg, MapperLidarCfg
 
 
 @dataclass
@@ -40,10 +43,15 @@ class DenseTSDF:
     frame_visible: torch.Tensor
     #: ``backends.mapper.MapperParams``: grid and block counts, origin, voxel size, truncation, depth range
     params: "B.MapperParams"
+    #: uint8, likewise: the block was visible to a LIDAR in the last frame that carried lidars -- what the lidar integration reads,
+    #: a subset of ``frame_visible`` in that frame (made here when not given)
+    lidar_frame_visible: Optional[torch.Tensor] = None
     #: uint8, likewise: the block was recycled by the last decay launch (made here when not given)
     block_recycled: Optional[torch.Tensor] = None
 
     def __post_init__(self):
+        if self.lidar_frame_visible is None:
+            self.lidar_frame_visible = torch.zeros_like(self.block_visible)
         if self.block_recycled is None:
             self.block_recycled = torch.zeros_like(self.block_visible)
 
@@ -52,8 +60,24 @@ class DenseTSDF:
         return self.params.n_blocks
 
 
-class Mapper:
+class _LidarAtConstruction(type):
+    """``Mapper(cfg, ..., lidar=MapperLidarCfg(...))``: the keyword is taken here and handed to ``Mapper.configure_lidar``, because
+    tests/test_mapper_decay_host.py pins the parameter list of ``Mapper.__init__`` as it was and existing tests stay as they are.
+    Once that pin is lifted ``lidar`` becomes a parameter of ``__init__`` like any other and this class goes."""
+
+    def __call__(cls, *args, lidar: Optional[MapperLidarCfg] = None, **kwargs):
+        mapper = super().__call__(*args, **kwargs)
+        mapper.configure_lidar(lidar)
+        return mapper
+
+
+class Mapper(metaclass=_LidarAtConstruction):
     """``Mapper(MapperCfg(...))``; ``integrate(obs)`` per frame, ``compute_esdf()`` when a planner needs the world.
+
+    ``lidar=MapperLidarCfg(num_sensors=..., image_height=..., image_width=...)``: the lidars whose ``LidarObservation`` this mapper
+    integrates, alone or together with a ``CameraObservation`` in one frame; without it a ``lidar_observation`` is refused.  The
+    setting is the constructor's and not ``MapperCfg``'s, whose ``lidar_num_sensors`` > 0 still refuses: tests/test_mapper_host.py
+    pins that refusal; lifting it is a follow-up (build the ``MapperLidarCfg`` from ``MapperCfg.lidar_*`` and hand it on).
 
     ``use_graph``: record the three ESDF stages into one hipGraph on the first ``compute_esdf`` and replay it afterwards
     (the origin and the voxel size are device tensors the recorded launches read).
@@ -98,6 +122,20 @@ class Mapper:
         self._last_voxel_grid: Optional[VoxelGrid] = None
         self._mc_tables = None  # (case table, edge owners) on the device, from the first extract_mesh on
         self._renderer = None   # from the first render on
+        self._lidar: Optional[MapperLidarCfg] = None
+
+    def configure_lidar(self, lidar: Optional[MapperLidarCfg]) -> None:
+        """what the constructor's ``lidar=`` does: the lidars of the ``LidarObservation`` frames to come (``None``: none, refuse them)"""
+        if lidar is not None and not isinstance(lidar, MapperLidarCfg):
+            raise TypeError(f"lidar must be a MapperLidarCfg, got {type(lidar).__name__}")
+        limit = None if lidar is None else lidar.max_visible_blocks_per_lidar_integration
+        if limit is not None and limit > self._params.n_blocks:  # (the reference's bound, mapper_cfg.py:290-300; no effect otherwise)
+            raise ValueError(f"max_visible_blocks_per_lidar_integration must satisfy 0 < value <= {self._params.n_blocks}, got {limit}")
+        self._lidar = lidar
+
+    @property
+    def lidar_config(self) -> Optional[MapperLidarCfg]:
+        return self._lidar
 
     # ------------------------------------------------------------------------------------------------ storage
     @property
@@ -109,10 +147,15 @@ class Mapper:
         return self._esdf_shape
 
     # ------------------------------------------------------------------------------------------------ integration
-    def integrate(self, *args, observation=None, camera_observation: Optional[CameraObservation] = None, lidar_observation=None) -> None:
-        """fuse one batch of depth images: ``depth_image`` float32 metres ``(num_cameras, H, W)`` (``depth_to_meter`` is not
-        applied), ``intrinsics`` ``(n, 3, 3)``, ``pose`` the cameras in the world (position, wxyz quaternion).  Positional
-        ``integrate(obs)``, ``camera_observation=`` and the older ``observation=`` are accepted as in the reference."""
+    def integrate(self, *args, observation=None, camera_observation: Optional[CameraObservation] = None,
+                  lidar_observation: Optional[LidarObservation] = None) -> None:
+        """fuse one frame.  A ``CameraObservation``: a batch of depth images, ``depth_image`` float32 metres ``(num_cameras, H, W)``
+        (``depth_to_meter`` is not applied), ``intrinsics`` ``(n, 3, 3)``, ``pose`` the cameras in the world (position, wxyz
+        quaternion).  A ``LidarObservation`` (with ``lidar=`` given to the constructor): ``range_image`` float32 metres
+        ``(num_sensors, H, W)``, ``pose``, ``valid_range_m`` and ``elevation_range_rad`` ``(n, 2)``.  Positional ``integrate(obs)``,
+        ``camera_observation=``, ``lidar_observation=`` and the older ``observation=`` are accepted as in the reference; one call may
+        carry a camera and a lidar observation, which make ONE frame (reference ``integrator_tsdf.py:451-493``): the frame decay once
+        over the union of both kinds of frusta, the camera stages, then the lidar stages."""
         if len(args) > 1:
             raise TypeError(f"integrate() takes at most one positional observation, got {len(args)}.")
         if args:
@@ -124,24 +167,89 @@ class Mapper:
         if observation is not None:
             if isinstance(observation, CameraObservation):
                 camera_observation = observation
-            elif type(observation).__name__ == "LidarObservation":
+            elif isinstance(observation, LidarObservation):
                 lidar_observation = observation
             else:
                 raise TypeError(f"observation must be CameraObservation or LidarObservation, got {type(observation).__name__}.")
-        if lidar_observation is not None:
-            raise NotImplementedError("lidar_observation: lidar integration is not part of this mapper")
-        if camera_observation is None:
-            raise TypeError("integrate() requires a camera_observation or one positional observation.")
-        depth, intrinsics, position, quaternion = self._camera_tensors(camera_observation)
+        if lidar_observation is not None and self._lidar is None:
+            raise NotImplementedError("lidar_observation: this mapper was built without lidars; enable lidar integration with "
+                                      "Mapper(cfg, lidar=MapperLidarCfg(num_sensors=..., image_height=..., image_width=...))")
+        if camera_observation is None and lidar_observation is None:
+            raise TypeError("integrate() requires a camera_observation, a lidar_observation or one positional observation.")
+        camera = None if camera_observation is None else self._camera_tensors(camera_observation)
+        lidar = None if lidar_observation is None else self._lidar_tensors(lidar_observation)
         t = self._tsdf
         if self._frame_count > 0 and (self._time_decay < 1.0 or self._frustum_decay < 1.0):  # integrator_tsdf.py:617-620
-            D.decay_frustum_aware_multi_camera(t, intrinsics, position, quaternion, depth.shape[1:], self.config.depth_minimum_distance,
-                                               self.config.depth_maximum_distance, self._time_decay, self._frustum_decay)
+            if lidar is None:
+                depth, intrinsics, position, quaternion = camera
+                D.decay_frustum_aware_multi_camera(t, intrinsics, position, quaternion, depth.shape[1:], self.config.depth_minimum_distance,
+                                                   self.config.depth_maximum_distance, self._time_decay, self._frustum_decay)
+            else:
+                kw = {}
+                if camera is not None:
+                    kw = dict(camera_intrinsics=camera[1], camera_positions=camera[2], camera_quaternions=camera[3],
+                              camera_img_shape=tuple(camera[0].shape[1:]))
+                D.decay_frustum_aware_multi_sensor(t, **kw, camera_depth_minimum_distance=self.config.depth_minimum_distance,
+                                                   camera_depth_maximum_distance=self.config.depth_maximum_distance, lidar_positions=lidar[1],
+                                                   lidar_quaternions=lidar[2], lidar_valid_range_m=lidar[3], lidar_elevation_range_rad=lidar[4],
+                                                   lidar_img_shape=tuple(lidar[0].shape[1:]), time_decay=self._time_decay,
+                                                   frustum_decay=self._frustum_decay)
         B.mapper_clear_mask(t.frame_visible)
-        B.mapper_mark_blocks(t.frame_visible, t.block_visible, depth, intrinsics, position, quaternion, self._params)
-        B.mapper_integrate(t.block_data, t.frame_visible, depth, intrinsics, position, quaternion, self._params)
+        if camera is not None:
+            B.mapper_mark_blocks(t.frame_visible, t.block_visible, *camera, self._params)
+            B.mapper_integrate(t.block_data, t.frame_visible, *camera, self._params)
+        if lidar is not None:  # after the cameras (integrator_tsdf.py:485-492); the lidar sums go to the blocks the LIDARS marked
+            vs = float(self.config.voxel_size)
+            B.mapper_clear_mask(t.lidar_frame_visible)
+            B.mapper_lidar_mark_blocks(t.lidar_frame_visible, t.frame_visible, t.block_visible, *lidar, self._params)
+            B.mapper_lidar_integrate(t.block_data, t.lidar_frame_visible, *lidar, self._params,
+                                     float(self._lidar.linear_interpolation_max_allowable_difference_vox) * vs,
+                                     float(self._lidar.nearest_interpolation_max_allowable_dist_to_ray_vox) * vs)
         self._frame_count += 1
         self._last_voxel_grid = None
+
+    def _lidar_tensors(self, obs: LidarObservation):
+        """the observation checked by the reference's rules (integrator_tsdf.py:709-835; there the colour image is required, here it
+        may be left out, and it is not used): (range_image, position, quaternion, valid_range_m, elevation_range_rad) on the device"""
+        cfg = self._lidar
+        expected = (cfg.num_sensors, cfg.image_height, cfg.image_width)
+        r = obs.range_image
+        if r is None:
+            raise ValueError("LidarObservation.range_image is required.")
+        if r.dim() != 3:
+            raise ValueError(f"range_image must be (num_lidars, H, W), got shape {tuple(r.shape)}.")
+        if tuple(r.shape) != expected:
+            raise ValueError(f"range_image shape mismatch: expected {expected}, got {tuple(r.shape)}.")
+        if r.dtype != torch.float32:
+            raise ValueError(f"range_image dtype must be torch.float32, got {r.dtype}.")
+        if obs.rgb_image is not None:
+            if tuple(obs.rgb_image.shape) != expected + (3,):
+                raise ValueError(f"rgb_image shape mismatch: expected {expected + (3,)}, got {tuple(obs.rgb_image.shape)}.")
+            if obs.rgb_image.dtype != torch.uint8:
+                raise ValueError(f"rgb_image dtype must be torch.uint8, got {obs.rgb_image.dtype}.")
+        if obs.feature_grid is not None:
+            raise NotImplementedError("LidarObservation.feature_grid was provided but feature_dim == 0: feature channels are not part of "
+                                      "this mapper")
+        if obs.pose is None:
+            raise ValueError("LidarObservation.pose is required.")
+        n = cfg.num_sensors
+        f32 = dict(device=self._device, dtype=torch.float32)
+        position, quaternion = obs.pose.position.to(**f32).reshape(-1, 3), obs.pose.quaternion.to(**f32).reshape(-1, 4)
+        if position.shape[0] != n or quaternion.shape[0] != n:
+            raise ValueError(f"LidarObservation.pose holds {position.shape[0]} lidars, range_image {n}")
+        bounds = []
+        for name in ("valid_range_m", "elevation_range_rad"):
+            v = getattr(obs, name)
+            if v is None:
+                raise ValueError(f"LidarObservation.{name} is required.")
+            if tuple(v.shape) != (n, 2):
+                raise ValueError(f"{name} must be (num_lidars, 2), got shape {tuple(v.shape)}.")
+            if v.dtype != torch.float32:
+                raise ValueError(f"{name} dtype must be torch.float32, got {v.dtype}.")
+            bounds.append(v.to(**f32).contiguous())
+        if cfg.image_height == 1 and not torch.allclose(bounds[1][:, 0], bounds[1][:, 1]):
+            raise ValueError("Planar LiDAR with image_height == 1 requires elevation_range_rad[:, 0] == elevation_range_rad[:, 1].")
+        return r.to(**f32).contiguous(), position.contiguous(), quaternion.contiguous(), bounds[0], bounds[1]
 
     def _camera_tensors(self, obs: CameraObservation):
         if obs.depth_image is None or obs.intrinsics is None or obs.pose is None:
@@ -207,6 +315,7 @@ class Mapper:
         t.block_data.zero_()
         t.block_visible.zero_()
         t.frame_visible.zero_()
+        t.lidar_frame_visible.zero_()
         t.block_recycled.zero_()
         self._frame_count = 0
         self._last_voxel_grid = None
@@ -358,7 +467,7 @@ class Mapper:
 
     def memory_usage_mb(self) -> float:
         t = self._tsdf
-        tensors = (t.block_data, t.block_visible, t.frame_visible, t.block_recycled, self._sites, self._sites_scratch, self._dist_field)
+        tensors = (t.block_data, t.block_visible, t.frame_visible, t.lidar_frame_visible, t.block_recycled, self._sites, self._sites_scratch, self._dist_field)
         return sum(x.numel() * x.element_size() for x in tensors) / (1024.0 * 1024.0)
 
     def get_stats(self) -> dict:

@@ -14,6 +14,49 @@ ESDF_MAX_AXIS = 1024
 _BLOCK_SIZES = (1, 2, 4, 8, 16, 32)
 
 
+def _plain_int(name: str, value) -> int:
+    if not isinstance(value, int) or isinstance(value, bool):
+        raise ValueError(f"{name} must be a plain int, got {type(value).__name__} ({value!r})")
+    return value
+
+
+@dataclass
+class MapperLidarCfg:
+    """The lidar settings of :class:`Mapper`, handed to its constructor: ``Mapper(cfg, lidar=MapperLidarCfg(...))``.  The fields are
+    the reference's ``MapperCfg.lidar_*`` (``mapper_cfg.py:138-158``) without the prefix, with its checks (``constants.py:179-263``):
+    ``num_sensors`` range images of ``image_height`` x ``image_width`` pixels per frame (``image_height == 1``: a planar scan);
+    a bilinear range is accepted when no corner differs from it by more than
+    ``linear_interpolation_max_allowable_difference_vox`` voxels, the nearest pixel's when the voxel lies within
+    ``nearest_interpolation_max_allowable_dist_to_ray_vox`` voxels of that pixel's ray.
+
+    ``max_visible_blocks_per_lidar_integration`` and ``max_support_pixels_per_block_lidar`` are accepted, checked as the
+    reference checks them, and have no effect: the map is dense, so no list of visible blocks is sized, and there is no colour
+    or feature channel for the support pixels to gather."""
+
+    num_sensors: int = 1
+    image_height: Optional[int] = None
+    image_width: Optional[int] = None
+    linear_interpolation_max_allowable_difference_vox: float = 2.0
+    nearest_interpolation_max_allowable_dist_to_ray_vox: float = 0.5
+    max_visible_blocks_per_lidar_integration: Optional[int] = None
+    max_support_pixels_per_block_lidar: int = 8
+
+    def __post_init__(self):
+        if _plain_int("num_sensors", self.num_sensors) <= 0:
+            raise ValueError(f"num_sensors must be positive: {self.num_sensors}")
+        if self.image_height is None or self.image_width is None:
+            raise ValueError("MapperLidarCfg requires image_height and image_width")
+        if _plain_int("image_height", self.image_height) <= 0 or _plain_int("image_width", self.image_width) <= 0:
+            raise ValueError(f"image_height and image_width must be positive, got {self.image_height}x{self.image_width}")
+        if _plain_int("max_support_pixels_per_block_lidar", self.max_support_pixels_per_block_lidar) <= 0:
+            raise ValueError(f"max_support_pixels_per_block_lidar must be positive: {self.max_support_pixels_per_block_lidar}")
+        for name in ("linear_interpolation_max_allowable_difference_vox", "nearest_interpolation_max_allowable_dist_to_ray_vox"):
+            if not float(getattr(self, name)) > 0.0:
+                raise ValueError(f"{name} must be positive: {getattr(self, name)}")
+        if self.max_visible_blocks_per_lidar_integration is not None and self.max_visible_blocks_per_lidar_integration <= 0:
+            raise ValueError(f"max_visible_blocks_per_lidar_integration must be positive: {self.max_visible_blocks_per_lidar_integration}")
+
+
 @dataclass
 class MapperCfg:
     """Grid, sensor and ESDF settings of :class:`Mapper`.
@@ -34,6 +77,11 @@ class MapperCfg:
     integrator has them instead: ``Mapper(cfg, time_decay=..., frustum_decay=...)``, or call ``Mapper.decay_and_recycle`` /
     ``perception.mapper.decay`` yourself.  Lifting the refusal is a two-line follow-up: drop the two rows of the refusal table
     below and hand the fields to ``Mapper`` as its defaults.
+
+    Lidar range-image integration IS built as well, and ``lidar_num_sensors`` > 0 is refused here for the same reason (the same
+    test pins it).  Configure the sensors at the constructor: ``Mapper(cfg, lidar=MapperLidarCfg(num_sensors=...,
+    image_height=..., image_width=...))``.  Lifting the refusal is the same kind of follow-up: drop the ``lidar_num_sensors`` row
+    and build the ``MapperLidarCfg`` from ``lidar_*`` fields here.
     """
 
     # grid

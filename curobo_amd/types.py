@@ -703,6 +703,57 @@ class CameraObservation:
                                  pose=None if self.pose is None else self.pose.stack(new_observation.pose), **kw)
 
 
+@dataclass
+class LidarObservation:
+    """one frame of a batch of spinning lidars as range images (reference ``_src/types/lidar.py``): ``range_image`` float32
+    ``(num_lidars, H, W)`` metres, the EUCLIDEAN range from the sensor's origin (not a z-depth); column ``px`` looks along the
+    azimuth ``px 2 pi / W - pi`` of the sensor frame, row ``py`` along the elevation ``max - py (max - min) / (H - 1)``.
+    ``rgb_image`` uint8 ``(n, H, W, 3)`` and ``feature_grid`` fp16 ``(n, fH, fW, feature_dim)`` are registered to the same
+    pixels; ``pose`` the sensors in the world; ``valid_range_m`` ``(n, 2)`` = [min, max] metres; ``elevation_range_rad`` ``(n, 2)``
+    = [min, max] radians, equal for a planar scan (``H == 1``)."""
+
+    name: str = "lidar_range_image"
+    range_image: Optional[torch.Tensor] = None
+    rgb_image: Optional[torch.Tensor] = None
+    feature_grid: Optional[torch.Tensor] = None
+    pose: Optional["Pose"] = None
+    valid_range_m: Optional[torch.Tensor] = None
+    elevation_range_rad: Optional[torch.Tensor] = None
+    timestamp: Optional[torch.Tensor] = None
+
+    _TENSORS = ("range_image", "rgb_image", "feature_grid", "valid_range_m", "elevation_range_rad", "timestamp")
+
+    @property
+    def shape(self):
+        if self.range_image is None:
+            raise ValueError("range_image is None, cannot get shape")
+        return self.range_image.shape
+
+    def copy_(self, new_data: "LidarObservation") -> "LidarObservation":
+        """in place, into the tensors this observation already holds"""
+        for k in ("range_image", "valid_range_m", "elevation_range_rad"):
+            if getattr(self, k) is not None:
+                getattr(self, k).copy_(getattr(new_data, k))
+        for k in ("rgb_image", "feature_grid", "timestamp"):
+            if getattr(self, k) is not None and getattr(new_data, k) is not None:
+                getattr(self, k).copy_(getattr(new_data, k))
+        if self.pose is not None:
+            self.pose.copy_(new_data.pose)
+        return self
+
+    def clone(self) -> "LidarObservation":
+        kw = {k: (None if getattr(self, k) is None else getattr(self, k).clone()) for k in self._TENSORS}
+        return LidarObservation(name=self.name, pose=None if self.pose is None else self.pose.clone(), **kw)
+
+    def to(self, device) -> "LidarObservation":
+        for k in self._TENSORS:
+            if getattr(self, k) is not None:
+                setattr(self, k, getattr(self, k).to(device=device))
+        if self.pose is not None:
+            self.pose = self.pose.to(device=device)
+        return self
+
+
 class _FramePoseMembers:
     """what the reference's ``ToolPose`` [batch, horizon, links, 3 | 4] and ``GoalToolPose`` [batch, horizon, links, goal set, 3 | 4]
     share (types/tool_pose.py:54-163, 214-357): the per-frame accessors and the tensor-wise copies, on ``tool_frames`` /

@@ -1300,6 +1300,52 @@ int curobo_hip_mapper_decay(void *block_data, uint8_t *block_mask, uint8_t *recy
                             float factor_outside, float factor_inside, float empty_threshold,
                             const curobo_hip_mapper_params *params, curobo_hip_stream_t stream);
 
+/* The same launch over the union of the frusta of n_cameras cameras AND n_lidars lidars (reference kernel/wp_decay.py :152-291,
+ * builder_decay.py :217-313); either set may be empty (its pointers null) and with both empty factor_outside holds throughout.
+ * lidar_position [n_lidars, 3], lidar_quaternion [n_lidars, 4] wxyz, lidar_valid_range [n_lidars, 2] = (min, max) metres,
+ * lidar_elevation_range [n_lidars, 2] = (min, max) radians, lidar_height the rows of the range image (1: a planar scan).  In the
+ * frustum of lidar l, with rho the range of the block's centre in the lidar frame, el = atan2(z, |xy|) its elevation and r as
+ * above: not when rho + r < min or rho - r > max; else with the angular radius a = asin(r / rho) (pi when rho <= r): for
+ * lidar_height == 1 iff |el - (min_el + max_el) / 2| <= a, otherwise iff el + a >= min_el and el - a <= max_el.  A lidar sees
+ * every azimuth; no range image is read.  curobo_hip_mapper_decay is this entry with n_lidars = 0. */
+int curobo_hip_mapper_decay_sensors(void *block_data, uint8_t *block_mask, uint8_t *recycled, const float *intrinsics,
+                                    const float *cam_position, const float *cam_quaternion, int n_cameras, int height, int width,
+                                    const float *lidar_position, const float *lidar_quaternion, const float *lidar_valid_range,
+                                    const float *lidar_elevation_range, int n_lidars, int lidar_height, float factor_outside,
+                                    float factor_inside, float empty_threshold, const curobo_hip_mapper_params *params,
+                                    curobo_hip_stream_t stream);
+
+/* ---- lidar range images into the same TSDF (csrc/mapper_lidar.hip; reference kernel/builder/builder_lidar_integrate.py :75-180,
+ * :244-467).  range [n_lidars, height, width] metres is the EUCLIDEAN range from the sensor, lidar_position [n_lidars, 3],
+ * lidar_quaternion [n_lidars, 4] wxyz the sensors in the world, valid_range [n_lidars, 2] = (min, max) metres, elevation_range
+ * [n_lidars, 2] = (min, max) radians.  Pixel (px, py) looks along azimuth px 2 pi / width - pi (no half pixel) and elevation
+ * max_el - py (max_el - min_el) / (height - 1) (min_el when height == 1): ray = (cos az cos el, sin az cos el, sin el).
+ *
+ * mark: one lane per (lidar, pixel, sample).  A pixel with range in [min, max] is walked along its ray from
+ * max(range - truncation, min) in steps of step_size while r <= range + truncation + step_size; the block of every sample
+ * lidar_position + R(q) (ray r) that falls into the grid gets 1 in lidar_mask (what the integration reads), frame_mask (the
+ * frame's union with the cameras') and block_mask: plain byte stores of the same value, fp32 throughout. */
+int curobo_hip_mapper_lidar_mark_blocks(uint8_t *lidar_mask, uint8_t *frame_mask, uint8_t *block_mask, const float *range,
+                                        const float *lidar_position, const float *lidar_quaternion, const float *valid_range,
+                                        const float *elevation_range, const curobo_hip_mapper_params *params, int n_lidars,
+                                        int height, int width, curobo_hip_stream_t stream);
+
+/* One workgroup per block, returning at once where lidar_mask is 0.  Per voxel and lidar: the centre (x, y, z) in the lidar
+ * frame, its range rho in [min, max]; el = atan2(z, |xy|), for height > 1 in [min_el, max_el] and v = (max_el - el)(height - 1)
+ * / (max_el - min_el), else v = 0; u = (atan2(y, x) + pi) width / (2 pi) wrapped into [0, width).  The surface range is
+ * bilinear over rows floor(v), floor(v) + 1 and columns floor(u), (floor(u) + 1) mod width when height > 1, 0 <= floor(v) <
+ * height - 1, all four ranges are valid and none differs from the result by more than linear_max_diff_m; else that of the
+ * nearest pixel (floor(u + 0.5) wrapped, floor(v + 0.5) inside the image), valid, with the voxel within nearest_max_dist_m of
+ * that pixel's ray; else the lidar contributes nothing.  sdf = surface - rho >= -truncation, clamped to truncation, weight 1.
+ * (x, y, z), rho, el, u, v, the bilinear sum and the difference are evaluated in double from the fp32 inputs, with pi and 2 pi the
+ * fp32 constants widened (the sdf cancels at the surface and depends on u, v through the image's slope); the ray distance is
+ * fp32.  The sums over the lidars are fp32; where the summed weight is > 0 they are added to the stored pair in fp32 and
+ * rounded once to fp16. */
+int curobo_hip_mapper_lidar_integrate(void *block_data, const uint8_t *lidar_mask, const float *range, const float *lidar_position,
+                                      const float *lidar_quaternion, const float *valid_range, const float *elevation_range,
+                                      const curobo_hip_mapper_params *params, int n_lidars, int height, int width,
+                                      float linear_max_diff_m, float nearest_max_dist_m, curobo_hip_stream_t stream);
+
 /* ---- mesh extraction: marching cubes over the ever-visible blocks (reference kernel/builder/builder_mesh.py,
  * builder_raycast.py :63-375, marching_cubes/kernel/wp_mc_common.py :464-489, wp_mc_filter.py).  block_list int32 [n_slots]
  * holds the rows of the ever-visible blocks in ascending order, block_slot int32 [n_blocks] the slot of a block or -1.
